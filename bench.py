@@ -10,7 +10,11 @@ For N > 1 every rank owns its own batch of the same shape (utterances are
 independent units: no data-path collective; "scaling": "weak").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--utts U]
-                    [--workload fixed120|sweep|rt64|rt64pbp|l1]
+                    [--workload fixed120|sweep|rt64|rt64pbp|l1] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the headline line.  `--full` adds everything
+else this file measures or checks (the objects listed below, the other workloads' legs, the sanity
+guard); `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this script its own
 launcher: it starts N copies of itself (one process per GPU, RANK / LOCAL_RANK /
@@ -18,7 +22,7 @@ WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set) and relays rank 0's JSON l
 Under `python -m torch.distributed.run --nproc-per-node N` the environment is already
 there and the script is one rank.  Every rank asserts world size == --gpus.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
+Prints ONE JSON line on rank 0 (contract in the task statement); with `--full` it carries the extra objects
   roofline      SURVEY 8(d): whole-path achieved_fp32 / achieved_hbm from F_alg / B_alg per frame,
                 plus the dominant kernel (largest share of GPU time, HIP-event timed on the
                 context's stream inside the timed region) priced on ALGORITHMIC work: unique
@@ -80,6 +84,43 @@ def make_batch_inputs(utts, f0_of, device):
             acc.append((s + 0.01 * torch.as_tensor(noise, device=device, dtype=torch.float64)).float())
         x[u0:u0 + len(acc)] = torch.stack(acc).cpu().numpy()
     return x
+
+
+# ------------------------------------------------------------------ outputs (--dump-outputs)
+DUMP_UTTS = 16                 # a fixed, seeded sample of the utterances: the rows of a whole batch are about 1 GB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def batch_outputs(b, ids, n_utt):
+    """{name: array id} -> {name: the rows of the sampled utterances}, frame rows and waveforms cut at each
+    utterance's own offsets; what a caller downloads after the step, restricted to the sample."""
+    import libllsm2_amd as llsm
+    pick = np.sort(np.random.default_rng(0).choice(n_utt, min(n_utt, DUMP_UTTS), replace=False))
+    out = {}
+    for name, aid in ids.items():
+        a = b.download(aid)
+        off = b.y_off if aid in (llsm.A_Y, llsm.A_YSIN, llsm.A_YNOISE) else b.frm_off
+        out[name] = np.concatenate([a[off[u]:off[u + 1]] for u in pick])
+    return out
+
+
+def dump_outputs(path, arrays):
+    """{name: array} -> path/<name>.npy; float32 rows as they are, integer rows as float64 (exact)."""
+    arrays = {k: np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def layer0_ids(llsm):
+    """the eleven parameter rows and the three waveforms of an analysed + resynthesised batch"""
+    return {"f0": llsm.A_F0, "nhar": llsm.A_NHAR, "ampl": llsm.A_AMPL, "phse": llsm.A_PHSE, "psd": llsm.A_PSD,
+            "psdres": llsm.A_PSDRES, "has_psdres": llsm.A_HAS_PSDRES, "edc": llsm.A_EDC, "nhar_e": llsm.A_NHAR_E,
+            "eenv_ampl": llsm.A_EENV_AMPL, "eenv_phse": llsm.A_EENV_PHSE,
+            "y": llsm.A_Y, "y_sin": llsm.A_YSIN, "y_noise": llsm.A_YNOISE}
 
 
 # ------------------------------------------------------- algorithmic work (SURVEY 8d)
@@ -419,7 +460,7 @@ def bench_rt(args, llsm, world, rank, local, dev, dist, placement=None, workload
     return None
 
 
-def bench_l1(args, llsm, world, rank, local, dev, dist, placement=None, steps=None, warmup=None, x=None):
+def bench_l1(args, llsm, world, rank, local, dev, dist, placement=None, steps=None, warmup=None, x=None, dump=None):
     """SURVEY 8(f) rank 1 / BASELINE.json configs[4] shape on the batch API: the analysed config-2 batch is taken to
     layer 1 (Rd fit, vocal-tract envelope, phase residual), its harmonic models are dropped and the frames
     i % 100 > 50 marked PBPSYN (the pattern of test-layer1-anasynth.c:34-39); one step = llsm_gpu_batch_tolayer1 +
@@ -474,6 +515,10 @@ def bench_l1(args, llsm, world, rank, local, dev, dist, placement=None, steps=No
     dt = time.perf_counter() - t0
     prof = ctx.profile(); ctx.set_profiling(False)
     dt, frames_all = reduce_timing(dt, U * NFRM * steps, dev)
+    if dump and rank == 0:
+        dump_outputs(dump, batch_outputs(b, {"rd": llsm.A_RD, "vtmagn": llsm.A_VTMAGN, "vsphse": llsm.A_VSPHSE,
+                                             "nvsphse": llsm.A_NVSPHSE, "y": llsm.A_Y, "y_sin": llsm.A_YSIN,
+                                             "y_noise": llsm.A_YNOISE}, U))
     y = b.download(llsm.A_Y)[: b.y_off[1]]
     ok = bool(np.all(np.isfinite(y)) and 0.5 < np.sqrt(np.mean(y[4000:40000] ** 2)) / np.sqrt(np.mean(x[0, 4000:40000] ** 2)) < 1.5)
     if rank == 0:
@@ -671,9 +716,11 @@ def measure_e2e(args, llsm, local, ao, so, x, f0, U, fence, reduce):
                     "others compute"}
 
 
-def bench_layer0(args, llsm, world, rank, local, dev, dist, placement, workload, steps, warmup, full=True):
+def bench_layer0(args, llsm, world, rank, local, dev, dist, placement, workload, steps, warmup, mode="full", dump=None):
     """analyse + resynthesise a resident batch (BASELINE.json configs[1] `fixed120`, configs[2] `sweep`); returns
-    (rank 0's result dict | None, this rank's input waveforms)."""
+    (rank 0's result dict | None, this rank's input waveforms).  mode "plain": the timed steps and the headline figures
+    only; "full": with the survey pass, the roofline objects, the sanity guard and value_e2e; "leg": a leg of
+    `other_workloads` (survey pass and sanity guard, headline figures)."""
     from libllsm2_amd.sharding import gather_rank_times, reduce_timing, shard_strided, sweep_f0
     import torch
     total_u = args.utts * world                        # weak scaling: per-GPU work is fixed
@@ -708,40 +755,66 @@ def bench_layer0(args, llsm, world, rank, local, dev, dist, placement, workload,
         if world > 1:
             dist.barrier()
 
+    def headline(value, dt):
+        return {"metric": "frames/sec (layer0 analyze+synth, 44.1 kHz, 5 ms hop)", "value": value,
+                "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+                "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak",
+                "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "config": {"workload": f"{U} synthetic 1 s utterances per GPU, F0 "
+                                       f"{'120 Hz fixed' if workload == 'fixed120' else '80-400 Hz log sweep'}"
+                                       ", 44.1 kHz, 5 ms hop, layer0 analyze+synth, default options, f0_refine=0",
+                           "utterances_per_gpu": U, "frames_per_utterance": NFRM, "parallelism": f"dp{world}"}}
+
     for i in range(warmup):
         step(i)
     fence()
+    plain = mode == "plain"
     # Survey pass (UNTIMED, after the warm-up): HIP events around every launch of a few steps -- which kernel is the dominant
     # one, and the per-kernel times of `roofline_other_kernels` / `kernels_ms_per_step`.
     # The survey runs every launch on ONE stream (llsm_gpu_analysis_overlap(0)): each kernel's time is its time alone.
-    survey_steps = max(2, min(5, steps))
-    llsm.load().llsm_gpu_analysis_overlap(0)
-    ctx.set_profiling(True)
-    ctx.reset_profile()
-    for i in range(survey_steps):
-        step(10000 + i)
-    fence()
-    prof = ctx.profile()
-    llsm.load().llsm_gpu_analysis_overlap(1)
-    dom = max(prof.items(), key=lambda kv: kv[1][0])[0]
     # Timed region: the product path as a caller runs it, with events around the launches of the DOMINANT kernel only
     # (two events per step: the roofline's `avg_launch_ms` is measured live here, on the stream that kernel is launched on).
     # Rounds 1 - 5 kept the events around EVERY launch in the timed region, which also switched the analysis' second stream
     # off: the timed step was a serialised, instrumented variant of the product (about 0.2 ms longer).
-    ctx.set_profiling(True, only=dom)
-    ctx.reset_profile()
+    # A plain run has neither the survey nor the events: its timed region is the product path alone.
+    if not plain:
+        survey_steps = max(2, min(5, steps))
+        llsm.load().llsm_gpu_analysis_overlap(0)
+        ctx.set_profiling(True)
+        ctx.reset_profile()
+        for i in range(survey_steps):
+            step(10000 + i)
+        fence()
+        prof = ctx.profile()
+        llsm.load().llsm_gpu_analysis_overlap(1)
+        dom = max(prof.items(), key=lambda kv: kv[1][0])[0]
+        ctx.set_profiling(True, only=dom)
+        ctx.reset_profile()
     t0 = time.perf_counter()
     for i in range(steps):
         step(warmup + i)
     fence()
     dt = time.perf_counter() - t0
-    prof_timed = ctx.profile()
-    ctx.set_profiling(False)
-    prof = {k: (v[0] * steps / survey_steps, v[1] * steps / survey_steps) for k, v in prof.items()}   # scaled to `steps` steps
-    if dom in prof_timed:
-        prof[dom] = prof_timed[dom]                      # the dominant kernel: as measured inside the timed region
+    if not plain:
+        prof_timed = ctx.profile()
+        ctx.set_profiling(False)
+        prof = {k: (v[0] * steps / survey_steps, v[1] * steps / survey_steps) for k, v in prof.items()}   # scaled to `steps` steps
+        if dom in prof_timed:
+            prof[dom] = prof_timed[dom]                  # the dominant kernel: as measured inside the timed region
     rank_ms = gather_rank_times(dt / steps * 1e3, rank, world)           # every rank's own ms per step (imbalance shows here)
     dt, frames_all = reduce_timing(dt, U * NFRM * steps, dev)   # MAX over ranks, SUM of frames
+    if dump and rank == 0:
+        dump_outputs(dump, batch_outputs(b, layer0_ids(llsm), U))
+    if plain:
+        out = None
+        if rank == 0:
+            out = {**headline(frames_all / dt, dt), "rank_ms_per_step": rank_ms,
+                   "rank_ms_spread": (max(rank_ms) / min(rank_ms)) if min(rank_ms) > 0 else None,
+                   "backend": (placement or {}).get("backend"), "partition": "strided (utterance u -> rank u mod N)",
+                   "placement": placement}
+        b.close()
+        ctx.close()
+        return out, x
 
     # parity guard inside the bench: outputs finite and energy-preserving
     y = b.download(llsm.A_Y)[: b.y_off[1]]
@@ -753,7 +826,7 @@ def bench_layer0(args, llsm, world, rank, local, dev, dist, placement, workload,
     # host threads, so the transfers of one overlap the kernels of the others -- the arrangement the library's own
     # fan-out (llsm_gpu_set_fanout, csrc/capi.cpp) uses.  Reported beside `value`, never as it.
     e2e = None
-    if full and not args.no_e2e:
+    if mode == "full" and not args.no_e2e:
         e2e = measure_e2e(args, llsm, local, ao, so, x, f0, U, fence, lambda dte, n: reduce_timing(dte, U * NFRM * n, dev))
 
     out = None
@@ -829,21 +902,14 @@ def bench_layer0(args, llsm, world, rank, local, dev, dist, placement, workload,
                     "cannot reach 40 % of 8 TB/s); dominant kernel priced on algorithmic work (unique bytes in + out for "
                     "streaming kernels), traffic = rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this command"})
         others = [roof_of(k) for k, _ in sorted(prof.items(), key=lambda kv: -kv[1][0]) if k != dom][:8]
-        out = {"metric": "frames/sec (layer0 analyze+synth, 44.1 kHz, 5 ms hop)", "value": value,
-               "unit": "frames/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-               "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "config": {"workload": f"{U} synthetic 1 s utterances per GPU, F0 "
-                                      f"{'120 Hz fixed' if workload == 'fixed120' else '80-400 Hz log sweep'}"
-                                      ", 44.1 kHz, 5 ms hop, layer0 analyze+synth, default options, f0_refine=0",
-                          "utterances_per_gpu": U, "frames_per_utterance": NFRM, "parallelism": f"dp{world}"},
+        out = {**headline(value, dt),
                "roofline": roof, "roofline_other_kernels": others,
                "kernels_ms_per_step": {k: v[0] / steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
                "rank_ms_per_step": rank_ms, "rank_ms_spread": (max(rank_ms) / min(rank_ms)) if min(rank_ms) > 0 else None,
                "backend": (placement or {}).get("backend"),      # "nccl" (= RCCL) | "gloo" (only on explicit request) | None at N = 1
                "partition": "strided (utterance u -> rank u mod N)",
                "value_e2e": e2e, "sanity_ok": ok, "placement": placement}
-        if not full:                                   # a leg of `other_workloads`: the headline figures only
+        if mode == "leg":                              # a leg of `other_workloads`: the headline figures only
             out = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "config",
                                        "kernels_ms_per_step", "rank_ms_per_step", "rank_ms_spread", "partition", "sanity_ok")}
             out["roofline_frac_whole_path_fp32"] = roof["achieved_fp32"]
@@ -864,15 +930,22 @@ def main():
     ap.add_argument("--rt-hops", type=int, default=1, help="rt64*: hops per library call (llsm_rtsynth_group_feed_many when > 1)")
     ap.add_argument("--rt-pipeline", type=int, default=-1, help="rt64*: 1 / 0 = feeds return before the device has finished the hop (llsm_gpu_rt_pipeline) / synchronous feeds (default: library default = synchronous)")
     ap.add_argument("--rt-graph", type=int, default=-1, help="rt64*: 1 / 0 = one hipGraph launch per hop on / off (default: library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-other", action="store_true", help="skip the short sweep / rt64 / rt64pbp / l1 legs after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the survey pass and roofline objects, the sanity guard, value_e2e, the other workloads' legs "
+                         "and the CPU baseline (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (a fixed sample of the utterances)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip value_e2e")
+    ap.add_argument("--no-other", action="store_true", help="with --full: skip the short sweep / rt64 / rt64pbp / l1 legs after the headline")
     ap.add_argument("--e2e-parts", type=int, default=0, help="value_e2e: sub-batches in flight (one context + host thread each); 0 = sweep 2 / 4 / 8 and keep the best")
     ap.add_argument("--e2e-steps", type=int, default=12, help="value_e2e: timed steps per repetition (after 2 warm-up steps)")
     ap.add_argument("--e2e-reps", type=int, default=3, help="value_e2e: repetitions (min / median / max reported)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU-only check of the N-rank launch / reduction plumbing (gloo); no compute")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -925,18 +998,21 @@ def main():
                  "ranks": rank_devices}
 
     if args.workload in ("rt64", "rt64pbp"):
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not available for the llsmrt workloads")
         res = bench_rt(args, llsm, world, rank, local, dev, dist, placement)
     elif args.workload == "l1":
-        res = bench_l1(args, llsm, world, rank, local, dev, dist, placement)
+        res = bench_l1(args, llsm, world, rank, local, dev, dist, placement, dump=args.dump_outputs)
     else:
-        res, x = bench_layer0(args, llsm, world, rank, local, dev, dist, placement, args.workload, args.steps, args.warmup)
-        # BASELINE.json configs[2-4] inside the driver-timed run: short legs after the headline's timed region (a few
+        res, x = bench_layer0(args, llsm, world, rank, local, dev, dist, placement, args.workload, args.steps, args.warmup,
+                              mode="full" if args.full else "plain", dump=args.dump_outputs)
+        # BASELINE.json configs[2-4] inside a --full run: short legs after the headline's timed region (a few
         # seconds in all; `--no-other` skips them).  With several ranks only the sweep leg runs (it IS the multi-GPU
         # config); the llsmrt and layer-1 legs are single-GPU configs.
-        if args.workload == "fixed120" and not args.no_other:
+        if args.full and args.workload == "fixed120" and not args.no_other:
             others = {}
             t_legs = time.perf_counter()
-            r, _ = bench_layer0(args, llsm, world, rank, local, dev, dist, placement, "sweep", 3, 1, full=False)
+            r, _ = bench_layer0(args, llsm, world, rank, local, dev, dist, placement, "sweep", 3, 1, mode="leg")
             others["sweep"] = r
             if world == 1:
                 # llsmrt: synchronous feeds (the reference's semantics: a feed returns with its samples in the rings) and,
@@ -967,7 +1043,7 @@ def main():
             if rank == 0:
                 res["other_workloads"] = others
                 res["other_workloads_wall_s"] = time.perf_counter() - t_legs
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(res))

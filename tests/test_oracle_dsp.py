@@ -55,16 +55,10 @@ def test_chebyshev_table_rows(o64):
 
 
 def test_chebyshev_table_vs_reference_header(o64):
-    """Spot check against the reference's own table when the tree is mounted."""
-    import os, re
-    path = "/root/reference/filter-coef.h"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
-    txt = open(path).read()
-    tabs = {}
-    for name in ("cheby_l_a", "cheby_l_b", "cheby_h_a", "cheby_h_b"):
-        m = re.search(name + r"\[240\]\s*=\s*\{([^}]*)\}", txt)
-        tabs[name] = np.array([float(v) for v in m.group(1).replace("\n", " ").split(",") if v.strip()]).reshape(48, 5)
+    """Spot check against the reference's own table (filter-coef.h's values, stored as
+    tests/golden/ref_cheby_tables.npz by tests/golden/make_ref_fixtures.py)."""
+    import os
+    tabs = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cheby_tables.npz"))
     for i in range(48):
         bl, al = o64.cheby1(4, 0.5, (i + 1) * 0.02, 0)
         bh, ah = o64.cheby1(4, 0.5, (i + 1) * 0.02, 1)

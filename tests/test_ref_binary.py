@@ -11,10 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "oracle", "_ref", "ref_test_structs")
 
 
-def test_reference_test_structs_passes_against_the_product():
+def test_reference_test_structs_passes_against_the_product(tmp_path):
     if not os.path.exists(EXE):
         if not os.path.isdir("/root/reference"):
             pytest.skip("oracle/_ref/ref_test_structs not built and no reference tree here")
         subprocess.run(["bash", os.path.join(ROOT, "oracle", "build_ref_tests.sh")], check=True)
-    r = subprocess.run([EXE], cwd="/tmp", capture_output=True, text=True, timeout=120)
+    r = subprocess.run([EXE], cwd=tmp_path, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -15,6 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from libllsm2_amd.sharding import reduce_timing, shard_range, shard_strided, sweep_f0, utt_cost  # noqa: E402
 
+# The bench's launcher self-tests are CPU-only plumbing checks: their ranks see no device, also on a machine that has one
+# (a rank whose LOCAL_RANK names a device the node lacks would otherwise fail on a 1-GPU machine).
+NO_DEVICES = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
 
 def test_shard_range_partitions():
     for total in (0, 1, 7, 8, 1024, 8192, 1000):
@@ -89,6 +93,7 @@ def test_bench_launcher_spawns_n_ranks(backend):
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(NO_DEVICES)
     env["LLSM_BENCH_BACKEND"] = backend
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--utts", "128",
                           "--launcher-selftest"], env=env, capture_output=True, text=True, timeout=240)
@@ -116,6 +121,7 @@ def test_bench_under_torchrun_falls_back_to_gloo_when_rccl_is_unavailable():
     import subprocess
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LLSM_BENCH_BACKEND")}
+    env.update(NO_DEVICES)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                           "--gpus", "2", "--utts", "5", "--launcher-selftest"], env=env, capture_output=True, text=True, timeout=240)
@@ -128,7 +134,7 @@ def test_bench_under_torchrun_falls_back_to_gloo_when_rccl_is_unavailable():
 
 def test_bench_refuses_world_size_mismatch():
     import subprocess
-    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
+    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", **NO_DEVICES)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launcher-selftest"],
                          env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode != 0 and "WORLD_SIZE" in (out.stderr + out.stdout)
@@ -163,6 +169,7 @@ def _selftest(env_extra, gpus=2):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LLSM_BENCH_BACKEND",
                                                              "LLSM_BENCH_ASSUME_DEVICES")}
+    env.update(NO_DEVICES)
     env.update(env_extra)
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--utts", "16",
                            "--launcher-selftest"], env=env, capture_output=True, text=True, timeout=240)

@@ -7,8 +7,8 @@
 # Legs (arguments after ':' are comma-free, separated by ':'; a leg is one shell word):
 #   tests[:expr]            pytest -m gpu (optionally -k expr)
 #   smoke                   __graft_entry__.smoke()
-#   bench[:args]            python bench.py --gpus 1 <args with '+' for spaces> (default: --steps 20 --warmup 5)
-#   wl:NAME                 bench.py --workload NAME (sweep, rt64, rt64pbp, l1) without the cpu / e2e legs
+#   bench[:args]            python bench.py --gpus 1 --full <args with '+' for spaces> (default: --steps 20 --warmup 5)
+#   wl:NAME                 bench.py --full --workload NAME (sweep, rt64, rt64pbp, l1) without the cpu / e2e legs
 #   kbench:ABL1:ABL2...     tools/kbench.py per-kernel HIP-event times, product build first, then each ablation build
 #                           (exp_build/lib_<ABL>.so, made here beforehand with `tools/kbench.py --build --ablate ...`);
 #                           KB_UTTS / KB_STEPS override 1024 / 5
@@ -31,7 +31,7 @@ O=$REPO/gpurun_out/$TAG
 SETS=("SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU GRBM_GUI_ACTIVE"
       "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_VALU_MFMA_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VMEM"
       "SQ_WAIT_INST_LDS SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INST_LEVEL_VMEM")
-BARGS="--no-cpu-baseline --no-e2e --no-other"
+BARGS="--full --no-cpu-baseline --no-e2e --no-other"
 prof() {   # prof <dir> <rocprofv3 options...> -- <bench args...>   (run from /tmp, as the guide asks)
   local d=$1; shift
   (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 "$@" > ${O}_$d.log 2>&1)
@@ -46,9 +46,9 @@ for leg in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee ${O}_smoke.log ;;
     bench)
-      timeout 900 python bench.py --gpus 1 $( [ -n "$a1" ] && echo "${a1//+/ }" || echo "--steps 20 --warmup 5") 2>${O}_bench.err | tee ${O}_bench.json | cut -c1-400 ;;
+      timeout 900 python bench.py --gpus 1 --full $( [ -n "$a1" ] && echo "${a1//+/ }" || echo "--steps 20 --warmup 5") 2>${O}_bench.err | tee ${O}_bench.json | cut -c1-400 ;;
     wl)
-      timeout 400 python bench.py --workload $a1 --steps 5 --warmup 2 --no-cpu-baseline --no-e2e 2>${O}_bench_$a1.err | tee ${O}_bench_$a1.json | cut -c1-260 ;;
+      timeout 400 python bench.py --full --workload $a1 --steps 5 --warmup 2 --no-cpu-baseline --no-e2e 2>${O}_bench_$a1.err | tee ${O}_bench_$a1.json | cut -c1-260 ;;
     kbench)
       abl=""; for a in $a1 $a2 $a3 $a4 $a5 $a6; do abl="$abl $a"; done
       timeout 1200 python tools/kbench.py --utts ${KB_UTTS:-1024} --steps ${KB_STEPS:-5} --ablate $abl 2>&1 | tee -a ${O}_kbench.txt | cut -c1-700 ;;
