@@ -214,6 +214,50 @@ int llsm_gpu_batch_set_maxnhar_conf(llsm_gpu_batch* b, int maxnhar_conf);
 int llsm_gpu_batch_set_pbpeffect(llsm_gpu_batch* b, int frame, llsm_fgfm modifier, void* info,
   llsm_container* src_frame);
 
+/* ---- edits of a device-resident batch: the middle of the reference's time-stretch recipe (analyse, tolayer1,
+ * phasepropagate(-1), blend frames onto a new grid, tolayer0, phasepropagate(+1), synthesise) without leaving the device.
+ * All three are asynchronous; a refused call returns -1, sets llsm_gpu_last_error() and launches nothing.
+ *
+ * phasesync_rps   llsm_chunk_phasesync_rps over every frame.  The reference phase of a frame is VSPHSE[0] if layer1_based
+ *                 and NVSPHSE > 0, else PHSE[0] if the frame's HM rows are valid and NHAR > 0, else 0; the frame is shifted
+ *                 by minus it.
+ * phasepropagate  llsm_chunk_phasepropagate per utterance: frame i is shifted by
+ *                 (float)((double)acc_i * ((double)(float)(thop * sign) * 2 pi)), acc_i the float32 inclusive running sum of
+ *                 the utterance's F0 row in frame order.
+ *   A shift by theta maps phase k (0-based) to wrap(phi + theta (k + 1)) in float64 (llsm_frame_phaseshift) on: the first
+ *   NHAR entries of PHSE of voiced frames (F0 != 0) whose HM rows are valid (HAS_HM, when the batch has layer 1); the
+ *   first NHAR_E entries of every channel of EENV_PHSE of voiced frames; the first NVSPHSE entries of VSPHSE.  Nothing
+ *   else is written.  Both calls give rows bit-identical to the host functions on the same frames.
+ *
+ * retime          resamples every utterance of `src` (which it does not change) onto the frame grid of `dst`.  dst was
+ *                 created with src's options and sampling rate and the same number of utterances, with frame counts of
+ *                 its own (nx may be 0); src has layer 1 (llsm_gpu_batch_tolayer1).  dst gets layer 1 with src's nfft and
+ *                 takes over src's fnyq and maxnhar_conf.
+ *   pos         host, dst.total_frames floats: entry frm_off_dst[u] + i is the position of output frame i of utterance u in
+ *               source frames of that utterance, within [0, nfrm_src[u] - 1].  NULL: the uniform map
+ *               llsm_gpu_retime_uniform_positions(nfrm_src[u], nfrm_dst[u]).
+ *   psdres_src  host, dst.total_frames source frame indices (of the utterance): output frame i takes PSDRES and HAS_PSDRES
+ *               from that frame.  NULL: floor(pos).
+ *   Output frame at position t of an utterance of n source frames: a = min(floor(t), n - 2), b = a + 1, r = t - a (float32).
+ *   r == 0 or r == 1 (n == 1 included): a bit-exact copy of frame a or b.  Otherwise, with lin = x_a + (x_b - x_a) r in float32
+ *   and circ = atan2(lin(sin), lin(cos)):
+ *     both voiced  F0, RD lin; VTMAGN lin; VSPHSE circ over the first min(NVSPHSE) entries, the rest from the frame with the
+ *                  longer row; NVSPHSE = max
+ *     one voiced   F0, RD, VSPHSE, NVSPHSE of the voiced frame; VTMAGN its row + 20 log10(max(1e-8, w)) dB, w = r if b is the
+ *                  voiced frame, 1 - r if a is
+ *     neither      F0 = 0, RD = 1, layer-1 rows of frame a
+ *     VTMAGN is floored at -80 dB; PSD, EDC lin; EENV_AMPL lin and EENV_PHSE circ over the first min(NHAR_E) entries of each
+ *     channel, the rest from the longer frame, NHAR_E = max; PBPSYN of frame a; voiced output frames get NHAR = 0 and
+ *     HAS_HM = 0 (llsm_gpu_batch_tolayer0(dst, 1) rebuilds them), unvoiced ones frame a's NHAR, AMPL, PHSE and HAS_HM.
+ *   Per-frame effects (llsm_gpu_batch_set_pbpeffect) are not carried over.  An utterance's output depends on nothing else in
+ *   the batch.  Refused: differing options or utterance counts, different contexts, src == dst, src without layer 1, a NaN
+ *   or out-of-range position or psdres_src index, an utterance with frames on one side only, dst with layer 1 of another size.
+ * retime_uniform_positions  host only: pos[i] = min((float)i * nfrm_src / nfrm_dst, nfrm_src - 1) in float32, i < nfrm_dst. */
+int  llsm_gpu_batch_phasesync_rps(llsm_gpu_batch* b, int layer1_based);
+int  llsm_gpu_batch_phasepropagate(llsm_gpu_batch* b, int sign);
+int  llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* src, const FP_TYPE* pos, const int* psdres_src);
+void llsm_gpu_retime_uniform_positions(int nfrm_src, int nfrm_dst, FP_TYPE* pos);
+
 /* chunk <-> flat layer-1 rows (same row indexing as llsm_flat_params) */
 typedef struct {
   int nspec, maxnhar;

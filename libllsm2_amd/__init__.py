@@ -128,6 +128,7 @@ llsm_gpu_set_default_seed llsm_gpu_plan_index llsm_gpu_batch_set_fnyq llsm_gpu_b
 llsm_chunk_blob_size llsm_chunk_to_blob llsm_blob_view llsm_blob_to_chunk llsm_blob_view_l1 llsm_gpu_batch_upload_blob llsm_gpu_batch_upload_blobs
 llsm_create_rtsynth_group llsm_delete_rtsynth_group llsm_rtsynth_group_getlatency
 llsm_rtsynth_group_numoutput llsm_rtsynth_group_feed llsm_rtsynth_group_feed_many llsm_rtsynth_group_fetch llsm_rtsynth_group_fetch_all llsm_gpu_rt_graph llsm_gpu_rt_graph_hops llsm_gpu_rt_fused llsm_gpu_rt_direct llsm_gpu_rt_pipeline llsm_gpu_analysis_overlap llsm_slab_stats llsm_slab_trim llsm_delete_chunks llsm_gpu_release_cached_batches llsm_gpu_device_numa_node llsm_gpu_bind_thread_to_device llsm_gpu_batch_packed_words llsm_gpu_batch_download_packed llsm_gpu_batch_upload_packed llsm_gpu_batch_download_outputs llsm_gpu_batch_download_packed_block llsm_gpu_batch_upload_packed_block llsm_gpu_batch_transfer_many llsm_gpu_batch_params_layout llsm_gpu_batch_transfer_params llsm_gpu_shared_f0_tiles llsm_gpu_synth_tables llsm_gpu_pbp_real_ifft llsm_frame_compute_snr
+llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime llsm_gpu_retime_uniform_positions
 """.split()
 
 _lib = None
@@ -183,6 +184,11 @@ def load():
     L.llsm_gpu_batch_tolayer0.argtypes = [vp, C.c_int]
     L.llsm_gpu_batch_set_maxnhar_conf.argtypes = [vp, C.c_int]
     L.llsm_gpu_batch_set_pbpeffect.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.llsm_gpu_batch_phasesync_rps.argtypes = [vp, C.c_int]
+    L.llsm_gpu_batch_phasepropagate.argtypes = [vp, C.c_int]
+    L.llsm_gpu_batch_retime.argtypes = [vp, vp, P_fp, P_int]
+    L.llsm_gpu_retime_uniform_positions.argtypes = [C.c_int, C.c_int, P_fp]
+    L.llsm_gpu_retime_uniform_positions.restype = None
     L.llsm_chunk_to_flat_l1.argtypes = [C.POINTER(Chunk), C.POINTER(FlatL1), C.c_int]
     L.llsm_flat_l1_to_chunk.argtypes = [C.POINTER(FlatL1), C.c_int, C.POINTER(Chunk)]
     L.llsm_chunk_tolayer1.argtypes = [C.POINTER(Chunk), C.c_int]
@@ -303,6 +309,13 @@ def make_aoptions(**kw):
     o._cf = (fp * max(len(cf), 1))(*cf)
     o.chanfreq = C.cast(o._cf, P_fp)
     return o
+
+
+def retime_uniform_positions(nfrm_src, nfrm_dst):
+    """the source positions llsm_gpu_batch_retime uses without a map (llsm_gpu_retime_uniform_positions)"""
+    pos = np.zeros(max(int(nfrm_dst), 0), np.float32)
+    load().llsm_gpu_retime_uniform_positions(int(nfrm_src), int(nfrm_dst), pos.ctypes.data_as(P_fp))
+    return pos
 
 
 def make_soptions(fs, **kw):
@@ -443,6 +456,28 @@ class Batch:
 
     def tolayer0(self, only_missing=False):
         _check(self.L.llsm_gpu_batch_tolayer0(self.h, int(only_missing)), "tolayer0")
+
+    # ---- edits (llsm_gpu.h): the middle of the time-stretch recipe on the device
+    def phasesync_rps(self, layer1_based=False):
+        _check(self.L.llsm_gpu_batch_phasesync_rps(self.h, int(layer1_based)), "phasesync_rps")
+
+    def phasepropagate(self, sign):
+        _check(self.L.llsm_gpu_batch_phasepropagate(self.h, int(sign)), "phasepropagate")
+
+    def retime(self, src, pos=None, psdres_src=None):
+        """this batch's rows <- the frames of batch `src` blended onto this batch's frame grid (llsm_gpu_batch_retime);
+        pos: total_frames float32 source positions (None: the uniform map), psdres_src: total_frames source frame
+        indices for the PSDRES rows (None: floor(pos))"""
+        p = r = None
+        if pos is not None:
+            p = np.ascontiguousarray(pos, np.float32)
+            assert p.shape == (self.layout.total_frames,), p.shape
+        if psdres_src is not None:
+            r = np.ascontiguousarray(psdres_src, np.int32)
+            assert r.shape == (self.layout.total_frames,), r.shape
+        _check(self.L.llsm_gpu_batch_retime(self.h, src.h, None if p is None else p.ctypes.data_as(P_fp),
+                                            None if r is None else r.ctypes.data_as(P_int)), "retime")
+        self.nspec = src.nspec
 
     def synthesize(self, sopt, seed=0, injected_white=False):
         _check(self.L.llsm_gpu_batch_synthesize(self.h, C.byref(sopt), seed, int(injected_white)), "synthesize")

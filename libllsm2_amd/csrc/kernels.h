@@ -249,4 +249,22 @@ int launch_pbp_mix(LaunchCtx* P, int n_utt, int max_len, const int* out_off, con
   const int2* blk_jobs, const int* blk_off, const float* pulse_buf, const float* mixw, const float* ynoise,
   float* ysin, float* y);
 
+// ---- edits of a device-resident batch (modify_kernels.hip, modify.cpp) ----
+// Every parameter row of one batch; the layer-1 pointers are NULL (and nspec 0) when the batch has no layer 1.
+struct ModRows {
+  int nframes, maxnhar, maxnhar_e, npsd, nchannel, nspec;
+  float* f0; int* nhar; float* ampl; float* phse; float* psd; float* psdres; int* has_psdres; float* edc; int* nhar_e;
+  float* eenv_ampl; float* eenv_phse;
+  float* rd; float* vtmagn; float* vsphse; int* nvsphse; int* pbpsyn; int* has_hm;
+};
+// Frame-blending map of llsm_gpu_batch_retime: output frame g of utterance utt[g] sits at source position pos[g] of that
+// utterance (frames src_off[u] .. src_off[u] + src_nfrm[u]); res: source frame of its PSDRES row, NULL: floor(pos).
+struct RetimeMap { const float* pos; const int* res; const int* utt; const int* src_off; const int* src_nfrm; };
+// theta == NULL: each frame is shifted by minus its reference phase (llsm_frame_phasesync_rps); else by theta[frame]
+int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int layer1_based);
+// theta[frame] = (float)(running float32 sum of the utterance's F0 up to the frame x k2pi), llsm_chunk_phasepropagate
+int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, const int* nfrm, const float* f0,
+  double k2pi, float* theta);
+int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m);
+
 #endif

@@ -1,0 +1,135 @@
+// modify.cpp -- edits of a device-resident batch between analysis and synthesis: host side of modify_kernels.hip.
+//
+//   llsm_gpu_batch_phasesync_rps     llsm_chunk_phasesync_rps over every frame (model.cpp)
+//   llsm_gpu_batch_phasepropagate    llsm_chunk_phasepropagate per utterance (model.cpp)
+//   llsm_gpu_batch_retime            the frame-blending step of the reference's time-stretch recipe, onto the frame grid
+//                                    of another batch (rules: llsm_gpu.h)
+//   llsm_gpu_retime_uniform_positions  the map retime uses when it is given none
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "batch.h"
+
+namespace {
+const double kPi = 3.14159265358979323846;
+
+ModRows mod_rows(llsm_gpu_batch* b) {
+  ModRows r;
+  r.nframes = b -> lay.total_frames; r.maxnhar = b -> lay.maxnhar; r.maxnhar_e = b -> lay.maxnhar_e;
+  r.npsd = b -> lay.npsd; r.nchannel = b -> lay.nchannel; r.nspec = b -> l1_nspec;
+  r.f0 = (float*)b -> arr[LLSM_GPU_F0]; r.nhar = (int*)b -> arr[LLSM_GPU_NHAR];
+  r.ampl = (float*)b -> arr[LLSM_GPU_AMPL]; r.phse = (float*)b -> arr[LLSM_GPU_PHSE];
+  r.psd = (float*)b -> arr[LLSM_GPU_PSD]; r.psdres = (float*)b -> arr[LLSM_GPU_PSDRES];
+  r.has_psdres = (int*)b -> arr[LLSM_GPU_HAS_PSDRES]; r.edc = (float*)b -> arr[LLSM_GPU_EDC];
+  r.nhar_e = (int*)b -> arr[LLSM_GPU_NHAR_E];
+  r.eenv_ampl = (float*)b -> arr[LLSM_GPU_EENV_AMPL]; r.eenv_phse = (float*)b -> arr[LLSM_GPU_EENV_PHSE];
+  const bool l1 = b -> l1_nspec > 0;
+  r.rd = l1 ? (float*)b -> arr[LLSM_GPU_RD] : nullptr; r.vtmagn = l1 ? (float*)b -> arr[LLSM_GPU_VTMAGN] : nullptr;
+  r.vsphse = l1 ? (float*)b -> arr[LLSM_GPU_VSPHSE] : nullptr; r.nvsphse = l1 ? (int*)b -> arr[LLSM_GPU_NVSPHSE] : nullptr;
+  r.pbpsyn = l1 ? (int*)b -> arr[LLSM_GPU_PBPSYN] : nullptr; r.has_hm = l1 ? (int*)b -> arr[LLSM_GPU_HAS_HM] : nullptr;
+  return r;
+}
+
+int launch_failed(const char* what, int rc) {
+  llsm_set_error(std::string(what) + ": launch failed: " + hipGetErrorString((hipError_t)rc));
+  return -1;
+}
+
+int refuse(const std::string& why) { llsm_set_error("llsm_gpu_batch_retime: " + why); return -1; }
+}  // namespace
+
+extern "C" int llsm_gpu_batch_phasesync_rps(llsm_gpu_batch* b, int layer1_based) {
+  if(! b) { llsm_set_error("llsm_gpu_batch_phasesync_rps: NULL batch"); return -1; }
+  hipSetDevice(b -> ctx -> device);
+  const int rc = launch_phase_shift(& b -> ctx -> lc, mod_rows(b), nullptr, layer1_based);
+  return rc ? launch_failed("llsm_gpu_batch_phasesync_rps", rc) : 0;
+}
+
+extern "C" int llsm_gpu_batch_phasepropagate(llsm_gpu_batch* b, int sign) {
+  if(! b) { llsm_set_error("llsm_gpu_batch_phasepropagate: NULL batch"); return -1; }
+  const int F = b -> lay.total_frames;
+  if(F == 0) return 0;
+  hipSetDevice(b -> ctx -> device);
+  if(b -> mod_theta.alloc((size_t)F)) return -1;
+  // the factor of model.cpp's llsm_chunk_phasepropagate, formed the same way: (double)(float)(thop * sign) * 2 * pi
+  const double k2pi = (double)(float)(b -> opt.thop * (float)sign) * 2.0 * kPi;
+  LaunchCtx* P = & b -> ctx -> lc;
+  int rc = launch_phase_propagate_theta(P, b -> lay.n_utt, b -> d_frm_off.p, b -> d_nfrm.p, (const float*)b -> arr[LLSM_GPU_F0],
+    k2pi, b -> mod_theta.p);
+  if(! rc) rc = launch_phase_shift(P, mod_rows(b), b -> mod_theta.p, 0);
+  return rc ? launch_failed("llsm_gpu_batch_phasepropagate", rc) : 0;
+}
+
+extern "C" void llsm_gpu_retime_uniform_positions(int nfrm_src, int nfrm_dst, FP_TYPE* pos) {
+  if(! pos || nfrm_dst <= 0) return;
+  const float last = (float)(nfrm_src - 1);
+  for(int i = 0; i < nfrm_dst; i ++) {
+    const float t = (float)i * (float)nfrm_src / (float)nfrm_dst;
+    pos[i] = t < last ? t : last;
+  }
+}
+
+extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* src_c, const FP_TYPE* pos,
+  const int* psdres_src) {
+  llsm_gpu_batch* src = const_cast<llsm_gpu_batch*>(src_c);         // read only: the rows are not changed
+  if(! dst || ! src) return refuse("NULL batch");
+  if(src == dst) return refuse("src and dst are the same batch");
+  if(src -> ctx != dst -> ctx) return refuse("the two batches are on different contexts");
+  const llsm_aoptions& a = src -> opt; const llsm_aoptions& d = dst -> opt;
+  if(a.thop != d.thop || src -> fs != dst -> fs || a.nchannel != d.nchannel || a.npsd != d.npsd || a.maxnhar != d.maxnhar ||
+     a.maxnhar_e != d.maxnhar_e || src -> chanfreq != dst -> chanfreq)
+    return refuse("the batches were created with different options or sampling rates");
+  if(src -> lay.n_utt != dst -> lay.n_utt) return refuse("the batches hold different numbers of utterances");
+  if(src -> l1_nspec == 0) return refuse("src has no layer 1 (llsm_gpu_batch_tolayer1)");
+  if(dst -> l1_nspec != 0 && dst -> l1_nspec != src -> l1_nspec) return refuse("dst has layer 1 enabled with another size");
+  const int n_utt = dst -> lay.n_utt, Fd = dst -> lay.total_frames;
+  for(int u = 0; u < n_utt; u ++)
+    if((src -> nfrm[u] == 0) != (dst -> nfrm[u] == 0))
+      return refuse("utterance " + std::to_string(u) + " has frames on one side only");
+  // the map: positions checked (and formed, without one) on the host, then staged in page-locked memory
+  if(dst -> mod_ev) HIP_OK(hipEventSynchronize(dst -> mod_ev));    // the previous call's copy has left the stage
+  if(! dst -> mod_stage.resize(2 * (size_t)Fd + 1)) return -1;
+  float* hpos = (float*)dst -> mod_stage.data(); int* hres = dst -> mod_stage.data() + Fd;
+  for(int u = 0; u < n_utt; u ++) {
+    const int n = src -> nfrm[u], m = dst -> nfrm[u], o = dst -> frm_off[u];
+    if(pos) {
+      const float last = (float)(n - 1);
+      for(int i = 0; i < m; i ++) {
+        const float t = pos[o + i];
+        if(!(t >= 0.0f && t <= last))
+          return refuse("position " + std::to_string(o + i) + " (utterance " + std::to_string(u) + ") is NaN or outside [0, " +
+            std::to_string(n - 1) + "]");
+        hpos[o + i] = t;
+      }
+    } else llsm_gpu_retime_uniform_positions(n, m, hpos + o);
+    if(psdres_src)
+      for(int i = 0; i < m; i ++) {
+        const int k = psdres_src[o + i];
+        if(k < 0 || k >= n)
+          return refuse("psdres_src[" + std::to_string(o + i) + "] = " + std::to_string(k) + " is not a frame of utterance " +
+            std::to_string(u));
+        hres[o + i] = k;
+      }
+  }
+  // accepted: from here on dst changes
+  hipSetDevice(dst -> ctx -> device);
+  if(llsm_gpu_batch_enable_layer1(dst, (src -> l1_nspec - 1) * 2)) return -1;
+  dst -> fnyq = src -> fnyq;
+  dst -> maxnhar_conf = src -> maxnhar_conf;
+  dst -> min_f0 = 0; dst -> f0_unknown = true;           // the F0 row is written on the device
+  if(Fd == 0) return 0;
+  hipStream_t st = dst -> ctx -> stream;
+  if(dst -> mod_pos.alloc((size_t)Fd) || (psdres_src && dst -> mod_res.alloc((size_t)Fd))) return -1;
+  HIP_OK(hipMemcpyAsync(dst -> mod_pos.p, hpos, (size_t)Fd * sizeof(float), hipMemcpyHostToDevice, st));
+  if(psdres_src) HIP_OK(hipMemcpyAsync(dst -> mod_res.p, hres, (size_t)Fd * sizeof(int), hipMemcpyHostToDevice, st));
+  if(! dst -> mod_ev) HIP_OK(hipEventCreateWithFlags(& dst -> mod_ev, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(dst -> mod_ev, st));
+  RetimeMap m;
+  m.pos = dst -> mod_pos.p; m.res = psdres_src ? dst -> mod_res.p : nullptr; m.utt = dst -> d_frm_utt.p;
+  m.src_off = src -> d_frm_off.p; m.src_nfrm = src -> d_nfrm.p;
+  const int rc = launch_retime(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
+  return rc ? launch_failed("llsm_gpu_batch_retime", rc) : 0;
+}

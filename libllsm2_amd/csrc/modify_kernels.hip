@@ -1,0 +1,205 @@
+// modify_kernels.hip -- edits of a device-resident batch between analysis and synthesis (host side: modify.cpp).
+//
+//   k_phase_shift   llsm_frame_phaseshift on the rows of every frame (model.cpp), with the shift either given per frame
+//                   or formed from the frame's reference phase (llsm_frame_phasesync_rps); one wavefront per frame
+//   k_prop_theta    the per-frame shifts of llsm_chunk_phasepropagate: float32 running sum of an utterance's F0 row, in
+//                   frame order, staged through LDS; one workgroup per utterance
+//   k_retime        the frame-blending step of the reference's time-stretch recipe onto a new frame grid; one wavefront per
+//                   output frame, lanes across the rows
+//
+// No `#pragma clang fp contract(fast)` here: the phase kernels reproduce the host's float64 arithmetic bit for bit and the
+// blends are x_a + (x_b - x_a) r without contraction (the library is built with -ffp-contract=off).
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "launch.h"
+#include "plan.h"
+
+namespace lp = llsm_plan;
+
+#include "synth_frame.h"                                  // xcd_frame
+
+namespace {
+const int kPropChunk = 2048;                              // F0 values staged in LDS per pass of k_prop_theta
+
+DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// model.cpp wrap_phase: to (-pi, pi], float64, rounded to float
+DEV float md_wrap(double x) {
+  const double pi = 3.14159265358979323846;
+  double y = x - 2.0 * pi * floor((x + pi) / (2.0 * pi));
+  if(y <= -pi) y += 2.0 * pi;
+  return (float)y;
+}
+// llsm_hmframe_phaseshift on the first n entries of one row
+DEV void shift_row(float* p, int n, double th, int lane) {
+  for(int k = lane; k < n; k += 64) p[k] = md_wrap((double)p[k] + th * ((double)k + 1.0));
+}
+
+DEV float lin(float a, float b, float r) { return a + (b - a) * r; }
+DEV float circ(float pa, float pb, float r) {
+  return atan2f(lin(sinf(pa), sinf(pb), r), lin(cosf(pa), cosf(pb), r));
+}
+DEV void copy_row(float* __restrict__ d, const float* __restrict__ s, int n, int lane) {
+  for(int k = lane; k < n; k += 64) d[k] = s[k];
+}
+}  // namespace
+
+__global__ __launch_bounds__(64) void k_phase_shift(ModRows r, const float* __restrict__ theta, int layer1_based) {
+  const int g = xcd_frame(blockIdx.x, gridDim.x), lane = threadIdx.x;
+  const size_t G = (size_t)g;
+  const int me = r.maxnhar_e > 0 ? r.maxnhar_e : 1;
+  // counts as the rows define them: HM and noise envelopes only on voiced frames (llsm_flat_to_chunk), HM only where
+  // HAS_HM says it is valid, VSPHSE on frames with layer-1 members
+  const bool voiced = r.f0[g] != 0.0f;
+  const bool hm = voiced && (r.has_hm == nullptr || r.has_hm[g] != 0);
+  const int nh = hm ? clampi(r.nhar[g], 0, r.maxnhar) : 0;
+  const int ne = voiced ? clampi(r.nhar_e[g], 0, r.maxnhar_e) : 0;
+  const int nv = r.nvsphse ? clampi(r.nvsphse[g], 0, r.maxnhar) : 0;
+  float th;
+  if(theta) th = theta[g];
+  else {                                                  // llsm_frame_phasesync_rps
+    float ref = 0;
+    if(layer1_based && nv > 0) ref = r.vsphse[G * r.maxnhar];
+    else if(nh > 0) ref = r.phse[G * r.maxnhar];
+    th = -ref;
+  }
+  const double t = (double)th;
+  shift_row(r.phse + G * r.maxnhar, nh, t, lane);
+  for(int c = 0; c < r.nchannel; c ++) shift_row(r.eenv_phse + (G * r.nchannel + c) * me, ne, t, lane);
+  if(nv > 0) shift_row(r.vsphse + G * r.maxnhar, nv, t, lane);
+}
+
+__global__ __launch_bounds__(256) void k_prop_theta(const int* __restrict__ frm_off, const int* __restrict__ nfrm,
+  const float* __restrict__ f0, double k2pi, float* __restrict__ theta) {
+  __shared__ float buf[kPropChunk];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  const int off = frm_off[u], n = nfrm[u];
+  float acc = 0;                                          // (thread 0's is the running sum)
+  for(int c0 = 0; c0 < n; c0 += kPropChunk) {
+    const int m = min(kPropChunk, n - c0);
+    for(int i = tid; i < m; i += 256) buf[i] = f0[off + c0 + i];
+    __syncthreads();
+    if(tid == 0)
+      for(int i = 0; i < m; i ++) { acc += buf[i]; buf[i] = (float)((double)acc * k2pi); }
+    __syncthreads();
+    for(int i = tid; i < m; i += 256) theta[off + c0 + i] = buf[i];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(64) void k_retime(ModRows s, ModRows d, RetimeMap m) {
+  const int g = xcd_frame(blockIdx.x, gridDim.x), lane = threadIdx.x;
+  const int u = m.utt[g], n = m.src_nfrm[u];
+  const float t = m.pos[g];
+  const int fl = (int)floorf(t);
+  int a = 0; float r = 0;
+  if(n > 1) { a = min(fl, n - 2); r = t - (float)a; }
+  const int b = n > 1 ? a + 1 : a;
+  const size_t o = (size_t)m.src_off[u], G = (size_t)g;
+  const size_t ga = o + a, gb = o + b, gr = o + (m.res ? m.res[g] : min(fl, n - 1));
+  const int mh = s.maxnhar, np = s.npsd, nch = s.nchannel, ns = s.nspec;
+  const int me = s.maxnhar_e > 0 ? s.maxnhar_e : 1;
+
+  // PSDRES follows its own source frame in every case
+  copy_row(d.psdres + G * np, s.psdres + gr * np, np, lane);
+  if(lane == 0) d.has_psdres[G] = s.has_psdres[gr];
+
+  if(r == 0.0f || r == 1.0f) {                            // on a source frame: a bit-exact copy of it
+    const size_t gc = r == 0.0f ? ga : gb;
+    if(lane == 0) {
+      d.f0[G] = s.f0[gc]; d.nhar[G] = s.nhar[gc]; d.nhar_e[G] = s.nhar_e[gc]; d.rd[G] = s.rd[gc];
+      d.nvsphse[G] = s.nvsphse[gc]; d.pbpsyn[G] = s.pbpsyn[gc]; d.has_hm[G] = s.has_hm[gc];
+    }
+    copy_row(d.ampl + G * mh, s.ampl + gc * mh, mh, lane);
+    copy_row(d.phse + G * mh, s.phse + gc * mh, mh, lane);
+    copy_row(d.psd + G * np, s.psd + gc * np, np, lane);
+    copy_row(d.edc + G * nch, s.edc + gc * nch, nch, lane);
+    copy_row(d.eenv_ampl + G * nch * me, s.eenv_ampl + gc * nch * me, nch * me, lane);
+    copy_row(d.eenv_phse + G * nch * me, s.eenv_phse + gc * nch * me, nch * me, lane);
+    copy_row(d.vtmagn + G * ns, s.vtmagn + gc * ns, ns, lane);
+    copy_row(d.vsphse + G * mh, s.vsphse + gc * mh, mh, lane);
+    return;
+  }
+
+  // ---- source-filter part: F0, RD, VTMAGN, VSPHSE
+  const float fa = s.f0[ga], fb = s.f0[gb];
+  const bool va = fa > 0.0f, vb = fb > 0.0f;
+  const int nva = clampi(s.nvsphse[ga], 0, mh), nvb = clampi(s.nvsphse[gb], 0, mh);
+  float* vt = d.vtmagn + G * ns; float* vs = d.vsphse + G * mh;
+  const float* vta = s.vtmagn + ga * ns; const float* vtb = s.vtmagn + gb * ns;
+  const float* vsa = s.vsphse + ga * mh; const float* vsb = s.vsphse + gb * mh;
+  float f0, rd; int nv;
+  if(va && vb) {
+    f0 = lin(fa, fb, r); rd = lin(s.rd[ga], s.rd[gb], r); nv = max(nva, nvb);
+    for(int k = lane; k < ns; k += 64) vt[k] = fmaxf(lin(vta[k], vtb[k], r), -80.0f);
+    const int nmin = min(nva, nvb);
+    const float* lng = nva >= nvb ? vsa : vsb;
+    for(int k = lane; k < mh; k += 64) vs[k] = k < nmin ? circ(vsa[k], vsb[k], r) : lng[k];
+  } else if(va || vb) {                                   // voicing changes: the voiced side, faded in or out
+    const size_t gv = va ? ga : gb;
+    const float w = va ? 1.0f - r : r;
+    const float fade = 20.0f * log10f(fmaxf(1e-8f, w));
+    f0 = s.f0[gv]; rd = s.rd[gv]; nv = clampi(s.nvsphse[gv], 0, mh);
+    const float* vtv = s.vtmagn + gv * ns;
+    for(int k = lane; k < ns; k += 64) vt[k] = fmaxf(vtv[k] + fade, -80.0f);
+    copy_row(vs, s.vsphse + gv * mh, mh, lane);
+  } else {
+    f0 = 0.0f; rd = 1.0f; nv = nva;
+    for(int k = lane; k < ns; k += 64) vt[k] = fmaxf(vta[k], -80.0f);
+    copy_row(vs, vsa, mh, lane);
+  }
+  const bool voiced = va || vb;
+
+  // ---- noise part: PSD, EDC, envelopes
+  for(int k = lane; k < np; k += 64) d.psd[G * np + k] = lin(s.psd[ga * np + k], s.psd[gb * np + k], r);
+  for(int k = lane; k < nch; k += 64) d.edc[G * nch + k] = lin(s.edc[ga * nch + k], s.edc[gb * nch + k], r);
+  const int nea = clampi(s.nhar_e[ga], 0, s.maxnhar_e), neb = clampi(s.nhar_e[gb], 0, s.maxnhar_e);
+  const int nemin = min(nea, neb);
+  const size_t gle = nea >= neb ? ga : gb;
+  for(int k = lane; k < nch * me; k += 64) {
+    const int j = k % me;
+    const size_t ia = ga * nch * me + k, ib = gb * nch * me + k, il = gle * nch * me + k;
+    if(j < nemin) {
+      d.eenv_ampl[G * nch * me + k] = lin(s.eenv_ampl[ia], s.eenv_ampl[ib], r);
+      d.eenv_phse[G * nch * me + k] = circ(s.eenv_phse[ia], s.eenv_phse[ib], r);
+    } else {
+      d.eenv_ampl[G * nch * me + k] = s.eenv_ampl[il];
+      d.eenv_phse[G * nch * me + k] = s.eenv_phse[il];
+    }
+  }
+
+  // ---- harmonic model: rebuilt from layer 1 on voiced output frames (llsm_gpu_batch_tolayer0(dst, 1)), frame a's
+  // rows on unvoiced ones
+  if(voiced) {
+    for(int k = lane; k < mh; k += 64) { d.ampl[G * mh + k] = 0.0f; d.phse[G * mh + k] = 0.0f; }
+  } else {
+    copy_row(d.ampl + G * mh, s.ampl + ga * mh, mh, lane);
+    copy_row(d.phse + G * mh, s.phse + ga * mh, mh, lane);
+  }
+  if(lane == 0) {
+    d.f0[G] = f0; d.rd[G] = rd; d.nvsphse[G] = nv; d.nhar_e[G] = max(nea, neb);
+    d.pbpsyn[G] = s.pbpsyn[ga];
+    d.nhar[G] = voiced ? 0 : s.nhar[ga];
+    d.has_hm[G] = voiced ? 0 : s.has_hm[ga];
+  }
+}
+
+int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int layer1_based) {
+  if(r.nframes <= 0) return 0;
+  LAUNCH("k_phase_shift", k_phase_shift, dim3(r.nframes), dim3(64), 0, r, theta, layer1_based);
+  return 0;
+}
+
+int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, const int* nfrm, const float* f0,
+  double k2pi, float* theta) {
+  if(n_utt <= 0) return 0;
+  LAUNCH("k_prop_theta", k_prop_theta, dim3(n_utt), dim3(256), 0, frm_off, nfrm, f0, k2pi, theta);
+  return 0;
+}
+
+int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m) {
+  if(dst.nframes <= 0) return 0;
+  LAUNCH("k_retime", k_retime, dim3(dst.nframes), dim3(64), 0, src, dst, m);
+  return 0;
+}
