@@ -258,6 +258,34 @@ int  llsm_gpu_batch_phasepropagate(llsm_gpu_batch* b, int sign);
 int  llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* src, const FP_TYPE* pos, const int* psdres_src);
 void llsm_gpu_retime_uniform_positions(int nfrm_src, int nfrm_dst, FP_TYPE* pos);
 
+/* ---- pitch and formant edit of a device-resident layer-1 batch: the middle of the reference's pitch-shift recipe
+ * (analyse, tolayer1, phasepropagate(-1), F0 *= ratio and VTMAGN -= 20 log10(ratio) with HM dropped, tolayer0,
+ * phasepropagate(+1), synthesise), with an optional formant warp of VTMAGN and PSD.  Asynchronous; a refused call returns
+ * -1, sets llsm_gpu_last_error() and writes and launches nothing.
+ *
+ * f0_ratio, formant_ratio  host, total_frames floats each, in the batch's frame order; NULL: 1 on every frame.
+ * flags                    0 or LLSM_GPU_WARP_PSD (the PSD row is warped too).
+ * For frame g with rho = f0_ratio[g], alpha = formant_ratio[g]:
+ *   rho == 1 and alpha == 1  the frame is not touched (every row bit for bit, HM included).
+ *   unvoiced (F0 == 0)       F0 and the layer-1 rows are not touched; with LLSM_GPU_WARP_PSD and alpha != 1 the PSD row
+ *                            is warped by alpha.  Nothing else changes.
+ *   voiced, otherwise        F0' = F0 * rho in float32;
+ *                            W = VTMAGN warped by alpha (an exact copy when alpha == 1);
+ *                            VTMAGN'[k] = (float)((double)W[k] - 20 log10((double)rho)), the logarithm in float64, no floor;
+ *                            NHAR = 0 and HAS_HM = 0, so that llsm_gpu_batch_tolayer0(b, 1) rebuilds the harmonics (the
+ *                            AMPL and PHSE rows are not written); with LLSM_GPU_WARP_PSD and alpha != 1 the PSD row is
+ *                            warped by alpha.  RD, VSPHSE, NVSPHSE, PBPSYN, PSDRES, EDC and EENV are not touched.
+ *   Warp of a row x of n bins on linspace(0, fnyq, n) (VTMAGN: n = nspec, PSD: n = npsd), moving the envelope at f to
+ *   alpha f: for each bin k, p = (double)k / (double)alpha (correctly rounded), i = floor(p); i >= n - 1: out[k] = x[n - 1];
+ *   else out[k] = x[i] + (x[i + 1] - x[i]) r in float32 without contraction, r = (float)(p - i).
+ * Refused: a NULL batch, a batch without layer 1, an unknown flag bit, a ratio that is NaN, infinite or outside its range
+ * (rho in [1/16, 16], alpha in [1/4, 4]; the message names the frame), rows too long for the kernel's LDS
+ * (nspec + npsd > 10240).  The batch's lowest-F0 bound follows the edit.
+ * Known limit: tolayer0 caps the harmonics of a frame at NVSPHSE, as the reference does, so a downward shift by rho also
+ * narrows the harmonic band by rho; VSPHSE is not extended. */
+enum { LLSM_GPU_WARP_PSD = 1 };
+int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0_ratio, const FP_TYPE* formant_ratio, int flags);
+
 /* chunk <-> flat layer-1 rows (same row indexing as llsm_flat_params) */
 typedef struct {
   int nspec, maxnhar;

@@ -129,6 +129,7 @@ llsm_chunk_blob_size llsm_chunk_to_blob llsm_blob_view llsm_blob_to_chunk llsm_b
 llsm_create_rtsynth_group llsm_delete_rtsynth_group llsm_rtsynth_group_getlatency
 llsm_rtsynth_group_numoutput llsm_rtsynth_group_feed llsm_rtsynth_group_feed_many llsm_rtsynth_group_fetch llsm_rtsynth_group_fetch_all llsm_gpu_rt_graph llsm_gpu_rt_graph_hops llsm_gpu_rt_fused llsm_gpu_rt_direct llsm_gpu_rt_pipeline llsm_gpu_analysis_overlap llsm_slab_stats llsm_slab_trim llsm_delete_chunks llsm_gpu_release_cached_batches llsm_gpu_device_numa_node llsm_gpu_bind_thread_to_device llsm_gpu_batch_packed_words llsm_gpu_batch_download_packed llsm_gpu_batch_upload_packed llsm_gpu_batch_download_outputs llsm_gpu_batch_download_packed_block llsm_gpu_batch_upload_packed_block llsm_gpu_batch_transfer_many llsm_gpu_batch_params_layout llsm_gpu_batch_transfer_params llsm_gpu_shared_f0_tiles llsm_gpu_synth_tables llsm_gpu_pbp_real_ifft llsm_frame_compute_snr
 llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime llsm_gpu_retime_uniform_positions
+llsm_gpu_batch_pitch_formant
 """.split()
 
 _lib = None
@@ -189,6 +190,7 @@ def load():
     L.llsm_gpu_batch_retime.argtypes = [vp, vp, P_fp, P_int]
     L.llsm_gpu_retime_uniform_positions.argtypes = [C.c_int, C.c_int, P_fp]
     L.llsm_gpu_retime_uniform_positions.restype = None
+    L.llsm_gpu_batch_pitch_formant.argtypes = [vp, P_fp, P_fp, C.c_int]
     L.llsm_chunk_to_flat_l1.argtypes = [C.POINTER(Chunk), C.POINTER(FlatL1), C.c_int]
     L.llsm_flat_l1_to_chunk.argtypes = [C.POINTER(FlatL1), C.c_int, C.POINTER(Chunk)]
     L.llsm_chunk_tolayer1.argtypes = [C.POINTER(Chunk), C.c_int]
@@ -316,6 +318,28 @@ def retime_uniform_positions(nfrm_src, nfrm_dst):
     pos = np.zeros(max(int(nfrm_dst), 0), np.float32)
     load().llsm_gpu_retime_uniform_positions(int(nfrm_src), int(nfrm_dst), pos.ctypes.data_as(P_fp))
     return pos
+
+
+WARP_PSD = 1                                               # LLSM_GPU_WARP_PSD (llsm_gpu_batch_pitch_formant)
+
+
+def per_frame_ratio(value, nfrm):
+    """a pitch_formant ratio as total_frames float32 values: None stays None (1 everywhere), a scalar is every frame's,
+    n_utt values are one per utterance, total_frames values one per frame (the two agree when every utterance has one
+    frame)"""
+    if value is None:
+        return None
+    nfrm = np.asarray(nfrm, np.int64)
+    F = int(nfrm.sum())
+    v = np.asarray(value, np.float32)
+    if v.ndim == 0:
+        return np.full(F, v, np.float32)
+    if v.shape == (F,):
+        return np.ascontiguousarray(v)
+    if v.shape == (len(nfrm),):
+        return np.repeat(v, nfrm).astype(np.float32)
+    raise ValueError("ratio of shape %s: expected a scalar, %d utterance values or %d frame values"
+                     % (v.shape, len(nfrm), F))
 
 
 def make_soptions(fs, **kw):
@@ -478,6 +502,15 @@ class Batch:
         _check(self.L.llsm_gpu_batch_retime(self.h, src.h, None if p is None else p.ctypes.data_as(P_fp),
                                             None if r is None else r.ctypes.data_as(P_int)), "retime")
         self.nspec = src.nspec
+
+    def pitch_formant(self, f0_ratio=None, formant_ratio=None, warp_psd=False):
+        """F0 and formant ratios on a layer-1 batch (llsm_gpu_batch_pitch_formant); each ratio is None (1), a scalar,
+        n_utt values (one per utterance) or total_frames values; warp_psd: the formant warp moves the PSD row too"""
+        nfrm = np.diff(self.frm_off)
+        r, a = per_frame_ratio(f0_ratio, nfrm), per_frame_ratio(formant_ratio, nfrm)
+        _check(self.L.llsm_gpu_batch_pitch_formant(self.h, None if r is None else r.ctypes.data_as(P_fp),
+                                                   None if a is None else a.ctypes.data_as(P_fp),
+                                                   WARP_PSD if warp_psd else 0), "pitch_formant")
 
     def synthesize(self, sopt, seed=0, injected_white=False):
         _check(self.L.llsm_gpu_batch_synthesize(self.h, C.byref(sopt), seed, int(injected_white)), "synthesize")

@@ -266,5 +266,9 @@ int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int l
 int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, const int* nfrm, const float* f0,
   double k2pi, float* theta);
 int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m);
+// llsm_gpu_batch_pitch_formant over frames [g_lo, g_hi) (every edited frame): rho / alpha are per-frame F0 and formant
+// ratios (NULL: 1), warp_psd the PSD warp; LDS: 16 (nspec + npsd) bytes per workgroup
+int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, const float* rho, const float* alpha,
+  int warp_psd);
 
 #endif

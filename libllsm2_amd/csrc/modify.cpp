@@ -5,6 +5,8 @@
 //   llsm_gpu_batch_retime            the frame-blending step of the reference's time-stretch recipe, onto the frame grid
 //                                    of another batch (rules: llsm_gpu.h)
 //   llsm_gpu_retime_uniform_positions  the map retime uses when it is given none
+//   llsm_gpu_batch_pitch_formant     F0 and formant ratios per frame on a layer-1 batch, the edit of the reference's
+//                                    pitch-shift recipe (rules: llsm_gpu.h)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -132,4 +134,60 @@ extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* 
   m.src_off = src -> d_frm_off.p; m.src_nfrm = src -> d_nfrm.p;
   const int rc = launch_retime(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
   return rc ? launch_failed("llsm_gpu_batch_retime", rc) : 0;
+}
+
+namespace {
+int refuse_pf(const std::string& why) { llsm_set_error("llsm_gpu_batch_pitch_formant: " + why); return -1; }
+
+// ratios of frames [0, F) into `out` (NULL: all 1), each within [lo, hi]; first / last frame with a ratio != 1 widen
+// [*g_lo, *g_hi), *mn takes the smallest.  Returns false (error set) on the first bad value.
+bool stage_ratios(const float* v, int F, float lo, float hi, const char* name, const char* range, float* out, int* g_lo,
+  int* g_hi, float* mn) {
+  if(! v) return true;
+  for(int g = 0; g < F; g ++) {
+    const float x = v[g];
+    if(!(x >= lo && x <= hi)) {
+      refuse_pf(std::string(name) + " of frame " + std::to_string(g) + " (" + std::to_string(x) +
+        ") is NaN, infinite or outside " + range);
+      return false;
+    }
+    out[g] = x;
+    if(x != 1.0f) { if(g < *g_lo) *g_lo = g; if(g + 1 > *g_hi) *g_hi = g + 1; }
+    if(x < *mn) *mn = x;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0_ratio, const FP_TYPE* formant_ratio,
+  int flags) {
+  if(! b) return refuse_pf("NULL batch");
+  if(b -> l1_nspec == 0) return refuse_pf("the batch has no layer 1 (llsm_gpu_batch_tolayer1)");
+  if(flags & ~LLSM_GPU_WARP_PSD) return refuse_pf("unknown flag bits " + std::to_string(flags & ~LLSM_GPU_WARP_PSD));
+  const size_t lds = (size_t)4 * (b -> l1_nspec + b -> lay.npsd) * sizeof(float);
+  if(lds > 160 * 1024) return refuse_pf("nspec + npsd = " + std::to_string(b -> l1_nspec + b -> lay.npsd) +
+    " floats per frame do not fit the kernel's LDS (at most 10240)");
+  const int F = b -> lay.total_frames;
+  // the ratios: checked on the host, then staged in page-locked memory ([2][F]: F0, formant)
+  if(b -> mod_ev) HIP_OK(hipEventSynchronize(b -> mod_ev));       // the previous call's copy has left the stage
+  if(! b -> mod_stage.resize(2 * (size_t)F + 1)) return -1;
+  float* hr = (float*)b -> mod_stage.data(); float* ha = hr + F;
+  int g_lo = F, g_hi = 0; float rho_min = 1.0f, alpha_min = 1.0f;
+  if(! stage_ratios(f0_ratio, F, 1.0f / 16.0f, 16.0f, "f0_ratio", "[1/16, 16]", hr, & g_lo, & g_hi, & rho_min)) return -1;
+  if(! stage_ratios(formant_ratio, F, 0.25f, 4.0f, "formant_ratio", "[1/4, 4]", ha, & g_lo, & g_hi, & alpha_min)) return -1;
+  if(g_hi <= g_lo) return 0;                                       // every ratio is 1: nothing changes
+  // accepted: from here on the batch changes.  Lowest voiced F0: every voiced F0' = fl(F0 rho) >= fl(min_f0 rho_min)
+  // (rounding is monotonic), so the product stays a lower bound of the new rows; unknown stays unknown.
+  if(b -> min_f0 > 0 && ! b -> f0_unknown) b -> min_f0 = b -> min_f0 * rho_min;
+  hipSetDevice(b -> ctx -> device);
+  hipStream_t st = b -> ctx -> stream;
+  if(b -> mod_ratio.alloc(2 * (size_t)F)) return -1;
+  float* dr = f0_ratio ? b -> mod_ratio.p : nullptr;
+  float* da = formant_ratio ? b -> mod_ratio.p + F : nullptr;
+  if(dr) HIP_OK(hipMemcpyAsync(dr, hr, (size_t)F * sizeof(float), hipMemcpyHostToDevice, st));
+  if(da) HIP_OK(hipMemcpyAsync(da, ha, (size_t)F * sizeof(float), hipMemcpyHostToDevice, st));
+  if(! b -> mod_ev) HIP_OK(hipEventCreateWithFlags(& b -> mod_ev, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(b -> mod_ev, st));
+  const int rc = launch_pitch_formant(& b -> ctx -> lc, mod_rows(b), g_lo, g_hi, dr, da, flags & LLSM_GPU_WARP_PSD);
+  return rc ? launch_failed("llsm_gpu_batch_pitch_formant", rc) : 0;
 }

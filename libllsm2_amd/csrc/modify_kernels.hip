@@ -6,6 +6,9 @@
 //                   frame order, staged through LDS; one workgroup per utterance
 //   k_retime        the frame-blending step of the reference's time-stretch recipe onto a new frame grid; one wavefront per
 //                   output frame, lanes across the rows
+//   k_pitch_formant F0 scaling, VTMAGN amplitude compensation and formant warp (VTMAGN, optionally PSD) of
+//                   llsm_gpu_batch_pitch_formant; four consecutive frames per 256-thread workgroup, rows staged in LDS with
+//                   16-byte accesses, the warp a gather from LDS
 //
 // No `#pragma clang fp contract(fast)` here: the phase kernels reproduce the host's float64 arithmetic bit for bit and the
 // blends are x_a + (x_b - x_a) r without contraction (the library is built with -ffp-contract=off).
@@ -42,6 +45,25 @@ DEV float circ(float pa, float pb, float r) {
 }
 DEV void copy_row(float* __restrict__ d, const float* __restrict__ s, int n, int lane) {
   for(int k = lane; k < n; k += 64) d[k] = s[k];
+}
+
+// k_pitch_formant: a workgroup takes frames g0 .. g0 + 3 with g0 a multiple of 4, so its spans of VTMAGN (4 nspec floats)
+// and PSD (4 npsd floats) start on a 16-byte boundary of the (256-byte aligned) rows and move as float4; only the batch's
+// last group can end off a float4 and finish with single floats.
+const int kPfFrames = 4, kPfThreads = 256;
+
+// bin k of row x (n bins) warped by alpha: the envelope at f moves to alpha f (llsm_gpu.h)
+DEV float warp_at(const float* x, int n, double alpha, int k) {
+  const double p = (double)k / alpha;
+  if(p >= (double)(n - 1)) return x[n - 1];              // floor(p) >= n - 1: the top bin is held
+  const int i = (int)p;                                   // (p >= 0: truncation is floor)
+  return lin(x[i], x[i + 1], (float)(p - (double)i));
+}
+// span [0, n) of global row memory <-> LDS, float4 where it can
+DEV void pf_stage(float* __restrict__ d, const float* __restrict__ s, int n, int tid) {
+  const int n4 = n >> 2;
+  for(int q = tid; q < n4; q += kPfThreads) ((float4*)d)[q] = ((const float4*)s)[q];
+  for(int e = (n4 << 2) + tid; e < n; e += kPfThreads) d[e] = s[e];
 }
 }  // namespace
 
@@ -185,6 +207,72 @@ __global__ __launch_bounds__(64) void k_retime(ModRows s, ModRows d, RetimeMap m
   }
 }
 
+// The span of VTMAGN (ns bins per frame) or PSD of one workgroup's frames, rewritten from its LDS image `x`: bin k of local
+// frame f is warped by alpha[f] where warp[f], minus comp[f] where sub[f] (sub NULL: nowhere), and copied otherwise.
+DEV void pf_write(float* __restrict__ d, const float* __restrict__ x, int ns, int nf, const int* warp, const int* sub,
+  const float* alpha, const double* comp, int tid) {
+  auto val = [&](int f, int k) {
+    const float* xf = x + f * ns;
+    const bool s = sub && sub[f];
+    if(! warp[f] && ! s) return xf[k];
+    const float w = warp[f] ? warp_at(xf, ns, (double)alpha[f], k) : xf[k];
+    return s ? (float)((double)w - comp[f]) : w;
+  };
+  const int n = nf * ns, n4 = n >> 2;
+  for(int q = tid; q < n4; q += kPfThreads) {
+    int f = (4 * q) / ns, k = 4 * q - f * ns;
+    float o[4];
+    for(int j = 0; j < 4; j ++) { o[j] = val(f, k); if(++ k == ns) { k = 0; f ++; } }
+    ((float4*)d)[q] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+  for(int e = (n4 << 2) + tid; e < n; e += kPfThreads) d[e] = val(e / ns, e % ns);
+}
+
+// g_lo: first frame of the launch (a multiple of kPfFrames); frames whose two ratios are both 1 are left alone
+__global__ __launch_bounds__(kPfThreads) void k_pitch_formant(ModRows r, int g_lo, const float* __restrict__ rho,
+  const float* __restrict__ alpha, int warp_psd) {
+  extern __shared__ float4 pf_lds[];
+  __shared__ int s_vt[kPfFrames], s_psd[kPfFrames], s_warpvt[kPfFrames];
+  __shared__ float s_alpha[kPfFrames];
+  __shared__ double s_comp[kPfFrames];
+  const int g0 = g_lo + (int)blockIdx.x * kPfFrames, tid = threadIdx.x;
+  const int nf = min(kPfFrames, r.nframes - g0);
+  // the ratios first: a group with nothing to do ends here, before it reads a row
+  bool any = false;
+  for(int f = 0; f < nf; f ++) any = any || (rho ? rho[g0 + f] : 1.0f) != 1.0f || (alpha ? alpha[g0 + f] : 1.0f) != 1.0f;
+  if(! any) return;
+  if(tid < kPfFrames) {
+    int vt = 0, ps = 0; float al = 1.0f; double comp = 0.0;
+    if(tid < nf) {
+      const int g = g0 + tid;
+      const float rh = rho ? rho[g] : 1.0f;
+      al = alpha ? alpha[g] : 1.0f;
+      const bool touched = rh != 1.0f || al != 1.0f;
+      const float f0 = r.f0[g];
+      vt = touched && f0 != 0.0f;
+      ps = warp_psd && al != 1.0f;
+      if(vt) {
+        comp = 20.0 * log10((double)rh);
+        r.f0[g] = f0 * rh; r.nhar[g] = 0; r.has_hm[g] = 0;
+      }
+    }
+    s_vt[tid] = vt; s_warpvt[tid] = vt && al != 1.0f; s_psd[tid] = ps; s_alpha[tid] = al; s_comp[tid] = comp;
+  }
+  __syncthreads();
+  bool do_vt = false, do_psd = false;
+  for(int f = 0; f < nf; f ++) { do_vt = do_vt || s_vt[f]; do_psd = do_psd || s_psd[f]; }
+  const int ns = r.nspec, np = r.npsd;
+  float* lv = (float*)pf_lds;                             // [kPfFrames][ns] VTMAGN, then [kPfFrames][np] PSD
+  float* lp_ = lv + kPfFrames * ns;
+  float* gv = r.vtmagn + (size_t)g0 * ns;
+  float* gp = r.psd + (size_t)g0 * np;
+  if(do_vt) pf_stage(lv, gv, nf * ns, tid);
+  if(do_psd) pf_stage(lp_, gp, nf * np, tid);
+  __syncthreads();
+  if(do_vt) pf_write(gv, lv, ns, nf, s_warpvt, s_vt, s_alpha, s_comp, tid);
+  if(do_psd) pf_write(gp, lp_, np, nf, s_psd, nullptr, s_alpha, s_comp, tid);
+}
+
 int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int layer1_based) {
   if(r.nframes <= 0) return 0;
   LAUNCH("k_phase_shift", k_phase_shift, dim3(r.nframes), dim3(64), 0, r, theta, layer1_based);
@@ -201,5 +289,19 @@ int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, co
 int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m) {
   if(dst.nframes <= 0) return 0;
   LAUNCH("k_retime", k_retime, dim3(dst.nframes), dim3(64), 0, src, dst, m);
+  return 0;
+}
+
+int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, const float* rho, const float* alpha,
+  int warp_psd) {
+  if(g_hi <= g_lo) return 0;
+  g_lo -= g_lo % kPfFrames;
+  const size_t lds = (size_t)kPfFrames * (r.nspec + r.npsd) * sizeof(float);
+  if(lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)k_pitch_formant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if(e != hipSuccess) return (int)e;
+  }
+  const int groups = (g_hi - g_lo + kPfFrames - 1) / kPfFrames;
+  LAUNCH("k_pitch_formant", k_pitch_formant, dim3(groups), dim3(kPfThreads), lds, r, g_lo, rho, alpha, warp_psd);
   return 0;
 }

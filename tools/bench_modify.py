@@ -1,13 +1,17 @@
-"""Times the device-side time-stretch chain at the bench shape (1 024 utterances x 200 frames, F0 = 120 Hz, thop = 5 ms,
-layer 1 at nfft = 2048), stretched 2x:
+"""Times a device-side edit chain at the bench shape (1 024 utterances x 200 frames, F0 = 120 Hz, thop = 5 ms, layer 1 at
+nfft = 2048).  --edit stretch (the default) stretches 2x:
 
     phasepropagate(-1) -> retime -> tolayer0(1) -> phasepropagate(+1) -> synthesize
 
-and prints one JSON object: ms per call of each kernel of the chain (the context's per-launch HIP events), GB/s of the
-edit kernels on unique bytes, the wall time of the chain, and the host round trip the device retime replaces (the rows
-downloaded, blended in numpy by the same rules, uploaded again) on the same box.
+--edit pitch shifts F0 by 1.5 and the formants by 1.2, PSD warped too:
 
-    python tools/bench_modify.py [--utts 1024] [--steps 5] [--warmup 2] [--nfft 2048] [--out FILE]
+    phasepropagate(-1) -> pitch_formant(1.5, 1.2, warp_psd) -> tolayer0(1) -> phasepropagate(+1) -> synthesize
+
+and prints one JSON object: ms per call of each kernel of the chain (the context's per-launch HIP events), GB/s of the
+edit kernels on unique bytes, the wall time of the chain, and the host round trip the device edit replaces (the rows
+downloaded, edited in numpy by the same rules, uploaded again) on the same box.
+
+    python tools/bench_modify.py [--edit stretch|pitch] [--utts 1024] [--steps 5] [--warmup 2] [--nfft 2048] [--out FILE]
 """
 import argparse
 import json
@@ -94,8 +98,115 @@ def numpy_retime(s, n_src, n_dst, n_utt, pos):
     return out
 
 
+def numpy_pitch(s, rho, alpha):
+    """the pitch_formant rules for one F0 and one formant ratio over every frame, PSD warped (rows edited in place)"""
+    rho, alpha = np.float32(rho), np.float32(alpha)         # the ratios as the C API takes them
+
+    def warp(x):
+        n = x.shape[1]
+        p = np.arange(n, dtype=np.float64) / np.float64(alpha)
+        i = np.floor(p).astype(np.int64)
+        top = i >= n - 1
+        ic = np.minimum(i, n - 2)
+        r = (p - i).astype(np.float32)
+        out = x[:, ic] + (x[:, ic + 1] - x[:, ic]) * r[None, :]
+        out[:, top] = x[:, n - 1:n]
+        return out
+    v = s[llsm.A_F0] != 0
+    s[llsm.A_PSD] = warp(s[llsm.A_PSD])
+    vt = warp(s[llsm.A_VTMAGN][v]) if alpha != 1 else s[llsm.A_VTMAGN][v]
+    s[llsm.A_VTMAGN][v] = (vt.astype(np.float64) - 20 * np.log10(np.float64(rho))).astype(np.float32)
+    s[llsm.A_F0][v] *= np.float32(rho)
+    s[llsm.A_NHAR][v] = 0; s[llsm.A_HAS_HM][v] = 0
+    return s
+
+
+PITCH_ROWS = (llsm.A_F0, llsm.A_NHAR, llsm.A_HAS_HM, llsm.A_VTMAGN, llsm.A_PSD)   # what pitch_formant reads and writes
+
+
+def pitch_leg(a):
+    n_utt, rho, alpha = a.utts, 1.5, 1.2
+    x = make_batch_inputs(list(range(n_utt)), lambda u: 120.0, "cuda:0")
+    ctx = llsm.Context(0)
+    ao = llsm.make_aoptions(f0_refine=0)
+    so = llsm.make_soptions(FS)
+    b = llsm.Batch(ctx, ao, FS, [NX] * n_utt, [NFRM] * n_utt)
+    b.upload(llsm.A_X, x.ravel()); b.upload(llsm.A_F0, np.full(n_utt * NFRM, 120.0, np.float32))
+    b.analyze(); b.tolayer1(a.nfft)
+    ctx.sync()
+    # the rows the edit changes, kept in page-locked memory and put back between steps (outside the timed chains)
+    keep = {aid: b.pinned_array(aid) for aid in PITCH_ROWS}
+    for aid, arr in keep.items():
+        b.download(aid, out=arr)
+
+    def restore():
+        for aid, arr in keep.items():
+            b.upload(aid, arr)
+        ctx.sync()
+
+    def chain():
+        b.phasepropagate(-1); b.pitch_formant(rho, alpha, warp_psd=True); b.tolayer0(True); b.phasepropagate(+1)
+        b.synthesize(so, seed=1)
+
+    for _ in range(a.warmup):
+        restore(); chain()
+    ctx.sync()
+    walls = []
+    for _ in range(a.steps):
+        restore()
+        t0 = time.perf_counter(); chain(); ctx.sync(); walls.append((time.perf_counter() - t0) * 1e3)
+    ctx.set_profiling(True); ctx.reset_profile()
+    for _ in range(a.steps):
+        ctx.set_profiling(False); restore(); ctx.set_profiling(True)
+        chain()
+    ctx.sync()
+    prof = ctx.profile()
+    ctx.set_profiling(False)
+    kern = {k: dict(ms_per_call=v[0] / v[1], calls_per_step=v[1] / a.steps) for k, v in prof.items() if v[1] > 0}
+    F = n_utt * NFRM
+    nspec, npsd = a.nfft // 2 + 1, b.layout.npsd
+    nv = int((keep[llsm.A_F0] != 0).sum())
+    # unique bytes of one call: both ratio rows and every F0 read; VTMAGN read + written, F0 written, NHAR and HAS_HM
+    # written on voiced frames; PSD read + written on every frame
+    uniq = F * (4 + 4 + 4) + nv * (2 * 4 * nspec + 4 + 4 + 4) + F * 2 * 4 * npsd
+    out = dict(edit="pitch", rho=rho, alpha=alpha, warp_psd=True,
+               shape=dict(utterances=n_utt, frames=F, voiced=nv, nfft=a.nfft, nspec=nspec, npsd=npsd),
+               chain_wall_ms=dict(min=min(walls), median=float(np.median(walls)), max=max(walls)), kernels=kern)
+    if "k_pitch_formant" in kern:
+        t = kern["k_pitch_formant"]["ms_per_call"]
+        out["pitch_formant"] = dict(ms=t, unique_gb=uniq / 1e9, gbs=uniq / t / 1e6)
+    if a.host_reps > 0:
+        # the host round trip the device edit replaces: the five rows down, numpy edit, rows up
+        restore(); b.phasepropagate(-1); ctx.sync()
+        hosts = []
+        for _ in range(a.host_reps):
+            t0 = time.perf_counter()
+            s = {aid: b.download(aid) for aid in PITCH_ROWS}
+            t1 = time.perf_counter()
+            nbytes = sum(v.nbytes for v in s.values())
+            s = numpy_pitch(s, rho, alpha)
+            t2 = time.perf_counter()
+            for aid in PITCH_ROWS:
+                b.upload(aid, s[aid])
+            ctx.sync()
+            t3 = time.perf_counter()
+            hosts.append(dict(download_ms=(t1 - t0) * 1e3, edit_ms=(t2 - t1) * 1e3, upload_ms=(t3 - t2) * 1e3,
+                              total_ms=(t3 - t0) * 1e3, bytes=int(2 * nbytes)))
+            restore(); b.phasepropagate(-1); ctx.sync()
+        out["host_round_trip"] = min(hosts, key=lambda h: h["total_ms"])
+        # the numpy rows agree with the device's
+        b.pitch_formant(rho, alpha, warp_psd=True); ctx.sync()
+        dev = {aid: b.download(aid) for aid in PITCH_ROWS}
+        out["host_vs_device_max_abs"] = {str(k): float(np.abs(dev[k].astype(np.float64) - s[k]).max()) for k in dev}
+    for arr in keep.values():
+        b.free_pinned(arr)
+    b.close(); ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--edit", choices=("stretch", "pitch"), default="stretch")
     ap.add_argument("--utts", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -103,6 +214,13 @@ def main():
     ap.add_argument("--host-reps", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.edit == "pitch":
+        line = json.dumps(pitch_leg(a))
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     n_utt, n2 = a.utts, 2 * NFRM
     x = make_batch_inputs(list(range(n_utt)), lambda u: 120.0, "cuda:0")
     ctx = llsm.Context(0)
