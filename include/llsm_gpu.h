@@ -35,7 +35,8 @@ void*             llsm_gpu_context_stream(llsm_gpu_context* ctx);
 int               llsm_gpu_synchronize(llsm_gpu_context* ctx);
 
 /* Conventions of the un-vendored ciglet primitives that the reference's own code cannot confirm (DESIGN.md
- * section 6).  Process-wide; read when contexts, batches and llsmrt buffers are created.
+ * section 6).  Process-wide; read by contexts and batches at each call (below), by llsmrt buffers
+ * when they are created.
  *   "hann_periodic"       0 (default): overlap-add Hann windows use the symmetric definition (n - 1); 1: periodic (n)
  *   "moving_avg_half"     3 (default): moving_avg(x, n, 3) averages 7 taps; 1: 3 taps
  *   "filtfilt_pad"        15 (default, 3 x the 5 coefficients): samples of odd extension at both ends (1 .. 15)
@@ -46,7 +47,10 @@ int               llsm_gpu_synchronize(llsm_gpu_context* ctx);
  *                         spectrum sit on it) in units of 1e-6; 133979 (default) = the calibrated 0.13397922601295542
  *   "lf_rd_clamp"         lfmodel_from_rd: 0 (default) Fant's Rd regression with the usual extension formulas outside
  *                         0.21 <= Rd <= 2.7; 1: Rd limited to the range the regression was fitted on (0.3 .. 2.7) first
- * The CPU oracle has the same switches (oracle.h o_set_convention); set returns 0 or -1, get the value or -1. */
+ * The CPU oracle has the same switches (oracle.h o_set_convention); set returns 0 or -1, get the value or -1.
+ * A batch follows the conventions in force at each call: a batch created (or last used) under other values rebuilds
+ * the tables it bakes them into -- windows, filter padding -- on its next llsm_gpu_batch_analyze / _synthesize, and
+ * gives what a batch created under the new values gives, bit for bit. */
 int llsm_gpu_set_convention(const char* name, int value);
 int llsm_gpu_get_convention(const char* name);
 
@@ -477,7 +481,10 @@ void llsm_gpu_set_default_seed(unsigned long long seed);
 /* Index plan exported for tests: same float32
  * evaluation the kernels use. which: 0 center(i) 1 nwin_sin 2 nwin_env
  * 3 nwin_filt 4 nwin_psd 5 ny(i=nfrm) 6 hwin(f0) 7 nhar(f0,i=maxnhar)
- * 8 env_ola(i,j) 9 dcwin(f0) 10 spgmwin(f0,i=nwin_psd) */
+ * 8 env_ola(i,j) 9 dcwin(f0) 10 spgmwin(f0,i=nwin_psd) 13 time segments
+ * the zero-phase band filter cuts a signal of i samples into when its slowest
+ * pole reaches j samples (1: whole).  A function of the signal alone, so an
+ * utterance gets the same bits in every batch. */
 int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE thop,
   FP_TYPE fs, FP_TYPE rel_winsize);
 

@@ -143,6 +143,8 @@ struct llsm_gpu_batch {
   DevBuf<int> nfft_u;
   // synthesis plan cache
   float syn_fs = 0; int nwin_env = 0, nwin_filt = 0, nfft_filt = 0; float inv_wsqr = 0;
+  int wsym_filt = 0;                                 // symmetry denominator of win_filt, fixed when the table is built
+  unsigned long conv_epoch = 0;                      // llsm_engine_config_epoch() the convention-dependent tables were built in
   // layer 1 / pulse-by-pulse synthesis (l1.cpp)
   struct Effect { llsm_fgfm modifier = nullptr; void* info = nullptr; llsm_container* frame = nullptr; };
   int l1_nspec = 0;                       // 0: layer-1 arrays not allocated

@@ -26,7 +26,8 @@
 namespace lp = llsm_plan;
 
 // ------------------------------------------------------------- conventions
-// Process-wide; read when a context / batch / llsmrt buffer is created.
+// Process-wide; device switches are read at every launch, batch tables follow at each call (follow_conventions),
+// llsmrt buffers read them when they are created.
 namespace {
 struct HostConventions { int hann_periodic = 0, mavg_half = 3, filtfilt_pad = 15, interp1u_excl = 0, kalman_init = 0, lobe_1e6 = 133979, lf_rd_clamp = 0; } g_hconv;
 }
@@ -82,7 +83,8 @@ static void prof_drain(llsm_gpu_context* c) {
 }
 
 // Counts the changes of process-wide settings that a batch bakes into its tables when it is created (window conventions,
-// filter padding, unit plans): batches kept between calls (capi.cpp worker_batch) are reused only within one epoch.
+// filter padding, unit plans): batches kept between calls (capi.cpp worker_batch) are reused only within one epoch, and a
+// batch held by the caller rebuilds those tables on its next call once the epoch has moved (follow_conventions).
 static std::atomic<unsigned long> g_config_epoch{1};
 unsigned long llsm_engine_config_epoch(void) { return g_config_epoch.load(); }
 
@@ -532,6 +534,7 @@ extern "C" llsm_gpu_batch* llsm_gpu_create_batch(llsm_gpu_context* ctx,
     if(! blocks.empty()) bad |= upload_vec(b -> d_hblocks, blocks);
   }
   // batch-constant windows and normalisers (rounded from float64)
+  b -> conv_epoch = llsm_engine_config_epoch();
   bad |= upload_vec(b -> win_sin, make_hann(b -> nwin_sin));
   std::vector<float> wb = make_blackman(b -> nwin_psd);
   double wp = 0; for(float v : wb) wp += (double)v * v;
@@ -889,6 +892,16 @@ static int decay_length(const double* a, double tol) {
   return last + 1;
 }
 
+// Time segments of a zero-phase filtering job over a signal of n samples (its interior [lo, hi) of w = hi - lo samples)
+// whose slowest pole reaches H samples: signals shorter than kFiltCutLen stay whole -- among them every synthesis template
+// (at most 20 000 + 128 samples) and the bench's 1 s at 44.1 kHz --, longer ones get segments of at least max(2048, 6 H)
+// samples, at most 64.  Nothing about the batch enters (llsm_gpu_plan_index case 13 exports it).
+static const int kFiltCutLen = 65536;
+static int filt_segments(int n, int w, int H) {
+  if(n < kFiltCutLen || H <= 0) return 1;
+  return std::max(1, std::min(w / std::max(2048, 6 * H), 64));
+}
+
 static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
   const float* white) {
   const int U = b -> lay.n_utt, nch = b -> lay.nchannel;
@@ -899,17 +912,18 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
   // [w0, w1) from a stretch that reaches H samples further on both sides, H = the reach of the slowest pole to 1e-9 + 64
   // -- the rule the two end jobs of a fused band-pass already live by (identical to 1e-13 beyond that reach against
   // scipy); the stretch's own padding and initial state are a transient that has died before w0 / after w1.  Fused
-  // band-pass jobs and single-section jobs only (neither uses `mid`); batches with >= 1 024 signals are left alone.
+  // band-pass jobs and single-section jobs only (neither uses `mid`).  Whether and how a job is cut is a function of its
+  // signal alone (filt_segments): the transients differ from the uncut result in the last float32 places, so a rule that
+  // looked at the batch (it used to leave batches of >= 1 024 signals whole) gave an utterance other bits in other batches.
   std::vector<size_t> seg_tmp_off;                       // tmp offsets of the segment jobs inside iir_seg[which], by job index
   std::vector<int> seg_job;                              // ... and which entries of `jobs` they are
   size_t seg_need = 0;
   static const bool seg_ok = [] { const char* e = std::getenv("LLSM_GPU_FILT_SEGMENTS"); return !(e && e[0] == '0'); }();
   static const int seg_force = [] { const char* e = std::getenv("LLSM_GPU_FILT_SEGMENTS"); const int v = e ? std::atoi(e) : 0; return v > 1 ? v : 0; }();   // experiment: this many segments for every job
-  auto push_job = [&](const FiltJob& j, int H, int nsignals) {
+  auto push_job = [&](const FiltJob& j, int H) {
     const int lo = j.whi > j.wlo ? j.wlo : 0, hi = j.whi > j.wlo ? j.whi : j.n;
     int S = 1;
-    if(seg_ok && nsignals < 1024 && H > 0 && !(j.sec1 >= 0 && ! j.fused))
-      S = std::min((hi - lo) / std::max(2048, 6 * H), 64);   // (a function of the signal alone: the same cut in every small batch)
+    if(seg_ok && !(j.sec1 >= 0 && ! j.fused)) S = filt_segments(j.n, hi - lo, H);
     if(seg_force && H > 0 && !(j.sec1 >= 0 && ! j.fused) && (hi - lo) / std::max(2048, 6 * H) >= seg_force) S = seg_force;
     if(S <= 1) { jobs.push_back(j); return; }
     for(int sg = 0; sg < S; sg ++) {
@@ -987,7 +1001,7 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
           edge_jobs.push_back(e);
         }
       }
-      push_job(j, reach > 0 ? ((reach + 31) & ~31) + 64 : 0, U * (which == 0 ? nch : nact));
+      push_job(j, reach > 0 ? ((reach + 31) & ~31) + 64 : 0);
     }
   }
   if(tmp_off > b -> iir_tmp.n || edge_off > edge_buf.n) { llsm_set_error("internal: IIR scratch too small"); return -1; }
@@ -1000,6 +1014,21 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
   if(which == 0) { b -> njobs_ana = (int)jobs.size(); return upload_vec(b -> jobs_ana, jobs); }
   b -> njobs_syn = (int)jobs.size(); b -> nch_active = nact;
   return upload_vec(b -> jobs_syn, jobs);
+}
+
+// A batch follows the conventions in force at each call (llsm_gpu.h llsm_gpu_set_convention).  The device-side switches
+// are read live; what the batch bakes into tables -- the Hann window of the harmonic overlap-add (built at creation), the
+// filter jobs' padding, the synthesis windows and the symmetry denominator of win_filt -- is rebuilt here once the epoch
+// has moved since it was built.
+static int follow_conventions(llsm_gpu_batch* b) {
+  const unsigned long e = llsm_engine_config_epoch();
+  if(b -> conv_epoch == e) return 0;
+  HIP_OK(hipStreamSynchronize(b -> ctx -> stream));    // earlier launches may still read the old tables
+  if(b -> ctx -> aux) HIP_OK(hipStreamSynchronize(b -> ctx -> aux));
+  if(upload_vec(b -> win_sin, make_hann(b -> nwin_sin))) return -1;
+  b -> njobs_ana = 0; b -> njobs_syn = 0; b -> syn_fs = 0;
+  b -> conv_epoch = e;
+  return 0;
 }
 
 // HMPP (dsputils.c:196-213, 318-326) transforms every frame at 2^ceil(log2(longest window)) points; the peak-picking
@@ -1049,6 +1078,7 @@ extern "C" int llsm_gpu_batch_analyze(llsm_gpu_batch* b) {
   if(! hmpp && b -> opt.hm_method != LLSM_AOPTION_HMCZT) {
     llsm_set_error("unknown hm_method"); return -1;
   }
+  if(follow_conventions(b)) return -1;
   const llsm_gpu_layout& L = b -> lay;
   if(L.total_frames == 0) {
     // frameless batch: nothing to subtract, x_res = x (layer0.c:498-503 with no voiced frame)
@@ -1272,6 +1302,7 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
     llsm_set_error("llsm_soptions.fs must equal the sampling rate the batch was created with");
     return -1;
   }
+  if(follow_conventions(b)) return -1;
   const llsm_gpu_layout& L = b -> lay;
   if(L.total_frames == 0 || L.total_out == 0) return 0;
   const float fs = so -> fs, thop = b -> opt.thop;
@@ -1322,6 +1353,7 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
     double s = 0; for(float v : wf) s += (double)v * v;
     b -> inv_wsqr = (float)(1.0 / s);
     if(upload_vec(b -> win_filt, wf)) return -1;
+    b -> wsym_filt = hann_sym(b -> nwin_filt);
     b -> syn_fs = fs; b -> njobs_syn = 0;
   }
   if(so -> use_l1 && llsm_l1_prefetch_rows(b, so)) return -1;
@@ -1353,7 +1385,7 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
   int fused = -2;
   if(fused_ok)
     fused = launch_noise_filter_ola(P, d, b -> nf_units.p, b -> n_nf_units, b -> nf_halo, b -> yexc.p,
-      b -> d_y_off.p, b -> d_ny.p, b -> fnyq, fs, b -> nwin_filt, b -> win_filt.p, hann_sym(b -> nwin_filt), b -> inv_wsqr,
+      b -> d_y_off.p, b -> d_ny.p, b -> fnyq, fs, b -> nwin_filt, b -> win_filt.p, b -> wsym_filt, b -> inv_wsqr,
       ilog2(b -> nfft_filt), ynoise);
   if(fused != 0 && fused != -2) {
     llsm_set_error(std::string("launch_noise_filter_ola failed: ") + hipGetErrorString((hipError_t)fused));
@@ -1472,6 +1504,7 @@ extern "C" int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE 
     case 10: return lp::spgmwin(f0, fs, i);
     case 11: { int b2; float r; return lp::stretch_index(i, j, (int)f0, 128, & b2, & r); }
     case 12: { int b2; float r; lp::stretch_index(i, j, (int)f0, 128, & b2, & r); return b2; }
+    case 13: return filt_segments(i, i, j);
   }
   return -1;
 }

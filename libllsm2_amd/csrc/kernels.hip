@@ -1296,6 +1296,27 @@ DEV void unpack_pair(const float2* Z, int M, int logM, int k, float2* A, float2*
 // layer0.c:341), forward FFT of N/fold.  Persistent: each wavefront walks
 // frame pairs.  LDS: N float2 + N/2 float2 twiddles.
 // =====================================================================
+#ifndef SPGM_EDGE_F64
+#define SPGM_EDGE_F64 1                             // 0: bins 0 and N/2 of the spectrogram always as the float32 transform returns them (rounds 1 - 5)
+#endif
+// The exact DC and Nyquist sums of one Hann-windowed frame (window of ws samples centred on sample c of xs[0, nxe)), by one
+// wavefront: float64 window, products and sums.  Of k_spgm_env_wf only the FIX instantiation contains it: inside the
+// ordinary kernel -- inlined behind a rare branch, or as a real call -- its register needs made the compiler spill a
+// hundred values of the common path (profiles/r06_b_*).  The LDS kernel k_spgm_env uses it for every frame.
+DEV void spgm_exact_edges(const float* __restrict__ xs, int nxe, int c, int ws, int lane, double* dc, double* ny) {
+  const int half = ws / 2;
+  const double inv = 1.0 / (double)(ws - 1);
+  double sd = 0.0, sn = 0.0;
+  for(int j = lane; j < ws; j += WAVE) {             // window sample j sits at transform position (j - half) mod N
+    const int idx = c - half + j;
+    if(idx < 0 || idx >= nxe) continue;
+    const double t = (0.5 - 0.5 * cospi(2.0 * (double)j * inv)) * (double)xs[idx];
+    sd += t; sn += ((j - half) & 1) ? -t : t;
+  }
+#pragma unroll
+  for(int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o, WAVE); sn += __shfl_xor(sn, o, WAVE); }
+  *dc = sd; *ny = sn;
+}
 __global__ __launch_bounds__(WAVE) void k_spgm_env(
   const float* __restrict__ x, const int* __restrict__ x_off, const int* __restrict__ nx,
   const int* __restrict__ frm_utt, const int* __restrict__ frm_off,
@@ -1363,13 +1384,31 @@ __global__ __launch_bounds__(WAVE) void k_spgm_env(
         }
       }
     }
+    // The DC and Nyquist bins of both frames as exact real sums (spgm_exact_edges), for EVERY frame: this kernel serves
+    // the rare shapes (4096-point transforms, folds of 8 and more, PSD windows longer than the spectrogram), so a
+    // detection pass is not worth its code.  A frame whose edge bin lies 110 dB and more under its harmonics got the float32
+    // transform's rounding there instead, 0.03 nepers off in the envelope (tests/test_gpu_invariance.py).
+    float edge_log[2][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};   // (bin 0, bin N/2) of frames a, b
+#pragma unroll
+    for(int e = 0; e < 2; e ++) {
+      if(gg[e] >= nframes || wsz[e] <= 1) continue;       // (wave-uniform)
+      double sd, sn;
+      spgm_exact_edges(xsp[e], nxu2[e], cc[e], wsz[e], lane, & sd, & sn);
+      edge_log[e][0] = __logf((float)fabs(sd) * normalizer[e] + 1e-10f);
+      edge_log[e][1] = __logf((float)fabs(sn) * normalizer[e] + 1e-10f);
+    }
     __syncthreads();
     fft_dif(X, tw, 1, N, logN, lane);
     // log magnitude of both frames, written back over the (bit-reversed) bin pair k, N-k
     for(int k = lane; k <= N / 2; k += WAVE) {
       float2 A, B; unpack_pair(X, N, logN, k, & A, & B);
-      const float La = __logf(__builtin_amdgcn_sqrtf(A.x * A.x + A.y * A.y) * normalizer[0] + 1e-10f);
-      const float Lb = __logf(__builtin_amdgcn_sqrtf(B.x * B.x + B.y * B.y) * normalizer[1] + 1e-10f);
+      float La = __logf(__builtin_amdgcn_sqrtf(A.x * A.x + A.y * A.y) * normalizer[0] + 1e-10f);
+      float Lb = __logf(__builtin_amdgcn_sqrtf(B.x * B.x + B.y * B.y) * normalizer[1] + 1e-10f);
+      if((k == 0 || k == N / 2) && SPGM_EDGE_F64) {
+        const int s = k == 0 ? 0 : 1;
+        if(gg[0] < nframes && wsz[0] > 1) La = edge_log[0][s];
+        if(gg[1] < nframes && wsz[1] > 1) Lb = edge_log[1][s];
+      }
       X[brevN(k, logN)] = make_float2(La, Lb);
       X[brevN((N - k) & (N - 1), logN)] = make_float2(La, Lb);
     }
@@ -1451,29 +1490,8 @@ __global__ __launch_bounds__(WAVE, 2) void k_wf_selftest(const float2* __restric
 // N / nfft_psd): the frame pair stays in registers from the global load of the samples to
 // the global store of the envelope; LDS only carries the exchanges inside the transforms.
 // Element lane + 64 m of every length-N (or M3) sequence is register m of lane `lane`.
-#ifndef SPGM_EDGE_F64
-#define SPGM_EDGE_F64 1                             // 0: bins 0 and N/2 of the spectrogram always as the float32 transform returns them (rounds 1 - 5)
-#endif
 #define SPGM_SEED_LDS (2 * WAVE * sizeof(float4))  // the seed cache of k_spgm_env_wf: two float4 per lane behind the exchange buffer
 #define SPGM_EDGE_THRESH 12.7f                      // a DC / Nyquist bin this many nepers (110 dB) under the bin of the frame's F0: recompute exactly
-// The exact DC and Nyquist sums of one Hann-windowed frame (window of ws samples centred on sample c of xs[0, nxe)), by one
-// wavefront: float64 window, products and sums.  Only the FIX instantiation of k_spgm_env_wf contains it: inside the
-// ordinary kernel -- inlined behind a rare branch, or as a real call -- its register needs made the compiler spill a
-// hundred values of the common path (profiles/r06_b_*).
-DEV void spgm_exact_edges(const float* __restrict__ xs, int nxe, int c, int ws, int lane, double* dc, double* ny) {
-  const int half = ws / 2;
-  const double inv = 1.0 / (double)(ws - 1);
-  double sd = 0.0, sn = 0.0;
-  for(int j = lane; j < ws; j += WAVE) {             // window sample j sits at transform position (j - half) mod N
-    const int idx = c - half + j;
-    if(idx < 0 || idx >= nxe) continue;
-    const double t = (0.5 - 0.5 * cospi(2.0 * (double)j * inv)) * (double)xs[idx];
-    sd += t; sn += ((j - half) & 1) ? -t : t;
-  }
-#pragma unroll
-  for(int o = 32; o > 0; o >>= 1) { sd += __shfl_xor(sd, o, WAVE); sn += __shfl_xor(sn, o, WAVE); }
-  *dc = sd; *ny = sn;
-}
 // FIX = false: every frame pair; pairs with a DC / Nyquist bin under the threshold are appended to fix_list (pair index,
 // mask of the frames concerned).  FIX = true (second launch, usually a handful of pairs): the listed pairs once more,
 // bit for bit the same arithmetic, with the exact bins put in place of the transform's.
