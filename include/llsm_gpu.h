@@ -484,7 +484,8 @@ void llsm_gpu_set_default_seed(unsigned long long seed);
  * 8 env_ola(i,j) 9 dcwin(f0) 10 spgmwin(f0,i=nwin_psd) 13 time segments
  * the zero-phase band filter cuts a signal of i samples into when its slowest
  * pole reaches j samples (1: whole).  A function of the signal alone, so an
- * utterance gets the same bits in every batch. */
+ * utterance gets the same bits in every batch.  14 frames per unit of the
+ * harmonic overlap-add for a one-utterance batch of i frames, maxnhar j. */
 int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE thop,
   FP_TYPE fs, FP_TYPE rel_winsize);
 

@@ -128,6 +128,7 @@ extern "C" int llsm_gpu_get_convention(const char* name) {
 #ifndef NF_UNIT_DIV
 #define NF_UNIT_DIV 2048
 #endif
+static int sin_unit_frames(long long F, int nf, int nwin, int maxnhar);
 static int virtual_devices(void);
 static std::atomic<int> g_overlap([] { const char* e = std::getenv("LLSM_GPU_OVERLAP"); return (e && e[0] == '0') ? 0 : 1; }());
 extern "C" int llsm_gpu_analysis_overlap(int on) { return on < 0 ? g_overlap.load() : g_overlap.exchange(on > 0 ? 1 : 0); }
@@ -548,17 +549,9 @@ extern "C" llsm_gpu_batch* llsm_gpu_create_batch(llsm_gpu_context* ctx,
   {
     // work units of k_synth_ola: frames [i0, i1) of one utterance; about 8 wavefronts / SIMD over
     // the batch, never below 4 frames; halo as for the noise frames (window of nwin_sin samples)
-    const int udiv = std::min(SYN_UNIT_DIV, synth_ola_unit_div(b -> nwin_sin, std::min(L.maxnhar, 2048)));
-    int C = std::max(4, (int)((F + udiv - 1) / udiv));
-    if(const char* e = std::getenv("LLSM_GPU_SIN_UNIT")) C = std::max(1, std::atoi(e));   // tuning override
     std::vector<int4> units;
     for(int u = 0; u < n_utt; u ++) {
-      int nu = (nfrm[u] + C - 1) / C;                // equal units within the utterance (no short remainder unit)
-      // whole groups where the utterance is long enough for it (5 units of 40 frames would cost 3 idle wavefronts:
-      // 8 units of 25 instead), units never shorter than 4 frames (2 halo frames are recomputed per unit)
-      const int G = synth_ola_group_units();
-      if(nu % G && nfrm[u] >= 4 * ((nu + G - 1) / G * G)) nu = (nu + G - 1) / G * G;
-      const int sz = nu > 0 ? (nfrm[u] + nu - 1) / nu : 1;
+      const int sz = sin_unit_frames((long long)F, nfrm[u], b -> nwin_sin, L.maxnhar);
       for(int i0 = 0; i0 < nfrm[u]; i0 += sz) units.push_back(make_int4(u, i0, std::min(i0 + sz, nfrm[u]), 0));
       if(nfrm[u] == 0) units.push_back(make_int4(u, 0, 0, 0));   // frameless utterance: x_res = x, y_sin = 0
       // groups of synth_ola_group_units() (four) units never straddle utterances (k_synth_ola4: one workgroup, one phasor table per group);
@@ -1488,6 +1481,20 @@ int llsm_engine_big_fft(llsm_gpu_context* c, int N, size_t elems) {
 }
 int llsm_engine_device(llsm_gpu_context* c) { return c -> device; }
 
+// frames per unit of k_synth_ola for an utterance of nf frames in a batch of F frames (about 8 wavefronts / SIMD over
+// the batch, never below 4 frames).  llsm_gpu_plan_index case 14 exports it.
+static int sin_unit_frames(long long F, int nf, int nwin, int maxnhar) {
+  const int udiv = std::min(SYN_UNIT_DIV, synth_ola_unit_div(nwin, std::min(maxnhar, 2048)));
+  int C = std::max(4, (int)((F + udiv - 1) / udiv));
+  if(const char* e = std::getenv("LLSM_GPU_SIN_UNIT")) C = std::max(1, std::atoi(e));   // tuning override
+  int nu = (nf + C - 1) / C;                         // equal units within the utterance (no short remainder unit)
+  // whole groups where the utterance is long enough for it (5 units of 40 frames would cost 3 idle wavefronts:
+  // 8 units of 25 instead), units never shorter than 4 frames (2 halo frames are recomputed per unit)
+  const int G = synth_ola_group_units();
+  if(nu % G && nf >= 4 * ((nu + G - 1) / G * G)) nu = (nu + G - 1) / G * G;
+  return nu > 0 ? (nf + nu - 1) / nu : 1;
+}
+
 extern "C" int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE thop,
   FP_TYPE fs, FP_TYPE rel) {
   switch(which) {
@@ -1505,6 +1512,7 @@ extern "C" int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE 
     case 11: { int b2; float r; return lp::stretch_index(i, j, (int)f0, 128, & b2, & r); }
     case 12: { int b2; float r; lp::stretch_index(i, j, (int)f0, 128, & b2, & r); return b2; }
     case 13: return filt_segments(i, i, j);
+    case 14: return sin_unit_frames(i, i, lp::nwin_sin(thop, fs), j);
   }
   return -1;
 }

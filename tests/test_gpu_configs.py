@@ -7,7 +7,7 @@ import pytest
 
 import libllsm2_amd as llsm
 from conftest import make_speechlike, make_utterance
-from gpu_common import (analysis_metrics, aopt_kwargs, assert_contract, gpu_analyze, Yard, oracle32_metrics, params_to_gpu_rows,
+from gpu_common import (analysis_metrics, aopt_kwargs, assert_contract, assert_synthesis, synthesis_metrics, gpu_analyze, Yard, oracle32_metrics, params_to_gpu_rows,
                         rel_rms, report)
 from test_gpu_parity import SYN_TOL
 
@@ -72,15 +72,16 @@ def _run_parity(ctx, o64, cid, fs, thop, kw, x, f0, oracle_out=None, quiet=False
         yo, yso, yno = o64.synthesize(o64.soptions(fs), p32, seed=5)
     else:
         yo, yso, yno = oracle_out[2]
-    m.update(ysin_rel_rms=rel_rms(ys, yso), ynoise_rel_rms=rel_rms(yn, yno), y_rel_rms=rel_rms(y, yo))
+    assert len(yo) == len(y)
+    m.update(synthesis_metrics(pr.astype(np.float32).astype(np.float64), ys, yso, yn, yno, thop, fs, y, yo))
     try:
         assert_contract(m, Yard(okw, x, fs, f0), cid)
     finally:
         if not quiet:
             report("config_" + cid, m)
-    assert len(yo) == len(y)
     for k in ("ysin_rel_rms", "ynoise_rel_rms", "y_rel_rms"):
         assert m[k] <= SYN_TOL, (cid, k, m[k])
+    assert_synthesis(m, cid)
     return m
 
 

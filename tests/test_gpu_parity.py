@@ -9,7 +9,7 @@ import pytest
 
 import libllsm2_amd as llsm
 from conftest import FS, make_speechlike, make_utterance, wrap
-from gpu_common import (analysis_metrics, aopt_kwargs, assert_contract, assert_hmpp_contract, gpu_analyze, Yard, oracle32_metrics, oracle_analyze,
+from gpu_common import (analysis_metrics, aopt_kwargs, assert_contract, assert_hmpp_contract, assert_synthesis, synthesis_metrics, gpu_analyze, Yard, oracle32_metrics, oracle_analyze,
                         params_to_gpu_rows, rel_rms, report)
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +84,7 @@ def test_synthesis_parity_small_batch(ctx, o64):
                                   y_rel_rms=rel_rms(y[sl], yo), ysin_abs_max=float(np.abs(ys[sl] - yso).max()),
                                   ynoise_abs_max=float(np.abs(yn[sl] - yno).max()),
                                   ysin_rms=float(np.sqrt(np.mean(yso ** 2))), ynoise_rms=float(np.sqrt(np.mean(yno ** 2))))
+            rep[f"utt{u}"]["local"] = synthesis_metrics(p32, ys[sl], yso, yn[sl], yno, pr.thop, FS, y[sl], yo)
         report("synthesis_small", rep)
         for u, m in rep.items():
             if m["ysin_rms"] > 0:
@@ -91,6 +92,7 @@ def test_synthesis_parity_small_batch(ctx, o64):
             else:
                 assert m["ysin_abs_max"] == 0, (u, m)
             assert m["ynoise_rel_rms"] <= SYN_TOL and m["y_rel_rms"] <= SYN_TOL, (u, m)
+            assert_synthesis(m["local"], u)
     finally:
         b.close()
 
@@ -113,8 +115,11 @@ def test_injected_white_templates(ctx, o64):
         ctx.sync()
         yn = b.download(llsm.A_YNOISE)
         p32 = pr.astype(np.float32).astype(np.float64)
-        _, _, yno = o64.synthesize(o64.soptions(FS), p32, seed=0, white=white[0, :, :ntpl].astype(np.float64))
+        _, yso, yno = o64.synthesize(o64.soptions(FS), p32, seed=0, white=white[0, :, :ntpl].astype(np.float64))
         assert rel_rms(yn, yno) <= SYN_TOL
+        m = synthesis_metrics(p32, b.download(llsm.A_YSIN), yso, yn, yno, pr.thop, FS)
+        report("injected_white", m)
+        assert_synthesis(m, "injected_white")
     finally:
         b.close()
 

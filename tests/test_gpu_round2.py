@@ -11,7 +11,7 @@ import pytest
 
 import libllsm2_amd as llsm
 from conftest import FS, make_speechlike, make_utterance
-from gpu_common import (analysis_metrics, aopt_kwargs, assert_contract, gpu_analyze, Yard, oracle32_metrics, oracle_analyze,
+from gpu_common import (analysis_metrics, aopt_kwargs, assert_contract, assert_synthesis, synthesis_metrics, gpu_analyze, Yard, oracle32_metrics, oracle_analyze,
                         params_to_gpu_rows, rel_rms, report)
 from test_gpu_parity import SYN_TOL
 from test_gpu_rt import chunk_from_oracle, rt_run
@@ -176,6 +176,9 @@ def test_synthesis_at_another_sampling_rate(ctx, o64):
         rep[str(int(fs2))] = m
         for k, v in m.items():
             assert v <= SYN_TOL, (fs2, k, v)
+        mloc = synthesis_metrics(p32, ys, yso, yn, yno, pr.thop, fs2, y, yo)
+        rep[str(int(fs2)) + "_local"] = mloc
+        assert_synthesis(mloc, fs2)
         # drop-in: a 44.1 kHz chunk through llsm_synthesize with options->fs = fs2 (the reference accepts it)
         ch = chunk_from_oracle(L, ao, pr, FS)
         so = llsm.make_soptions(fs2)

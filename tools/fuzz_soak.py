@@ -1,6 +1,8 @@
 """One-off soak: the seeded configuration fuzz of tests/test_gpu_configs.py over many more seeds than the suite runs.
     python tools/fuzz_soak.py [first_seed] [count]        (SOAK_ONLY=layer0,l1rt,hmpp,alt,coder picks sweeps;
-                                                           SOAK_PROCS=n oracle worker processes, default = CPUs)
+                                                           SOAK_PROCS=n oracle worker processes, default = CPUs;
+                                                           SOAK_CALIBRATE=1 records the metrics of gpu_common.HARM_CEILING
+                                                           and SYN_CEILING without asserting them)
 Layer 0: the float64 oracle runs in worker processes (forked BEFORE the device is opened; they never touch it), the
 product in this one.  One line per seed outside the contract of tests/gpu_common.py (FAIL), one per seed that the
 superseded round-2 ... round-4 tolerances would have flagged (MARGINAL: these go into tests/test_gpu_regressions.py),
@@ -17,6 +19,10 @@ from oracle.oracle import Oracle
 from test_gpu_configs import _fuzz_case, _run_parity, other_rate_case
 from gpu_common import CONDITIONED, CONTRACT, aopt_kwargs
 
+if os.environ.get("SOAK_CALIBRATE"):                         # calibration of the ceilings: measure, do not assert them
+    import gpu_common
+    gpu_common.HARM_CEILING = {}
+    gpu_common.SYN_CEILING = {}
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 only = [t for t in os.environ.get("SOAK_ONLY", "").split(",") if t]
@@ -97,6 +103,7 @@ for k in range(n0):
         f32 = {t: m.get(t + "_f32_oracle") for t in CONDITIONED if m.get(t + "_f32_oracle") is not None}
         print("MARGINAL seed", seed, fs, round(thop, 7), old, "float32 oracle:", f32, flush=True)
     for t in list(CONTRACT) + list(CONDITIONED) + ["ampl_abs_over_max", "ysin_rel_rms", "ynoise_rel_rms", "y_rel_rms"] + \
+            ["ampl_rel_max_m80_to_m40db", "phse_max_rad_m80_to_m40db", "ysin_local", "ynoise_local"] + \
             [k_ for k_ in m if k_.startswith(("psd_db_max_", "psdraw_db_max_", "psd_pow", "psdraw_pow", "psd_over_0p05_db_", "psdres_db_max"))]:
         if t not in worst or m[t] > worst[t][0]:
             worst[t] = (m[t], seed)
