@@ -485,7 +485,9 @@ void llsm_gpu_set_default_seed(unsigned long long seed);
  * the zero-phase band filter cuts a signal of i samples into when its slowest
  * pole reaches j samples (1: whole).  A function of the signal alone, so an
  * utterance gets the same bits in every batch.  14 frames per unit of the
- * harmonic overlap-add for a one-utterance batch of i frames, maxnhar j. */
+ * harmonic overlap-add for a one-utterance batch of i frames, maxnhar j.
+ * 15 first output sample of unit j of the noise excitation in an utterance of
+ * i samples, -1 past its last unit. */
 int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE thop,
   FP_TYPE fs, FP_TYPE rel_winsize);
 

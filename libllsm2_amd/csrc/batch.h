@@ -133,6 +133,7 @@ struct llsm_gpu_batch {
   DevBuf<int> env_over;                              // plan overflow flag
   DevBuf<int4> nf_units; int n_nf_units = 0, nf_halo = 0;   // work units of the fused noise filter + overlap-add
   DevBuf<int4> sin_units; int n_sin_units = 0, sin_halo = 0; // ... and of the fused harmonic frames + overlap-add
+  DevBuf<int4> exu_units; int n_exu_units = 0;      // ... and of the persistent noise excitation (two int4 per unit)
   DevBuf<int> live;
   DevBuf<float> win_sin, win_psd, win_env, win_filt;
   DevBuf<FiltSectionD> sections; DevBuf<FiltJob> jobs_ana, jobs_syn;

@@ -129,6 +129,7 @@ extern "C" int llsm_gpu_get_convention(const char* name) {
 #define NF_UNIT_DIV 2048
 #endif
 static int sin_unit_frames(long long F, int nf, int nwin, int maxnhar);
+static int excite_unit_start(int ny, int S, int k);
 static int virtual_devices(void);
 static std::atomic<int> g_overlap([] { const char* e = std::getenv("LLSM_GPU_OVERLAP"); return (e && e[0] == '0') ? 0 : 1; }());
 extern "C" int llsm_gpu_analysis_overlap(int on) { return on < 0 ? g_overlap.load() : g_overlap.exchange(on > 0 ? 1 : 0); }
@@ -588,7 +589,7 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> d_frm_off.release(); b -> d_y_off.release(); b -> d_frm_utt.release(); b -> d_pairs.release(); b -> d_hblocks.release();
   b -> packed.release(); b -> ce.release(); b -> mid.release(); b -> iir_tmp.release(); b -> iir_edge[0].release(); b -> iir_edge[1].release(); b -> iir_seg[0].release(); b -> iir_seg[1].release();
   b -> env.release(); b -> psd_log.release(); b -> pbuf.release(); b -> spgm_fix.release(); b -> spgm_fix_count.release();
-  b -> colored.release(); b -> env_cplx.release(); b -> env_hits.release(); b -> env_over.release(); b -> nf_units.release(); b -> sin_units.release(); b -> yexc.release(); b -> nframes.release();
+  b -> colored.release(); b -> env_cplx.release(); b -> env_hits.release(); b -> env_over.release(); b -> nf_units.release(); b -> sin_units.release(); b -> exu_units.release(); b -> yexc.release(); b -> nframes.release();
   b -> live.release(); b -> win_sin.release(); b -> win_psd.release(); b -> win_env.release();
   b -> win_filt.release(); b -> nfft_u.release(); b -> sections.release(); b -> jobs_ana.release(); b -> jobs_syn.release();
   b -> l1_model_power.release(); b -> l1_model_param.release(); b -> l1_model_inv_t.release(); b -> l1_model_cumlog_t.release(); b -> l1_rd_raw.release(); b -> l1_cont.release();
@@ -1342,6 +1343,20 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
       b -> nf_halo = (int)std::floor((b -> nfft_filt + 1) / std::max(hop, 1.0));
       if(upload_vec(b -> nf_units, units)) return -1;
     }
+    {
+      // work units of k_excite_units: runs of excite_unit_samples() output samples of one utterance, cut from the
+      // utterance's own length only (the same samples form a unit alone and in any batch)
+      const int S = excite_unit_samples();
+      std::vector<int4> units;
+      for(int u = 0; u < b -> lay.n_utt; u ++)
+        for(int k = 0; excite_unit_start(b -> ny[u], S, k) >= 0; k ++) {
+          const int s0 = excite_unit_start(b -> ny[u], S, k);
+          units.push_back(make_int4(u, s0, std::min(S, b -> ny[u] - s0), b -> ny[u]));
+          units.push_back(make_int4(b -> frm_off[u], b -> nfrm[u], b -> y_off[u], 0));
+        }
+      b -> n_exu_units = (int)(units.size() / 2);
+      if(! units.empty() && upload_vec(b -> exu_units, units)) return -1;
+    }
     std::vector<float> wf = make_hann(b -> nwin_filt);
     double s = 0; for(float v : wf) s += (double)v * v;
     b -> inv_wsqr = (float)(1.0 / s);
@@ -1367,10 +1382,14 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
   float* ysin = (float*)b -> arr[LLSM_GPU_YSIN];
   if(! use_injected_white) RUN(launch_white(P, d, white, L.ntemplate_ext, b -> d_ny.p, seed));
   RUN(launch_filtfilt(P, b -> jobs_syn.p, b -> njobs_syn, b -> sections.p));
-  RUN(launch_env_params(P, d, b -> env_cplx.p));
-  RUN(launch_excite_env(P, d, b -> colored.p, L.ntemplate_ext, b -> env_hits.p, b -> env_cplx.p,
+  // noise excitation: persistent units (k_excite_units) where the geometry allows and $LLSM_GPU_EXCITE4 is unset; set,
+  // it selects the per-sample kernel (0) or the template-position one (1) after k_env_params
+  const char* e4 = std::getenv("LLSM_GPU_EXCITE4");   // (read per call: tests switch it)
+  const bool by_units = !(e4 && e4[0]) && excite_units_ok(d, b -> nwin_env, fs);
+  if(! by_units) RUN(launch_env_params(P, d, b -> env_cplx.p));
+  RUN(launch_excite_env(P, d, b -> colored.p, L.ntemplate_ext, b -> env_hits.p, by_units ? nullptr : b -> env_cplx.p,
     b -> nwin_env, b -> win_env.p, b -> nch_active, b -> d_y_off.p, b -> d_ny.p, b -> max_ny, fs,
-    b -> yexc.p));
+    b -> yexc.p, b -> exu_units.p, b -> n_exu_units));
   // b -> fnyq: the PSD rows' axis (conf FNYQ; analysis fs / 2, layer0.c:481).  Transforms up to 2048 points: filter and overlap-add
   // in one kernel (the shaped frames stay on chip); larger ones: frames to HBM, gathered by the mix.
   float* ynoise = (float*)b -> arr[LLSM_GPU_YNOISE];
@@ -1481,6 +1500,13 @@ int llsm_engine_big_fft(llsm_gpu_context* c, int N, size_t elems) {
 }
 int llsm_engine_device(llsm_gpu_context* c) { return c -> device; }
 
+// first output sample of unit k of k_excite_units in an utterance of ny samples (units of S samples, the last one
+// shorter), -1 past the last unit.  llsm_gpu_plan_index case 15 exports it.
+static int excite_unit_start(int ny, int S, int k) {
+  const long long s0 = (long long)k * S;
+  return k >= 0 && s0 < ny ? (int)s0 : -1;
+}
+
 // frames per unit of k_synth_ola for an utterance of nf frames in a batch of F frames (about 8 wavefronts / SIMD over
 // the batch, never below 4 frames).  llsm_gpu_plan_index case 14 exports it.
 static int sin_unit_frames(long long F, int nf, int nwin, int maxnhar) {
@@ -1513,6 +1539,7 @@ extern "C" int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE 
     case 12: { int b2; float r; lp::stretch_index(i, j, (int)f0, 128, & b2, & r); return b2; }
     case 13: return filt_segments(i, i, j);
     case 14: return sin_unit_frames(i, i, lp::nwin_sin(thop, fs), j);
+    case 15: return excite_unit_start(i, excite_unit_samples(), j);
   }
   return -1;
 }

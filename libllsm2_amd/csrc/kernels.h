@@ -129,9 +129,14 @@ int launch_unpack_frames(LaunchCtx* P, const BatchDev& d, const LlsmPackedLayout
 int launch_scatter_outputs(LaunchCtx* P, int n_utt, int max_ny, const float* y, const float* ysin, const float* ynoise,
   const int* y_off, const int* ny, float* const* tab);
 int launch_env_plan(LaunchCtx* P, int max_ny, int max_nfrm, int nwin_env, float thop, float fs, int2* hits, int* over);
+// cplx == NULL: k_excite_units over `units` (two int4 per unit: {u, s0, samples, ny}, {frm_off, nfrm, y_off, 0}), which
+// forms the complex amplitudes itself; otherwise the k_env_params rows feed k_excite_env / k_excite_env4
 int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int ntemplate_ext,
   const int2* hits, const float2* cplx, int nwin_env, const float* win, int nch_active,
-  const int* out_off, const int* out_len, int max_len, float fs_syn, float* yexc);
+  const int* out_off, const int* out_len, int max_len, float fs_syn, float* yexc,
+  const int4* units = nullptr, int nunits = 0);
+bool excite_units_ok(const BatchDev& d, int nwin_env, float fs_syn);   // the geometry k_excite_units takes
+int excite_unit_samples();                            // output samples per unit of k_excite_units
 int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
   const int* out_off, const int* out_len, float fnyq_conf, float fs_syn, int nwin,
   const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax,

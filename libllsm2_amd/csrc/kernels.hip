@@ -2624,6 +2624,208 @@ __global__ __launch_bounds__(256) void k_excite_env(
   yexc[(size_t)out_off[u] + idx] = acc;
 }
 
+// S3 + S3b, third form (round 7): the per-sample kernel above, made persistent.  Its wavefronts lived for one 256-sample
+// block each and spent 81 % of that life waiting: frame rows -> LDS -> barrier -> env_hits -> window -> template gathers
+// -> one store, every round trip exposed.  Here a workgroup walks work units of EXU_Q x 256 consecutive output samples
+// of one utterance (table: llsm_gpu_batch_synthesize), thread t owning samples s0 + t + 256 q.  Every global load of a unit
+// -- the raw rows of its frames, its env_hits entries and its template samples -- is ISSUED one unit ahead, right
+// after the current unit's frame parameters reach LDS and before its arithmetic, and consumed at the top of the next
+// turn (the k_noise_filter_ola recipe).  The complex amplitudes are formed here with k_env_params' expression, once per
+// unit; the template index is seeded with one division per lane and unit and advanced by 256 per sample; the window
+// sits in LDS.  Per sample the (frame, offset) pairs, the phasors, the accumulation order, the square root and the
+// channel sum are those of k_excite_env: y_noise is the same bits.
+#ifndef EXU_Q
+#define EXU_Q 3                                     // samples per thread and unit: 768 samples (measured: 512 0.506, 768 0.461, 1024 0.488 ms)
+#endif
+#define EXU_SLOTS 16                                // frames staged per unit: hop >= 256 EXU_Q / 10 samples (launch_excite_env)
+#define EXU_WMAX 2048                               // envelope window samples kept in LDS
+#ifndef EXU_WPE
+#define EXU_WPE 4                                   // wavefronts per SIMD the register budget is cut for (ME = 8: one fewer)
+#endif
+template <int NCH, int ME>
+__global__ __launch_bounds__(256, ME > 4 ? EXU_WPE - 1 : EXU_WPE) void k_excite_units(
+  const int4* __restrict__ units, int nunits, const float* __restrict__ colored, int ntemplate_ext,
+  const int2* __restrict__ hits, const float* __restrict__ f0, const int* __restrict__ nhar_e,
+  const float* __restrict__ eamp, const float* __restrict__ ephs, const float* __restrict__ edc,
+  int nwin_env, const float* __restrict__ win, int nch, int me, int nch_active, float thop, float fs,
+  float* __restrict__ yexc) {
+  constexpr int NP = EXU_SLOTS * NCH * ME, EP = NP / 256;   // amplitudes per unit, per thread
+  static_assert(NP % 256 == 0 && EXU_SLOTS * NCH <= 256, "one staging pass per thread");
+  __shared__ float2 s_cp[EXU_SLOTS][NCH * ME];
+  __shared__ float s_off[EXU_SLOTS][NCH];
+  __shared__ float s_turn[EXU_SLOTS];               // f0 / fs, <= 0 when unvoiced
+  __shared__ float s_win[EXU_WMAX];
+  const int tid = threadIdx.x;
+  for(int j = tid; j < nwin_env; j += 256) s_win[j] = win[j];
+  const float hop = lp::fmul(thop, fs);
+  const int half = nwin_env / 2;
+  const int G = gridDim.x;
+  // staged unit: descriptor {u, s0, n, ny}, {frm_off, nfrm, y_off, -}, then per thread
+  int4 sd0, sd1; int simin;
+  float sa[EP], sp[EP], sf[EP]; int sk[EP];         // amplitude, phase, f0 and nhar_e of element tid + 256 e
+  float so, st;                                     // edc of (slot, channel) tid, f0 of slot tid
+  int2 sh[EXU_Q][EXC_HITS]; float stv[EXU_Q][NCH]; int sb[EXU_Q];
+  // every load is issued whatever the unit: an absent unit (n = 0, nfrm = 0) reads element 0 of each table and empty
+  // template ranges (a conditional call kept the previous unit's registers alive through the whole turn)
+  auto stage = [&](int4 d0, int4 d1) {
+    const int u = d0.x, s0 = d0.y, n = d0.z, ny = d0.w, fo = d1.x, nf = d1.y;
+    const int imin = max(0, (int)((float)s0 / hop) - 2);
+    simin = imin; sd0 = d0; sd1 = d1;
+#pragma unroll
+    for(int e = 0; e < EP; e ++) {
+      const int el = tid + 256 * e, sl = el / (NCH * ME), r = el % (NCH * ME), c = r / ME, k = r % ME, i = imin + sl;
+      const bool in = i < nf && c < nch && k < me;
+      const size_t g = in ? (size_t)(fo + i) : 0, x = in ? (g * nch + c) * me + k : 0;
+      sa[e] = eamp[x]; sp[e] = ephs[x]; sf[e] = in ? f0[g] : 0.0f; sk[e] = in ? nhar_e[g] : 0;
+    }
+    {
+      const int sl = tid / NCH, c = tid % NCH, i = imin + sl;
+      const bool in = tid < EXU_SLOTS * NCH && i < nf && c < nch;
+      so = edc[in ? (size_t)(fo + i) * nch + c : 0];
+      if(! in) so = 0.0f;
+      const bool it = tid < EXU_SLOTS && imin + tid < nf;
+      st = f0[it ? fo + imin + tid : 0];
+      if(! it) st = 0.0f;
+    }
+    // template index of sample s0 + tid + 256 q (plan.h stretch_index, ov = 128): (m, ri) with p = T + m T + ri, m = -1
+    // below the first cross-fade; one division per lane and unit, then one step of 256 per sample
+    const int nt = min(20000, ny);
+    const bool tiled = ny > nt;
+    const int T = nt - 128;
+    const int p0 = s0 + tid;
+    int m = -1, ri = p0;
+    if(tiled && p0 >= T) { const int q = p0 - T; m = q / T; ri = q - m * T; }
+    buf_t rng[NCH];
+#pragma unroll
+    for(int c = 0; c < NCH; c ++)
+      rng[c] = buf_range(colored + ((size_t)u * nch + c) * ntemplate_ext, 0, c < nch_active ? ntemplate_ext : 0);
+#pragma unroll
+    for(int q = 0; q < EXU_Q; q ++) {
+      const bool ok = tid + 256 * q < n;
+      int a = ri, b = -1;
+      if(m >= 0 && ri < 128) {
+        const bool applied = m == 0 ? true : ny >= nt + m * T;   // (m == 0: ny > nt holds when tiled)
+        a = T + ri;
+        if(applied) b = ri;
+      }
+      const size_t hp = ok ? (size_t)(p0 + 256 * q) * EXC_HITS : 0;
+#pragma unroll
+      for(int hh = 0; hh < EXC_HITS; hh ++) sh[q][hh] = hits[hp + hh];
+#pragma unroll
+      for(int c = 0; c < NCH; c ++) stv[q][c] = ld_range(rng[c], ok ? a : -1);
+      sb[q] = ok ? b : -1;
+      ri += 256;
+      if(tiled && ri >= T) { ri -= T; m ++; }      // T >= 19 872: at most one tile boundary per step
+    }
+  };
+  int un = xcd_frame(blockIdx.x, G);
+  const int4 z4 = make_int4(0, 0, 0, 0);
+  stage(un < nunits ? units[2 * un] : z4, un < nunits ? units[2 * un + 1] : z4);
+  for(; un < nunits; un += G) {
+    const int u = sd0.x, s0 = sd0.y, n = sd0.z, nf = sd1.y, yo = sd1.z, imin = simin;
+    __syncthreads();                                // (the previous unit's readers are done; the window is in)
+#pragma unroll
+    for(int e = 0; e < EP; e ++) {
+      const int el = tid + 256 * e, sl = el / (NCH * ME), r = el % (NCH * ME), k = r % ME;
+      const int K = sf[e] > 0 ? min(sk[e], me) : 0;   // k_env_params
+      float2 v = make_float2(0.0f, 0.0f);
+      if(k < K) {
+        float sn, co; sincosf(sp[e], & sn, & co);
+        const float a = sa[e];
+        v = make_float2(a * co, a * sn);
+      }
+      s_cp[sl][r] = v;
+    }
+    if(tid < EXU_SLOTS * NCH) s_off[tid / NCH][tid % NCH] = so;
+    if(tid < EXU_SLOTS) s_turn[tid] = st / fs;
+    // the current unit's pairs as (slot << 11 | offset), -1 when absent; its template samples and cross-fade partners
+    int ch[EXU_Q][EXC_HITS]; float ctv[EXU_Q][NCH]; int cb[EXU_Q];
+#pragma unroll
+    for(int q = 0; q < EXU_Q; q ++) {
+      cb[q] = sb[q];
+#pragma unroll
+      for(int hh = 0; hh < EXC_HITS; hh ++) {
+        const int2 hit = sh[q][hh];
+        const int sl = min(max(hit.x - imin, 0), EXU_SLOTS - 1);   // (in range: launch_excite_env)
+        ch[q][hh] = hit.x < 0 || hit.x >= nf ? -1 : sl << 11 | hit.y;   // (offset < nwin_env <= EXU_WMAX = 2048)
+      }
+#pragma unroll
+      for(int c = 0; c < NCH; c ++) ctv[q][c] = stv[q][c];
+    }
+    __syncthreads();
+    {
+      const int nx = un + G;
+      stage(nx < nunits ? units[2 * nx] : z4, nx < nunits ? units[2 * nx + 1] : z4);
+    }
+    // k_excite_env's terms of one pair, added to ev.  An absent pair (pk < 0) computes on a staged frame and adds
+    // nothing: the sum is SELECTED, so the two pairs of a sample go through one branch-free stretch of code whose
+    // chains interleave
+    auto term = [&](int pk, float (&ev)[NCH]) {
+      const int sl = (pk >> 11) & (EXU_SLOTS - 1), j = pk & 2047;
+      const float w = s_win[j];
+      const float tn = s_turn[sl];
+      float z1r = 1.0f, z1i = 0.0f;
+#if EXC_FAST
+      const float ph = tn * (float)(j - half);
+      const float cr = __builtin_amdgcn_cosf(ph), si = __builtin_amdgcn_sinf(ph);
+      if(tn > 0) { z1r = cr; z1i = si; }
+#else
+      if(tn > 0) cs_turns((double)tn * (double)(j - half), & z1r, & z1i);
+#endif
+      float zr[ME], zi[ME];                          // e^{j k th}, k = 1 .. ME
+      zr[0] = z1r; zi[0] = z1i;
+#pragma unroll
+      for(int k = 1; k < ME; k ++) {
+        zr[k] = zr[k - 1] * z1r - zi[k - 1] * z1i; zi[k] = zr[k - 1] * z1i + zi[k - 1] * z1r;
+      }
+#pragma unroll
+      for(int c = 0; c < NCH; c ++) {
+        // k_excite_env starts from y = 0.0f: the sums differ only where a partial sum is a zero of the other sign,
+        // and fmaxf(y + edc, 1e-8f) maps both to the same value (one addition fewer per channel and pair)
+        float y = s_cp[sl][c * ME].x * zr[0] - s_cp[sl][c * ME].y * zi[0];
+#pragma unroll
+        for(int k = 1; k < ME; k ++) {               // amplitudes are zero beyond nhar_e
+          const float2 av = s_cp[sl][c * ME + k];
+          y += av.x * zr[k] - av.y * zi[k];
+        }
+        const float s = ev[c] + fmaxf(y + s_off[sl][c], 1e-8f) * w;
+        ev[c] = pk >= 0 ? s : ev[c];
+      }
+    };
+#pragma unroll
+    for(int q = 0; q < EXU_Q; q ++) {
+      float e[NCH];
+#pragma unroll
+      for(int c = 0; c < NCH; c ++) e[c] = 0.0f;
+      term(ch[q][0], e);
+      term(ch[q][1], e);
+      if(ch[q][2] >= 0) term(ch[q][2], e);           // a third frame on a sample: none at nwin = 2 hop + 1
+      const int p = s0 + tid + 256 * q;
+      const int b = cb[q];
+      const float r = b >= 0 ? (float)b / 128.0f : 0.0f;
+      const float xf = b >= 0 ? __frsqrt_rn(2.0f * r * (r - 1.0f) + 1.0f) : 1.0f;
+      float acc = 0;
+#pragma unroll
+      for(int c = 0; c < NCH; c ++) {
+        if(c < nch_active) {
+          float v = ctv[q][c];
+          if(b >= 0) {                               // cross-fade: 128 samples per tile, its second sample read here
+            v *= 1.0f - r;
+            v += colored[((size_t)u * nch + c) * ntemplate_ext + b] * r;
+            v *= xf;
+          }
+#if EXC_FAST
+          v *= __builtin_amdgcn_sqrtf(e[c]);
+#else
+          v *= sqrtf(e[c]);
+#endif
+          acc += v;
+        }
+      }
+      if(tid + 256 * q < n) yexc[(size_t)yo + p] = acc;
+    }
+  }
+}
 
 // S3 + S3b, second form (round 5): the same sums, arranged by TEMPLATE position.  k_excite_env above walks the output
 // samples, so every template sample is fetched once per tile of the stretched noise (2.23 tiles at 1 s: 925 MB of
@@ -4492,10 +4694,38 @@ int launch_env_plan(LaunchCtx* P, int max_ny, int max_nfrm, int nwin_env, float 
   return 0;
 }
 
+// Geometries k_excite_units takes: up to 4 channels and 8 envelope harmonics, the window in LDS, and every frame a
+// unit's samples lie under among its EXU_SLOTS staged ones.  A hit (i, j) of sample p has i - 1 within 1 / 2 + nwin / hop
+// of p / hop - j / hop, so with nwin <= 2 hop + 1 the frames of samples [s0, s0 + S) are floor(s0 / hop) - 1 ..
+// floor((s0 + S - 1) / hop) + 2: S / hop + 5 of them counting the kernel's one frame of margin below.
+bool excite_units_ok(const BatchDev& d, int nwin_env, float fs_syn) {
+  const double hop = (double)lp::fmul(d.thop, fs_syn);
+  return d.nchannel <= 4 && d.maxnhar_e <= 8 && nwin_env <= EXU_WMAX && nwin_env <= 2.0 * hop + 1.0 &&
+    256.0 * EXU_Q / hop + 6.0 <= EXU_SLOTS;
+}
+int excite_unit_samples() { return 256 * EXU_Q; }
+// Workgroups of k_excite_units: one per resident slot (the kernel is a loop over units), at most one per unit.
+template <class K>
+static int resident_blocks(K kernel, int block, size_t lds) {
+  static std::mutex mx; static std::map<const void*, int> cache;
+  std::lock_guard<std::mutex> lock(mx);
+  auto it = cache.find((const void*)kernel);
+  if(it != cache.end()) return it -> second;
+  int per_cu = 0, dev = 0, cus = 0;
+  if(hipOccupancyMaxActiveBlocksPerMultiprocessor(& per_cu, kernel, block, lds) != hipSuccess) { per_cu = 0; (void)hipGetLastError(); }
+  if(hipGetDevice(& dev) != hipSuccess || hipDeviceGetAttribute(& cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { cus = 0; (void)hipGetLastError(); }
+  const int r = std::max(per_cu * cus, 256);
+  cache[(const void*)kernel] = r;
+  return r;
+}
+
 int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int ntemplate_ext,
   const int2* hits, const float2* cplx, int nwin_env, const float* win, int nch_active,
-  const int* out_off, const int* out_len, int max_len, float fs_syn, float* yexc) {
+  const int* out_off, const int* out_len, int max_len, float fs_syn, float* yexc,
+  const int4* units, int nunits) {
   if(d.n_utt == 0 || max_len == 0) return 0;
+  // default: persistent units (k_excite_units), which form the complex amplitudes themselves; $LLSM_GPU_EXCITE4=0 the
+  // per-sample kernel, =1 the template-position one, both after k_env_params (the caller launches it when cplx != NULL)
 #define EX_ARGS colored, ntemplate_ext, hits, cplx, d.edc, d.f0, nwin_env, win, d.nchannel, d.maxnhar_e, \
     nch_active, d.frm_off, d.nfrm, out_off, out_len, d.thop, fs_syn, yexc
   // $LLSM_GPU_EXCITE4=1: by template position, four samples per thread (k_excite_env4).  Measured and NOT the default:
@@ -4504,6 +4734,19 @@ int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int
   // instead of 8 wavefronts per SIMD and three dependent table / LDS rounds per tile.  Kept for its test and as a base.
   const char* e4 = std::getenv("LLSM_GPU_EXCITE4");   // (read per launch: tests switch it)
   const bool by_template = e4 && e4[0] == '1';
+  if(! cplx) {
+    if(nunits == 0) return 0;
+    if(d.maxnhar_e <= 4) {
+      const int g = std::min(nunits, resident_blocks(k_excite_units<4, 4>, 256, 0));
+      LAUNCH("k_excite_units", (k_excite_units<4, 4>), dim3(g), dim3(256), 0, units, nunits, colored, ntemplate_ext, hits,
+        d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, nwin_env, win, d.nchannel, d.maxnhar_e, nch_active, d.thop, fs_syn, yexc);
+    } else {
+      const int g = std::min(nunits, resident_blocks(k_excite_units<4, 8>, 256, 0));
+      LAUNCH("k_excite_units", (k_excite_units<4, 8>), dim3(g), dim3(256), 0, units, nunits, colored, ntemplate_ext, hits,
+        d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, nwin_env, win, d.nchannel, d.maxnhar_e, nch_active, d.thop, fs_syn, yexc);
+    }
+    return 0;
+  }
   if(by_template && d.nchannel <= 4 && d.maxnhar_e <= 8) {
     const dim3 grid4((std::min(max_len, 20000) + 1023) / 1024, d.n_utt);
     if(d.maxnhar_e <= 4) LAUNCH("k_excite_env4", (k_excite_env4<4, 4>), grid4, dim3(256), 0, EX_ARGS);
