@@ -16,9 +16,9 @@
 #include <string>
 #include <vector>
 
+#include "kernels.h"                                // first: its guard tests the tuning switches before cheby.h sets IIR_SEG
 #include "cheby.h"
 #include "engine.h"
-#include "kernels.h"
 #include "llsm_gpu.h"
 #include "plan.h"
 #include "batch.h"
@@ -1383,7 +1383,7 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
   if(! use_injected_white) RUN(launch_white(P, d, white, L.ntemplate_ext, b -> d_ny.p, seed));
   RUN(launch_filtfilt(P, b -> jobs_syn.p, b -> njobs_syn, b -> sections.p));
   // noise excitation: persistent units (k_excite_units) where the geometry allows and $LLSM_GPU_EXCITE4 is unset; set,
-  // it selects the per-sample kernel (0) or the template-position one (1) after k_env_params
+  // it selects the per-sample kernel after k_env_params
   const char* e4 = std::getenv("LLSM_GPU_EXCITE4");   // (read per call: tests switch it)
   const bool by_units = !(e4 && e4[0]) && excite_units_ok(d, b -> nwin_env, fs);
   if(! by_units) RUN(launch_env_params(P, d, b -> env_cplx.p));

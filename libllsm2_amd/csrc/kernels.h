@@ -3,6 +3,21 @@
 #ifndef LLSM_AMD_KERNELS_H
 #define LLSM_AMD_KERNELS_H
 
+// Build switches of experiments only.  Timing ablations and deliberately wrong builds (KAL_ABL, NF_ABL, KAL_BREAK and the
+// hooks of tools/kbench_experiments.h) and the tuning constants below (their defaults sit beside their kernels) can only be
+// set together with -DLLSM_KBENCH_EXPERIMENTS, which tools/kbench.py --build adds: a stray -D of one of them is a compile
+// error instead of a product library that is slow, spills or computes garbage.  Every kernel source and engine.cpp include
+// this header before any other of the library's, so the names are tested before a header sets a default.
+#if ! defined(LLSM_KBENCH_EXPERIMENTS) && ( \
+    defined(KAL_ABL) || defined(NF_ABL) || defined(KAL_BREAK) || defined(IIR_FAKE_L2) || defined(IIR_GEN_EXPERIMENT) || \
+    defined(RT2_TIMING) || defined(HT_TABLE_EXPERIMENT) || \
+    defined(HT_SEG) || defined(HT_CHUNK) || defined(HT_WPE) || defined(HE_WPE) || defined(IIR_SEG) || defined(IIR_WPE) || \
+    defined(KAL_WPE) || defined(KAL_CHUNK) || defined(EXU_Q) || defined(EXU_WPE) || defined(NF_OLA_WPE) || \
+    defined(SO4_WAVES) || defined(SO4_WPE) || defined(PBP_NT) || defined(PBP_WIDE_BELOW) || defined(PBP_WPE) || \
+    defined(SYN_UNIT_DIV) || defined(NF_UNIT_DIV))
+#error "experiment build switches need -DLLSM_KBENCH_EXPERIMENTS (tools/kbench.py --build); the product library is never built with them"
+#endif
+
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "cheby.h"                                // IIR_SEG
@@ -130,7 +145,7 @@ int launch_scatter_outputs(LaunchCtx* P, int n_utt, int max_ny, const float* y, 
   const int* y_off, const int* ny, float* const* tab);
 int launch_env_plan(LaunchCtx* P, int max_ny, int max_nfrm, int nwin_env, float thop, float fs, int2* hits, int* over);
 // cplx == NULL: k_excite_units over `units` (two int4 per unit: {u, s0, samples, ny}, {frm_off, nfrm, y_off, 0}), which
-// forms the complex amplitudes itself; otherwise the k_env_params rows feed k_excite_env / k_excite_env4
+// forms the complex amplitudes itself; otherwise the k_env_params rows feed k_excite_env
 int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int ntemplate_ext,
   const int2* hits, const float2* cplx, int nwin_env, const float* win, int nch_active,
   const int* out_off, const int* out_len, int max_len, float fs_syn, float* yexc,

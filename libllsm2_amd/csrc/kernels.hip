@@ -42,14 +42,10 @@ namespace lp = llsm_plan;
 #include "launch.h"
 // Timing experiments (tools/kbench.py --ablate IIR_FAKE_L2=1 / IIR_GEN_EXPERIMENT=1, RT2_TIMING) live OUTSIDE the product
 // sources, in tools/kbench_experiments.h, and only a build that also passes -DLLSM_KBENCH_EXPERIMENTS (kbench does) can
-// reach them: the product translation unit holds three empty hooks, and a stray -D of one of the switches is a
-// compile error instead of a library that computes garbage (IIR_FAKE_L2 does, by design).
+// reach them: the product translation unit holds empty hooks, and kernels.h refuses the switches without it.
 #if defined(LLSM_KBENCH_EXPERIMENTS)
 #include "../../tools/kbench_experiments.h"
 #else
-#if defined(IIR_FAKE_L2) || defined(IIR_GEN_EXPERIMENT) || defined(RT2_TIMING) || defined(HT_TABLE_EXPERIMENT) || defined(KAL_BREAK)
-#error "timing-experiment switches need -DLLSM_KBENCH_EXPERIMENTS (tools/kbench.py); the product library is never built with them"
-#endif
 #define RT2_T(i)
 #define IIR_EXP_JOB(job, jobs, j)
 #define IIR_EXP_GEN(fwd, square, src, gen_src, idx0, q) false
@@ -336,12 +332,6 @@ DEV float harm_block(const HarmRow& R, int KC, double turn1, int h0, int col, in
 #ifndef HT_CHUNK
 #define HT_CHUNK 2                                 // 4: 19 spilled registers at 4 wavefronts / SIMD and 2.5 % slower
 #endif
-#ifndef HT_SCHED
-#define HT_SCHED 1
-#endif
-#ifndef HT_PREFETCH
-#define HT_PREFETCH 1                              // -2.7 % (tools/kbench.py)
-#endif
 
 // The tile of one block: the first run of >= HT_MINROWS consecutive voiced frames with bit-identical F0
 // whose folded window fits the LDS provision (kcap table slots).  Wave-uniform result; lanes 0..15 each
@@ -408,12 +398,10 @@ DEV void harm_tile_steps(const HarmTileOps<C>& o, int ks, float (&wr)[NT], float
       const float ni = fmaf(wi[tt], rc[tt], -wr[tt] * rs[tt]);
       wr[tt] = nr; wi[tt] = ni;
     }
-#if HT_SCHED == 1
     // one run of MFMAs, then one run of VALU work per k-step: every MFMA <-> VALU alternation costs ~9 cycles of issue
     // on gfx950 (tools/ubench/mfma_valu: 14 MFMA + 28 VALU = 620 cycles interleaved, 545 grouped at 3 wavefronts / SIMD)
     __builtin_amdgcn_sched_group_barrier(0x008, 2 * NT, 0);
     __builtin_amdgcn_sched_group_barrier(0x002, 4 * NT, 0);
-#endif
   }
 }
 
@@ -460,9 +448,9 @@ DEV void harm_tile_block(buf_t rng, int cidx, const float* __restrict__ wp, cons
     }
     int ks = ks0;
     const int kmax = q + 4 * (nks - 1);
-#if HT_PREFETCH
     // the operands of chunk c + 1 are requested before the MFMAs of chunk c: their latency hides under the wavefront's
-    // own matrix work instead of waiting for the other wavefronts of the SIMD to cover it
+    // own matrix work instead of waiting for the other wavefronts of the SIMD to cover it (2.7 % faster than loading each
+    // chunk just before its MFMAs)
     HarmTileOps<HT_CHUNK> nxt;
     harm_tile_load<HT_CHUNK>(nxt, rng, cidx, wp, wm, q + 4 * ks, kmax);
     for(; ks + HT_CHUNK <= ks1; ks += HT_CHUNK) {
@@ -470,13 +458,6 @@ DEV void harm_tile_block(buf_t rng, int cidx, const float* __restrict__ wp, cons
       harm_tile_load<HT_CHUNK>(nxt, rng, cidx, wp, wm, q + 4 * (ks + HT_CHUNK), kmax);
       harm_tile_steps<NT, HT_CHUNK>(cur, ks, wr, wi, rc, rs, are, aim);
     }
-#else
-    for(; ks + HT_CHUNK <= ks1; ks += HT_CHUNK) {
-      HarmTileOps<HT_CHUNK> cur;
-      harm_tile_load<HT_CHUNK>(cur, rng, cidx, wp, wm, q + 4 * ks, kmax);
-      harm_tile_steps<NT, HT_CHUNK>(cur, ks, wr, wi, rc, rs, are, aim);
-    }
-#endif
     for(; ks < ks1; ks ++) {
       HarmTileOps<1> cur;
       harm_tile_load<1>(cur, rng, cidx, wp, wm, q + 4 * ks, kmax);
@@ -706,21 +687,6 @@ __global__ __launch_bounds__(4 * WAVE, HS_WPE) void k_harm_speech_rest(
 // 64 lanes split the WINDOW (only <= 8 harmonics are wanted) and the
 // per-harmonic sums are reduced with the shuffle butterfly.
 // =====================================================================
-#ifndef HE_DC2
-#define HE_DC2 1                                    // the short-time mean adds whole pairs (see the loop)
-#endif
-#ifndef HE_MID2
-#define HE_MID2 1                                   // the centre sample of an odd window is zeroed at its mirror load, not selected per channel
-#endif
-#if HE_DC2 && ! HE_MID2
-#error "HE_DC2 needs HE_MID2 (the pair sum must hold the centre sample once)"
-#endif
-#ifndef HE_CHEB
-#define HE_CHEB 0                                   // 1: harmonic phasors by the three-term recurrence c_k = 2 c_1 c_(k-1) - c_(k-2): 0.01 ms faster and, fed
-#endif                                              // with CARRIED phasors, 7e-4 rad on an envelope phase (seed 904505; rotation: 3e-5) against a bound of 1e-3: off
-#ifndef HE_CARRY
-#define HE_CARRY 1                                  // 1: phasors seeded once per frame and rotated from trip to trip (0: re-seeded every 4 pairs)
-#endif
 #ifndef HE_WPE
 #define HE_WPE 5                                   // <= 102 VGPRs: the <4, 4> form holds 99, no spills (0.577 -> 0.549 ms against 4; 3: 0.584; a budget of 85 spills 71 registers: 2.9x slower)
 #endif
@@ -806,90 +772,51 @@ __global__ __launch_bounds__(WAVE, (NCH * ME <= 16 ? HE_WPE : 1)) void k_harm_en
   // loaded once: the mirror load gets an offset outside the range (0), and its odd part meets sin(0) = 0.
   const int dcA = bdc - base, dcB = base + n - bdc - ndc;
   const int dcBoth = dc_inside ? max(dcA, dcB) : INT_MAX, dcOne = dc_inside ? min(dcA, dcB) : INT_MAX;
-#if HE_CARRY
   // window phase and phasor of pair p0 = lane from float64-reduced phases; every later pair of the lane (64 further each) by
   // rotation -- at most ceil(npair / 64) - 1 steps (a dozen at 4 periods of 100 Hz), 6e-8 each
   float wc, wsn, z1c, z1s;
   cs_turns((double)lane * inv_n1, & wc, & wsn);
   cs_turns(turn1 * 0.5 * (double)(n - 1 - 2 * lane), & z1c, & z1s);
-#endif
   for(int p0 = lane; p0 < npair; p0 += WAVE * 4) {
     float vm[4][NCH], vp[4][NCH];
 #pragma unroll
     for(int q = 0; q < 4; q ++) {
       const int pp = p0 + q * WAVE, im_ = base + pp, ip_ = base + n - 1 - pp;   // pp >= npair: not used below
-#if HE_MID2
       const int op_ = 2 * pp == n - 1 ? -1 : ip_ - rlo;
-#else
-      const int op_ = ip_ - rlo;
-#endif
 #pragma unroll
       for(int c = 0; c < NCH; c ++) {
         vm[q][c] = ld_range(rng[c], im_ - rlo);
         vp[q][c] = ld_range(rng[c], op_);
       }
     }
-#if ! HE_CARRY
-    float wc, wsn, z1c, z1s;
-    cs_turns((double)p0 * inv_n1, & wc, & wsn);
-    cs_turns(turn1 * 0.5 * (double)(n - 1 - 2 * p0), & z1c, & z1s);   // th tau' of the pair, turns
-#endif
 #pragma unroll
     for(int q = 0; q < 4; q ++) {
       const int pp = p0 + q * WAVE;
       if(pp < npair) {
         const bool mid = 2 * pp == n - 1;            // odd n: the centre sample pairs with itself
         float ev[NCH], on[NCH];
-#if HE_DC2
 #pragma unroll
         for(int c = 0; c < NCH; c ++) ev[c] = vp[q][c] + vm[q][c];
-        {
+        {                                            // the short-time mean adds whole pairs (see above)
           const float fb = pp >= dcBoth ? 1.0f : 0.0f;
 #pragma unroll
           for(int c = 0; c < NCH; c ++) dacc[c] = fmaf(ev[c], fb, dacc[c]);
           if(pp >= dcOne && pp < dcBoth) {
 #pragma unroll
-            for(int c = 0; c < NCH; c ++) dacc[c] += pp >= dcA ? vm[q][c] : (HE_MID2 || ! mid ? vp[q][c] : 0.0f);
+            for(int c = 0; c < NCH; c ++) dacc[c] += pp >= dcA ? vm[q][c] : vp[q][c];
           }
         }
-#else
-        if(dc_inside) {                              // short-time mean rides along (see above)
-          const int im_ = base + pp, ip_ = base + n - 1 - pp;
-          const bool dm = im_ >= bdc && im_ < bdc + ndc, dp = ! mid && ip_ >= bdc && ip_ < bdc + ndc;
-#pragma unroll
-          for(int c = 0; c < NCH; c ++) dacc[c] += (dm ? vm[q][c] : 0.0f) + (dp ? vp[q][c] : 0.0f);
-        }
-#endif
         // 0.42 - 0.5 cos a + 0.08 cos 2a with cos 2a = 2 cos^2 a - 1
         const float w = n > 1 ? fmaf(wc, fmaf(wc, 0.16f, -0.5f), 0.34f) : 1.0f;
         wsum += mid ? w : 2.0f * w;
 #pragma unroll
         for(int c = 0; c < NCH; c ++) {
-#if HE_MID2
-          ev[c] = (HE_DC2 ? ev[c] : vp[q][c] + vm[q][c]) * w;
+          ev[c] *= w;
           on[c] = (vm[q][c] - vp[q][c]) * w;         // -O (centre sample: meets sin 0 = 0 below)
-#else
-          ev[c] = mid ? vm[q][c] * w : (HE_DC2 ? ev[c] : vp[q][c] + vm[q][c]) * w;
-          on[c] = mid ? 0.0f : (vm[q][c] - vp[q][c]) * w;      // -O
-#endif
         }
-#if HE_CHEB
-        // cos, sin(k th tau'), k = 1 .. ME, by the three-term recurrence c_k = 2 c_1 c_(k-1) - c_(k-2) (likewise s_k): one
-        // fused multiply-add per value instead of a complex rotation; ME <= 8 steps from exact seeds
-        const float tc = z1c + z1c;
-        float zr = z1c, zi = z1s, zrp = 1.0f, zip = 0.0f;   // (c_k, s_k) and (c_(k-1), s_(k-1)); k = 0: (1, 0)
-#pragma unroll
-        for(int k = 0; k < ME; k ++) {
-#pragma unroll
-          for(int c = 0; c < NCH; c ++) {
-            are[c][k] = fmaf(ev[c], zr, are[c][k]);
-            aim[c][k] = fmaf(on[c], zi, aim[c][k]);
-          }
-          const float nr = fmaf(tc, zr, -zrp), ni = fmaf(tc, zi, -zip);
-          zrp = zr; zip = zi; zr = nr; zi = ni;
-        }
-#else
-        float zr = z1c, zi = z1s;                    // cos, sin(k th tau')
+        // cos, sin(k th tau') by rotation: the three-term recurrence c_k = 2 c_1 c_(k-1) - c_(k-2) is 0.01 ms faster but
+        // reaches 7e-4 rad on an envelope phase (seed 904505; rotation: 3e-5) against a bound of 1e-3
+        float zr = z1c, zi = z1s;
 #pragma unroll
         for(int k = 0; k < ME; k ++) {
 #pragma unroll
@@ -900,7 +827,6 @@ __global__ __launch_bounds__(WAVE, (NCH * ME <= 16 ? HE_WPE : 1)) void k_harm_en
           const float nr = zr * z1c - zi * z1s, ni = zr * z1s + zi * z1c;
           zr = nr; zi = ni;
         }
-#endif
       }
       float t1 = wc * wstc - wsn * wsts, t2 = wc * wsts + wsn * wstc; wc = t1; wsn = t2;
       t1 = z1c * zstc + z1s * zsts; t2 = z1s * zstc - z1c * zsts; z1c = t1; z1s = t2;   // tau' -= 64
@@ -1296,9 +1222,6 @@ DEV void unpack_pair(const float2* Z, int M, int logM, int k, float2* A, float2*
 // layer0.c:341), forward FFT of N/fold.  Persistent: each wavefront walks
 // frame pairs.  LDS: N float2 + N/2 float2 twiddles.
 // =====================================================================
-#ifndef SPGM_EDGE_F64
-#define SPGM_EDGE_F64 1                             // 0: bins 0 and N/2 of the spectrogram always as the float32 transform returns them (rounds 1 - 5)
-#endif
 // The exact DC and Nyquist sums of one Hann-windowed frame (window of ws samples centred on sample c of xs[0, nxe)), by one
 // wavefront: float64 window, products and sums.  Of k_spgm_env_wf only the FIX instantiation contains it: inside the
 // ordinary kernel -- inlined behind a rare branch, or as a real call -- its register needs made the compiler spill a
@@ -1404,7 +1327,7 @@ __global__ __launch_bounds__(WAVE) void k_spgm_env(
       float2 A, B; unpack_pair(X, N, logN, k, & A, & B);
       float La = __logf(__builtin_amdgcn_sqrtf(A.x * A.x + A.y * A.y) * normalizer[0] + 1e-10f);
       float Lb = __logf(__builtin_amdgcn_sqrtf(B.x * B.x + B.y * B.y) * normalizer[1] + 1e-10f);
-      if((k == 0 || k == N / 2) && SPGM_EDGE_F64) {
+      if(k == 0 || k == N / 2) {
         const int s = k == 0 ? 0 : 1;
         if(gg[0] < nframes && wsz[0] > 1) La = edge_log[0][s];
         if(gg[1] < nframes && wsz[1] > 1) Lb = edge_log[1][s];
@@ -1528,12 +1451,6 @@ __global__ __launch_bounds__(WAVE, 2) void k_spgm_env_wf(
     const int p = FIX ? fix_list[pw].x : pw;
     const int fixmask = FIX ? fix_list[pw].y : 0;
     int gg[2]; pair_of(pairs, p, nframes, gg[0], gg[1]);
-#ifdef SPGM_SINGLE_EXPERIMENT                         // (experiment: every frame transformed beside an EMPTY partner, twice the work)
-    const int g_both[2] = {gg[0], gg[1]};
-    for(int rep = 0; rep < 2; rep ++) {
-    gg[0] = g_both[rep]; gg[1] = nframes;
-    if(gg[0] >= nframes) continue;
-#endif
     float f0n[2], normalizer[2];
     const float* xsp[2]; int nxu[2], cc[2], wsz[2];
 #pragma unroll
@@ -1641,14 +1558,12 @@ __global__ __launch_bounds__(WAVE, 2) void k_spgm_env_wf(
         for(int m = 0; m < P; m ++) v[m] = stage[lane + WAVE * m];
         __syncthreads();
       }
-#if SPGM_EDGE_F64
       if(FIX && ((fixmask >> e) & 1)) {
         double sd, sn;
         spgm_exact_edges(xs, nxe, c, ws, lane, & sd, & sn);
         edge_log[e][0] = __logf((float)fabs(sd) * normalizer[e] + 1e-10f);
         edge_log[e][1] = __logf((float)fabs(sn) * normalizer[e] + 1e-10f);
       }
-#endif
     }
     wave_fft<LOGN>(xr, xi, twN, lds, lane);
     {                                                // log magnitude spectra of both frames
@@ -1660,15 +1575,9 @@ __global__ __launch_bounds__(WAVE, 2) void k_spgm_env_wf(
       for(int m = 0; m <= H; m ++) {                 // bins k <= N/2 (m = H: lane 0 only matters)
         const float ar = 0.5f * (xr[m] + mr[m]), ai = 0.5f * (xi[m] - mi[m]);
         const float br = 0.5f * (xi[m] + mi[m]), bi = -0.5f * (xr[m] - mr[m]);
-#ifdef SPGM_PRECISE_LOG                               // (experiment: correctly rounded sqrt / log instead of the hardware approximations)
-        xr[m] = logf(sqrtf(ar * ar + ai * ai) * normalizer[0] + 1e-10f);
-        xi[m] = logf(sqrtf(br * br + bi * bi) * normalizer[1] + 1e-10f);
-#else
         xr[m] = __logf(__builtin_amdgcn_sqrtf(ar * ar + ai * ai) * normalizer[0] + 1e-10f);
         xi[m] = __logf(__builtin_amdgcn_sqrtf(br * br + bi * bi) * normalizer[1] + 1e-10f);
-#endif
       }
-#if SPGM_EDGE_F64
       if constexpr (! FIX) {
         // log magnitudes: bins 0 .. 63 sit in register 0 of the 64 lanes, bins 0 and N/2 in registers 0 and H of lane 0.
         // The yardstick is the bin of the frame's F0 (its fundamental: a strong bin of a voiced frame; 200 Hz for an
@@ -1687,7 +1596,6 @@ __global__ __launch_bounds__(WAVE, 2) void k_spgm_env_wf(
         if(fixmask & 1) { xr[0] = edge_log[0][0]; xr[H] = edge_log[0][1]; }
         if(fixmask & 2) { xi[0] = edge_log[1][0]; xi[H] = edge_log[1][1]; }
       }
-#endif
       wave_reflect<P>(xr, xr, lane);                 // log spectra are even: L[N - k] = L[k]
       wave_reflect<P>(xi, xi, lane);
     }
@@ -1750,9 +1658,6 @@ __global__ __launch_bounds__(WAVE, 2) void k_spgm_env_wf(
     }
     if(! FIX && edge_mask && fix_list && lane == 0)
       fix_list[atomicAdd(fix_count, 1)] = make_int2(p, edge_mask);   // (at most one entry per pair: never beyond npair)
-#ifdef SPGM_SINGLE_EXPERIMENT
-    }
-#endif
   }
 }
 
@@ -2042,27 +1947,11 @@ __global__ __launch_bounds__(HPP_BIG_NT) void k_harm_pp_big(
 // =====================================================================
 // The two chains of an output point (bins k0 and k1) run as the two halves of float2 values:
 // explicit vector arithmetic gives v_pk_* instructions (the library is built without SLP
-// vectorisation, which pays everywhere except here), component-wise the same IEEE operations.
-#ifdef KAL_F64                                        // (experiment: the recursions in float64; rows and checkpoints stay float32)
-typedef double kal1;
-typedef double kal2 __attribute__((ext_vector_type(2)));
-#else
+// vectorisation, which pays everywhere except here), component-wise the same IEEE operations.  One bin chain per lane
+// instead (twice the wavefronts, half the registers each, the same instructions per wavefront) measured 0.54 ms against 0.46.
 typedef float kal1;
-typedef float kal2 __attribute__((ext_vector_type(2)));
-#endif
-#ifndef KAL_SPLIT
-#define KAL_SPLIT 0                                  // 1: one BIN chain per lane (lanes 2 j and 2 j + 1 carry the two bins point j interpolates between);
-#endif                                               // 0: both in one lane as packed pairs (rounds 1 - 5)
-// The split form was an experiment: the launch has n_utt x npsd points (132 k at 1 024 utterances = two wavefronts per SIMD of
-// 200 x 2 dependent steps each) and keeps the VALU a fifth busy; one bin per lane doubles the wavefronts (four per SIMD,
-// half the registers each) at the same instruction count per wavefront.  Measured 0.54 ms against 0.46: a switch only.
-#if KAL_SPLIT
-typedef kal1 kalv;
-#define KALV(x) ((kal1)(x))
-#else
-typedef kal2 kalv;
-#define KALV(x) ((kal2){(kal1)(x), (kal1)(x)})
-#endif
+typedef float kalv __attribute__((ext_vector_type(2)));
+#define KALV(x) ((kalv){(kal1)(x), (kal1)(x)})
 struct KalState { kalv xk, p, Q; };
 // bins are neighbours (k1 = k0 + 1, or k1 = k0 at the last point): one 8-byte load at p[k1 - 1]
 struct __attribute__((packed, aligned(4))) KalPair { float a, b; };
@@ -2073,40 +1962,22 @@ DEV kalv kal_ld(const float* __restrict__ p, size_t at, bool same) {
 #if KAL_ABL & 4
   return KALV((float)(at & 1023) * 1e-3f);
 #endif
-#if KAL_SPLIT
-  (void)same;
-  return (kal1)p[at];                                // (`at` already points at this lane's bin)
-#else
   // (a, b) as loaded: at the last point (k1 == k0) the chain in x runs on bin k1 - 1 and is not looked at -- the outputs take
   // y there.  Round 5 selected (b, b) HERE: the select sat behind an s_waitcnt right after each load (four loads in
   // flight, every "prefetched" row waited for at once).
   (void)same;
   const KalPair v = *(const KalPair*)(p + at);
-  return (kal2){(kal1)v.a, (kal1)v.b};
-#endif
+  return (kalv){(kal1)v.a, (kal1)v.b};
 }
-#ifndef KAL_FAST_OUT
-#define KAL_FAST_OUT 1                               // the output point's exp / log10 on the hardware's exp2 / log2
-#endif
-#ifndef KAL_RCP
-#define KAL_RCP 1                                    // gains as numerator x reciprocal (hardware 1-ulp reciprocal + one Newton step) instead of an IEEE division
-#endif
-// num / den for den > 0.  An IEEE float32 division is 11 dependent instructions (~60 cycles, tools/ubench/dep_latency.hip)
-// on the one chain that bounds this kernel (the covariance recursion: every step waits for the previous gain); the
-// reciprocal form is 5 (~40).  Both are good to an ulp; the filter contracts such errors.
+// num / den for den > 0 as numerator x reciprocal (hardware 1-ulp reciprocal + one Newton step).  An IEEE float32
+// division is 11 dependent instructions (~60 cycles, tools/ubench/dep_latency.hip) on the one chain that bounds this
+// kernel (the covariance recursion: every step waits for the previous gain); the reciprocal form is 5 (~40).  Both are
+// good to an ulp; the filter contracts such errors.
 DEV kalv kal_ratio(kalv num, kalv den) {
-#if KAL_RCP && ! defined(KAL_F64)
-#if KAL_SPLIT
-  kalv r = __builtin_amdgcn_rcpf(den);
-#else
   kalv r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-#endif
   const kalv er = (kal1)1.0f - den * r;
   r = r + r * er;
   return num * r;
-#else
-  return num / den;
-#endif
 }
 // process variance = the 3-frame moving variance of the envelope, m2 / 3 - m1^2 / 9 (layer0.c:366-375), evaluated as the
 // mean squared deviation from the 3-frame mean: in float32 the reference's difference of two numbers of the size of the
@@ -2144,7 +2015,7 @@ DEV void kal_step(KalState& s, int i, kalv e_prev, kalv e_cur, kalv e_next, kalv
 }
 
 #ifndef KAL_WPE
-#define KAL_WPE (KAL_SPLIT ? 4 : 2)                               // wavefronts per SIMD the register budget is cut for: the flat numbering leaves two wavefronts per SIMD in all at 1 024 utterances (3: 168 registers, spills with per-lane frame counts)
+#define KAL_WPE 2                                    // wavefronts per SIMD the register budget is cut for: the flat numbering leaves two wavefronts per SIMD in all at 1 024 utterances (3: 168 registers, spills with per-lane frame counts)
 #endif
 __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
   const float* __restrict__ env, const float* __restrict__ psd_log, float* __restrict__ ck,
@@ -2153,13 +2024,7 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
   // One thread per (utterance, output point), numbered flat: with a grid of (points / 128, utterances) the 129 points of
   // the default grid made a second workgroup per utterance with ONE live lane -- half of the launch's wavefronts, each
   // as long as a full one.  A wavefront may straddle two utterances: frame counts and offsets are per lane.
-#if KAL_SPLIT
-  const int flat2 = blockIdx.x * 128 + threadIdx.x;  // lanes 2 j and 2 j + 1: the bins k1 - 1 and k1 of point j
-  const int flat = flat2 >> 1, cb = flat2 & 1;
-#else
   const int flat = blockIdx.x * 128 + threadIdx.x;
-  const int cb = 0;
-#endif
   if(flat >= n_utt * npsd) return;
   const int u = flat / npsd, j = flat - u * npsd;
   const int n = nfrm[u];
@@ -2175,13 +2040,13 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
   else { if(k0 < 0) k0 = 0; k1 = k0 + 1; r = pos - (float)k0; }
   const size_t ns = (size_t)nspec, fo = (size_t)frm_off[u];
   const bool same = k1 == k0;
-  const size_t op = fo * ns + (size_t)max(k1 - 1, 0) + (size_t)cb;   // pair base: bins (k1 - 1, k1) (split: this lane's bin of the two)
+  const size_t op = fo * ns + (size_t)max(k1 - 1, 0);   // pair base: bins (k1 - 1, k1)
   constexpr int KC = KAL_CHUNK;                        // frames per chunk (checkpoint spacing, rows per request)
   // checkpoints: chunk c of utterance u at row (frm_off[u] / KC + u + c) of 4 npsd floats
   // (xa, pa, xb, pb per output point); rows of different utterances cannot overlap because
   // floor((fo + n) / 8) - floor(fo / 8) + 1 >= ceil(n / 8)
   const size_t cstride = (size_t)4 * npsd;
-  float* ckp = ck + (fo / KC + (size_t)u) * cstride + (size_t)4 * j + (size_t)2 * cb;
+  float* ckp = ck + (fo / KC + (size_t)u) * cstride + (size_t)4 * j;
   KalState S = {KALV(0), KALV(0), KALV(0)};
   {
     kalv e_prev = kal_ld(env, op, same), e_cur = e_prev;           // clamped at i = -1
@@ -2194,7 +2059,7 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
     // waited for at its bottom.  MEASURED (round 6, profiles/r06_*kalman*): a single utterance (llsm_analyze, 1 154
     // frames) 0.53 -> 0.49 ms; the batch of 1 024 did not move (0.45 ms) -- nor did it with the loads' select removed,
     // the per-frame branches gone (55 -> 27 dependent instructions per frame), reciprocal gains, or twice the wavefronts
-    // (one bin per lane, KAL_SPLIT: slower).  Its timing ablations say 0.20 ms arithmetic + 0.17 loads + 0.09 stores.
+    // (one bin per lane: slower).  Its timing ablations say 0.20 ms arithmetic + 0.17 loads + 0.09 stores.
     // What bounds it is HBM: the planes are 513 bins wide (420 MB each), read once forward and 1.1 times backward, plus
     // 420 MB of outputs = 2.6 GB per launch at 1 024 utterances = 5.6 TB/s in 0.46 ms (LAB.md round 6, item 5).
     struct Rows { kalv e[KC], z[KC]; };
@@ -2233,11 +2098,7 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
         }
       }
       float* c = ckp + (size_t)(i0 / KC) * cstride;  // state after frame min(i0 + KC - 1, n - 1)
-#if KAL_SPLIT
-      *(float2*)c = make_float2((float)S.xk, (float)S.p);
-#else
       *(float4*)c = make_float4((float)S.xk.x, (float)S.p.x, (float)S.xk.y, (float)S.p.y);
-#endif
     };
     Rows r0, r1, r2;
     load_rows(r0, 0); load_rows(r1, KC);
@@ -2248,7 +2109,7 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
     }
   }
 #if KAL_ABL & 1
-  if((float)(S.xk + S.p)[0 * KAL_SPLIT] == 1.2345f) psd[flat] = 0.0f;
+  if((float)(S.xk + S.p)[0] == 1.2345f) psd[flat] = 0.0f;
   return;
 #endif
   kalv sm = S.xk;                                    // smoothed values at i = n - 1
@@ -2267,39 +2128,24 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
       rb.z[q] = kal_ld(psd_log, op + ic, same);
     }
     rb.cpt = make_float4(0, 0, 0, 0);
-#if KAL_SPLIT
-    if(i0 > 0) { const float2 c2 = *(const float2*)(ckp + (size_t)(i0 / KC - 1) * cstride); rb.cpt = make_float4(c2.x, c2.y, 0.0f, 0.0f); }
-#else
     if(i0 > 0) rb.cpt = *(const float4*)(ckp + (size_t)(i0 / KC - 1) * cstride);
-#endif
   };
   // smoothed log-PSD (+ EULERGAMMA bias removal) and residual at the two bins, interpolated
   auto put = [&](int i, kalv smv, kalv zv) {
     const kalv m = smv + (kal1)0.57721566f, rs = zv - smv;
-#if KAL_SPLIT
-    // the even lane of a pair writes the point: its own bin (k1 - 1) and the odd lane's (k1), one cross-lane read each
-    const kal1 my = __shfl_xor(m, 1, WAVE), ry = __shfl_xor(rs, 1, WAVE);
-    if(cb) return;
-    const float a = same ? (float)my : (float)(m + (my - m) * (kal1)r);
-    const float b = same ? (float)ry : (float)(rs + (ry - rs) * (kal1)r);
-#else
     const float a = same ? (float)m.y : (float)(m.x + (m.y - m.x) * (kal1)r);
     const float b = same ? (float)rs.y : (float)(rs.x + (rs.y - rs.x) * (kal1)r);
-#endif
     const size_t g = (fo + (size_t)i) * npsd + j;
 #if KAL_ABL & 8
     if(a == 1.2345f) psd[g] = b;
 #elif KAL_ABL & 2
     psdres[g] = b; psd[g] = a;
-#elif KAL_FAST_OUT
+#else
     // hardware exp2 / log2 (1 ulp) and a multiplication instead of the library's correctly rounded exp / log10 and an IEEE
     // division: 82 -> 30 instructions per output point in a kernel whose wavefronts run alone on their SIMDs; the level
     // moves by < 1e-5 dB (|a| log2(e) rounds at 2e-6 relative)
     psdres[g] = b * (10.0f / 2.3025851f);
     psd[g] = (10.0f * 0.30102999566f) * __builtin_amdgcn_logf(__builtin_amdgcn_exp2f(a * 1.44269504089f) * (44100.0f / fs) + 1e-12f);
-#else
-    psdres[g] = b / 2.3025851f * 10.0f;
-    psd[g] = 10.0f * log10f(expf(a) * 44100.0f / fs + 1e-12f);
 #endif
     if(j == 0) has_psdres[fo + i] = 1;
   };
@@ -2307,11 +2153,7 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
   // pass), chunk i0 recomputed from its checkpoint and smoothed from `cur`
   auto chunk_b = [&](int i0, const RowsB& cur, RowsB& ahead) {
     if(i0 >= 2 * KC) fetch(i0 - 2 * KC, ahead);
-#if KAL_SPLIT
-    if(i0 > 0) { S.xk = (kal1)cur.cpt.x; S.p = (kal1)cur.cpt.y; }
-#else
     if(i0 > 0) { S.xk = (kalv){cur.cpt.x, cur.cpt.z}; S.p = (kalv){cur.cpt.y, cur.cpt.w}; }
-#endif
     kalv xf[KC], pf[KC], qf[KC];
     if(__builtin_amdgcn_ballot_w64(i0 + KC > n) == 0) {
       // a full chunk on every live lane: the filter steps again (variances up front, as above), then the smoother's gains
@@ -2371,9 +2213,6 @@ __global__ __launch_bounds__(128, KAL_WPE) void k_kalman(
 // (utterance u, channel c) has n_ext(u) = min(20000, ny_u) + 128 samples; the
 // reference's own wrap-around of the extension (dsputils.c:358-359) is kept.
 // =====================================================================
-#ifndef WHITE_FAST
-#define WHITE_FAST 1
-#endif
 __global__ __launch_bounds__(256) void k_white(
   float* __restrict__ white, int ntemplate_ext, const int* __restrict__ out_len,
   int nch, unsigned long long seed) {
@@ -2386,14 +2225,10 @@ __global__ __launch_bounds__(256) void k_white(
   float u1, u2;
   lp::rng_uniforms((seed + (unsigned long long)u) * 16ULL + (unsigned long long)c,
     (unsigned long long)src, & u1, & u2);
-#if WHITE_FAST
   // Box-Muller on the hardware's log2 / sqrt / cos-of-turns (1 ulp; |error| of a sample ~ 1e-6 of sigma): the correctly
   // rounded libm forms were 2/3 of this kernel's ~60 instructions per sample (it is VALU-bound, not bound by its 0.33 GB)
   white[((size_t)u * nch + c) * ntemplate_ext + i] =
     __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1)) * __builtin_amdgcn_cosf(u2);   // -2 ln u1 = -2 ln 2 log2 u1
-#else
-  white[((size_t)u * nch + c) * ntemplate_ext + i] = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-#endif
 }
 
 // =====================================================================
@@ -2500,9 +2335,6 @@ __global__ __launch_bounds__(256) void k_env_params(
 // not on the utterance), at most EXC_HITS of them in ascending (i, j) order -- the
 // accumulation order of the reference's frame loop.
 #define EXC_HITS 3
-#ifndef EXC_FAST
-#define EXC_FAST 1                                  // hardware sin / cos / sqrt in k_excite_env (0: float64-reduced phases, libm sqrt: rounds 1 - 5)
-#endif
 #define EXC_SLOTS 8                                 // envelope frames staged per block of 256 samples
 template <int NCH, int ME>
 __global__ __launch_bounds__(256) void k_excite_env(
@@ -2557,14 +2389,10 @@ __global__ __launch_bounds__(256) void k_excite_env(
     if(sl >= 0 && sl < EXC_SLOTS) {
       const float tn = s_turn[sl];
       float z1r = 1.0f, z1i = 0.0f;
-#if EXC_FAST
       // |j - half| <= nwin / 2 and tn <= 1/2: the float32 product is good to 6e-8 of its (<= ~100) turns and the hardware
       // sine / cosine take turns directly (|error| ~ 1e-6 of an envelope value whose square root modulates NOISE; the
       // float64 phase reduction + polynomial of cs_turns was a tenth of this kernel's instructions)
       if(tn > 0) { const float ph = tn * (float)(j - half); z1r = __builtin_amdgcn_cosf(ph); z1i = __builtin_amdgcn_sinf(ph); }
-#else
-      if(tn > 0) cs_turns((double)tn * (double)(j - half), & z1r, & z1i);
-#endif
       float zr[ME], zi[ME];                          // e^{j k th}, k = 1 .. ME
       zr[0] = z1r; zi[0] = z1i;
 #pragma unroll
@@ -2613,11 +2441,7 @@ __global__ __launch_bounds__(256) void k_excite_env(
         v += tpl[b] * r;
         v *= xf;
       }
-#if EXC_FAST
       v *= __builtin_amdgcn_sqrtf(e[c]);               // e >= 1e-8 w > 0 or exactly 0: the hardware root (1 ulp) has no special case to miss
-#else
-      v *= sqrtf(e[c]);
-#endif
       acc += v;
     }
   }
@@ -2765,13 +2589,9 @@ __global__ __launch_bounds__(256, ME > 4 ? EXU_WPE - 1 : EXU_WPE) void k_excite_
       const float w = s_win[j];
       const float tn = s_turn[sl];
       float z1r = 1.0f, z1i = 0.0f;
-#if EXC_FAST
       const float ph = tn * (float)(j - half);
       const float cr = __builtin_amdgcn_cosf(ph), si = __builtin_amdgcn_sinf(ph);
       if(tn > 0) { z1r = cr; z1i = si; }
-#else
-      if(tn > 0) cs_turns((double)tn * (double)(j - half), & z1r, & z1i);
-#endif
       float zr[ME], zi[ME];                          // e^{j k th}, k = 1 .. ME
       zr[0] = z1r; zi[0] = z1i;
 #pragma unroll
@@ -2814,11 +2634,7 @@ __global__ __launch_bounds__(256, ME > 4 ? EXU_WPE - 1 : EXU_WPE) void k_excite_
             v += colored[((size_t)u * nch + c) * ntemplate_ext + b] * r;
             v *= xf;
           }
-#if EXC_FAST
           v *= __builtin_amdgcn_sqrtf(e[c]);
-#else
-          v *= sqrtf(e[c]);
-#endif
           acc += v;
         }
       }
@@ -2826,188 +2642,6 @@ __global__ __launch_bounds__(256, ME > 4 ? EXU_WPE - 1 : EXU_WPE) void k_excite_
     }
   }
 }
-
-// S3 + S3b, second form (round 5): the same sums, arranged by TEMPLATE position.  k_excite_env above walks the output
-// samples, so every template sample is fetched once per tile of the stretched noise (2.23 tiles at 1 s: 925 MB of
-// fetches for 330 MB of templates, profiles/r04_zz_traffic.json) and every sample pays its own index division, float64
-// phase reductions and 16 complex amplitudes from LDS per frame it lies under.  Here a thread owns FOUR consecutive
-// residues rho .. rho + 3 of the tiling period T = ntemplate - 128 (T and the 128-sample cross-fade are multiples of
-// four) and walks the tiles p = rho + t T: the templates are loaded once (16-byte loads) and stay in registers; the four
-// samples lie under the same frames, so the frame's amplitudes are read from LDS once per four samples, the phasor of
-// the first sample is seeded from a float64-reduced phase and the next three are one rotation by e^{j 2 pi f0 / fs}
-// each; the output goes out as one 16-byte store.  stretch_index's closed form becomes the tile loop itself.
-// Same (frame, offset) table and the same accumulation order per sample as above; the results differ from it by the
-// float32 rounding of the three rotations (~1e-7 of an envelope value).
-#ifndef EXC4_WPE
-#define EXC4_WPE 4                                  // wavefronts per SIMD the register budget is cut for
-#endif
-#define EXC4_SLOTS 16                               // envelope frames staged per tile of 1024 samples (hop >= 79 samples; shorter hops: HBM path)
-template <int NCH, int ME>
-__global__ __launch_bounds__(256, EXC4_WPE) void k_excite_env4(
-  const float* __restrict__ colored, int ntemplate_ext, const int2* __restrict__ hits,
-  const float2* __restrict__ cplx, const float* __restrict__ edc, const float* __restrict__ f0,
-  int nwin_env, const float* __restrict__ win, int nch, int me, int nch_active,
-  const int* __restrict__ frm_off, const int* __restrict__ nfrm,
-  const int* __restrict__ out_off, const int* __restrict__ out_len, float thop, float fs,
-  float* __restrict__ yexc) {
-  __shared__ __attribute__((aligned(16))) float2 s_cp[EXC4_SLOTS][NCH * ME];
-  __shared__ float s_off[EXC4_SLOTS][NCH];
-  __shared__ float s_turn[EXC4_SLOTS];              // f0 / fs, <= 0 when unvoiced
-  __shared__ float2 s_w[EXC4_SLOTS];                // e^{j 2 pi f0 / fs}
-  const int u = blockIdx.y;
-  const int ny = out_len[u];
-  const int nt = min(20000, ny);
-  const bool tiled = ny > nt;
-  const int T = nt - 128;                           // tiling period (plan.h stretch_index)
-  const int R = tiled ? T : ny;                     // residues
-  const int r0 = blockIdx.x * 1024;
-  if(r0 >= R) return;
-  const int rho = r0 + 4 * threadIdx.x;
-  const int nf = nfrm[u], fo = frm_off[u];
-  const float hop = lp::fmul(thop, fs);
-  const int half = nwin_env / 2;
-  const int n_ext = nt + 128;                       // samples of a template row (k_white)
-  // templates of the four residues, every active channel (and, inside the cross-fade, of T + rho ..)
-  float tv[NCH][4];
-#pragma unroll
-  for(int c = 0; c < NCH; c ++) {
-#pragma unroll
-    for(int q = 0; q < 4; q ++) tv[c][q] = 0.0f;
-    if(c < nch_active) {
-      const float* tpl = colored + ((size_t)u * nch + c) * ntemplate_ext;
-      if(rho + 3 < n_ext) { const f4u v = *(const f4u*)(tpl + rho); tv[c][0] = v.x; tv[c][1] = v.y; tv[c][2] = v.z; tv[c][3] = v.w; }
-      else {
-#pragma unroll
-        for(int q = 0; q < 4; q ++) if(rho + q < n_ext) tv[c][q] = tpl[rho + q];
-      }
-    }
-  }
-  const int ntile = tiled ? (ny - r0 + T - 1) / T : 1;   // tiles t with r0 + t T < ny (the same for the whole block)
-  for(int t = 0; t < ntile; t ++) {
-    const int b0 = r0 + t * T;                      // first output sample of the block in this tile
-    const int imin = max(0, (int)((float)b0 / hop) - 1);
-    __syncthreads();                                // (the previous tile's readers are done)
-    for(int k2 = threadIdx.x; k2 < EXC4_SLOTS * NCH * ME; k2 += 256) {
-      const int sl = k2 / (NCH * ME), r = k2 % (NCH * ME), c = r / ME, k = r % ME;
-      const int i = imin + sl;
-      float2 v = make_float2(0.0f, 0.0f);
-      if(i < nf && c < nch && k < me) v = cplx[((size_t)(fo + i) * nch + c) * me + k];
-      s_cp[sl][r] = v;
-    }
-    if(threadIdx.x < EXC4_SLOTS * NCH) {
-      const int sl = threadIdx.x / NCH, c = threadIdx.x % NCH, i = imin + sl;
-      s_off[sl][c] = (i < nf && c < nch) ? edc[(size_t)(fo + i) * nch + c] : 0.0f;
-    }
-    if(threadIdx.x < EXC4_SLOTS) {
-      const int i = imin + threadIdx.x;
-      const float tn = i < nf ? f0[fo + i] / fs : 0.0f;
-      s_turn[threadIdx.x] = tn;
-      float wr = 1.0f, wi = 0.0f;
-      if(tn > 0) cs_turns((double)tn, & wr, & wi);
-      s_w[threadIdx.x] = make_float2(wr, wi);
-    }
-    __syncthreads();
-    const int p0 = rho + t * T;
-    if(rho >= R || p0 >= ny) continue;
-    float e[4][NCH];
-#pragma unroll
-    for(int q = 0; q < 4; q ++)
-#pragma unroll
-      for(int c = 0; c < NCH; c ++) e[q][c] = 0.0f;
-#pragma unroll 1
-    for(int hh = 0; hh < EXC_HITS; hh ++) {                // (not unrolled: one set of amplitude registers, 154 -> VGPRs of one pass)
-      int fi = -2, prevj = 0;
-      float tn = 0, wr = 1.0f, wi = 0.0f, z1r = 1.0f, z1i = 0.0f;
-#pragma unroll
-      for(int q = 0; q < 4; q ++) {
-        if(rho + q >= R || p0 + q >= ny) continue;
-        const int2 hit = hits[(size_t)(p0 + q) * EXC_HITS + hh];
-        if(hit.x < 0 || hit.x >= nf) continue;
-        const int sl = hit.x - imin, j = hit.y;
-        const float w = win[j];
-        if(sl >= 0 && sl < EXC4_SLOTS) {
-          const bool seed = hit.x != fi;
-          if(seed) { fi = hit.x; tn = s_turn[sl]; const float2 wv = s_w[sl]; wr = wv.x; wi = wv.y; }
-          if(seed || j != prevj + 1) {
-            z1r = 1.0f; z1i = 0.0f;
-            if(tn > 0) cs_turns((double)tn * (double)(j - half), & z1r, & z1i);
-          } else { const float t1 = z1r * wr - z1i * wi, t2 = z1r * wi + z1i * wr; z1r = t1; z1i = t2; }
-          prevj = j;
-          float zr[ME], zi[ME];                      // e^{j k th}, k = 1 .. ME
-          zr[0] = z1r; zi[0] = z1i;
-          // explicit fused multiply-adds (the file is compiled with contraction off: a complex multiply-add written
-          // with * and + is four instructions per term, and the 16 terms of a frame are most of this kernel)
-#pragma unroll
-          for(int k = 1; k < ME; k ++) {
-            zr[k] = fmaf(zr[k - 1], z1r, -(zi[k - 1] * z1i)); zi[k] = fmaf(zr[k - 1], z1i, zi[k - 1] * z1r);
-          }
-#pragma unroll
-          for(int c = 0; c < NCH; c ++) {
-            float y = s_off[sl][c];
-#pragma unroll
-            for(int k = 0; k < ME; k += 2) {         // amplitudes are zero beyond nhar_e; two per 16-byte LDS broadcast
-              const float4 av = *(const float4*)& s_cp[sl][c * ME + k];
-              y = fmaf(av.x, zr[k], y); y = fmaf(-av.y, zi[k], y);
-              y = fmaf(av.z, zr[k + 1], y); y = fmaf(-av.w, zi[k + 1], y);
-            }
-            e[q][c] = fmaf(fmaxf(y, 1e-8f), w, e[q][c]);
-          }
-        } else {
-          // hop shorter than 1024 / (EXC4_SLOTS - 3) samples: frame not staged, read it from HBM
-          const int g = fo + hit.x;
-          const float f = f0[g];
-          float y1r = 1.0f, y1i = 0.0f;
-          if(f > 0) cs_turns((double)(f / fs) * (double)(j - half), & y1r, & y1i);
-          for(int c = 0; c < nch; c ++) {
-            float y = 0.0f, zr = y1r, zi = y1i;
-            for(int k = 0; k < me; k ++) {
-              const float2 av = cplx[((size_t)g * nch + c) * me + k];
-              y += av.x * zr - av.y * zi;
-              const float nr = zr * y1r - zi * y1i, ni = zr * y1i + zi * y1r;
-              zr = nr; zi = ni;
-            }
-            const float val = fmaxf(y + edc[(size_t)g * nch + c], 1e-8f) * w;
-#pragma unroll
-            for(int cc = 0; cc < NCH; cc ++) if(cc == c) e[q][cc] += val;
-          }
-        }
-      }
-    }
-    // template sample of output p0 + q (plan.h stretch_index with p = rho + q + t T): the residue's own sample, or -- in
-    // the first 128 residues of a later tile -- the cross-fade of the template's tail into its head
-    const bool fade_zone = t > 0 && rho < 128;
-    const bool applied = fade_zone && (t == 1 ? true : ny >= nt + (t - 1) * T);
-    float acc[4];
-#pragma unroll
-    for(int q = 0; q < 4; q ++) {
-      const float r = (float)(rho + q) / 128.0f;
-      const float xf = applied ? __frsqrt_rn(2.0f * r * (r - 1.0f) + 1.0f) : 1.0f;
-      float a = 0;
-#pragma unroll
-      for(int c = 0; c < NCH; c ++) {
-        if(c < nch_active) {
-          // (the template's tail T + rho .. is only ever read here: 128 residues of the later tiles)
-          float v = fade_zone ? colored[((size_t)u * nch + c) * ntemplate_ext + T + rho + q] : tv[c][q];
-          if(applied) {
-            v *= 1.0f - r;
-            v += tv[c][q] * r;
-            v *= xf;
-          }
-          v *= sqrtf(e[q][c]);
-          a += v;
-        }
-      }
-      acc[q] = a;
-    }
-    float* dst = yexc + (size_t)out_off[u] + p0;
-    if(rho + 3 < R && p0 + 3 < ny) *(f4u*)dst = f4u{acc[0], acc[1], acc[2], acc[3]};
-    else {
-#pragma unroll
-      for(int q = 0; q < 4; q ++) if(rho + q < R && p0 + q < ny) dst[q] = acc[q];
-    }
-  }
-}
-
 
 // =====================================================================
 // S4  per-frame spectral noise shaping (HOT LOOP E) -- replaces the frame body
@@ -3436,13 +3070,13 @@ DEV void nf_gain_loop(float (&xr)[(1 << LOGN) / WAVE], float (&xi)[(1 << LOGN) /
       // bins k - 3 .. k + 3 (zero beyond the ends), summed in ascending order like the general loop; the
       // count is 7 except at the three lowest and the two highest bins of the half spectrum
 #pragma unroll
-      for(int q = 0; q < 7; q ++) { const float2 pv = lds_rd64(Pw + k + q); ea += pv.x; eb += pv.y; }
+      for(int q = 0; q < 7; q ++) { const float2 pv = Pw[k + q]; ea += pv.x; eb += pv.y; }
       float inv = 1.0f / 7.0f;
       if(m == 0 || m == H - 1) { const int lo = max(0, k - 3), hi = min(nspec - 1, k + 3); inv = 1.0f / (float)(hi - lo + 1); }
       ea *= inv; eb *= inv;
     } else {
 #pragma unroll
-      for(int q = 0; q < 7; q ++) { const float2 pv = lds_rd64(Pw + k + q); const bool in = abs(q - 3) <= mavg_h; ea += in ? pv.x : 0.0f; eb += in ? pv.y : 0.0f; }
+      for(int q = 0; q < 7; q ++) { const float2 pv = Pw[k + q]; const bool in = abs(q - 3) <= mavg_h; ea += in ? pv.x : 0.0f; eb += in ? pv.y : 0.0f; }
       const int lo = max(0, k - mavg_h), hi = min(nspec - 1, k + mavg_h);
       const float inv = 1.0f / (float)(hi - lo + 1);
       ea *= inv; eb *= inv;
@@ -4445,7 +4079,7 @@ int launch_spgm_env(LaunchCtx* P, const BatchDev& d, int nwin_psd, int N, int lo
     LAUNCH("k_spgm_env_wf", (k_spgm_env_wf<LN, LF, false>), dim3(persistent_grid(k_spgm_env_wf<LN, LF, false>, sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS, npairs_of(d))), dim3(WAVE), \
       sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS, d.x, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, \
       d.nframes, d.thop, d.fs, nwin_psd, norm_base, env_out, d.pairs, npairs_of(d), fix_list, fix_count); \
-    if((which & 2) && fix_list && SPGM_EDGE_F64) /* the listed pairs again, exact edge bins (a few dozen wavefronts find work, if any) */ \
+    if((which & 2) && fix_list) /* the listed pairs again, exact edge bins (a few dozen wavefronts find work, if any) */ \
       LAUNCH("k_spgm_env_fix", (k_spgm_env_wf<LN, LF, true>), dim3(npairs_of(d) < 256 ? npairs_of(d) : 256), dim3(WAVE), \
         sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS, d.x, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, \
         d.nframes, d.thop, d.fs, nwin_psd, norm_base, env_out, d.pairs, npairs_of(d), fix_list, fix_count); \
@@ -4508,7 +4142,7 @@ int launch_psd_frames(LaunchCtx* P, const BatchDev& d, const float* xres, int nw
 int launch_kalman(LaunchCtx* P, const BatchDev& d, const float* env, const float* psd_log,
   float* ck, int nspec) {
   if(d.nframes == 0) return 0;
-  LAUNCH("k_kalman", k_kalman, dim3((unsigned)(((size_t)d.npsd * d.n_utt * (KAL_SPLIT ? 2 : 1) + 127) / 128)), dim3(128), 0,
+  LAUNCH("k_kalman", k_kalman, dim3((unsigned)(((size_t)d.npsd * d.n_utt + 127) / 128)), dim3(128), 0,
     env, psd_log, ck, d.frm_off, d.nfrm, d.n_utt, nspec, d.npsd, d.fs, d.psd, d.psdres, d.has_psdres);
   return 0;
 }
@@ -4724,16 +4358,10 @@ int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int
   const int* out_off, const int* out_len, int max_len, float fs_syn, float* yexc,
   const int4* units, int nunits) {
   if(d.n_utt == 0 || max_len == 0) return 0;
-  // default: persistent units (k_excite_units), which form the complex amplitudes themselves; $LLSM_GPU_EXCITE4=0 the
-  // per-sample kernel, =1 the template-position one, both after k_env_params (the caller launches it when cplx != NULL)
+  // default: persistent units (k_excite_units), which form the complex amplitudes themselves; $LLSM_GPU_EXCITE4 set: the
+  // per-sample kernel after k_env_params (the caller launches it when cplx != NULL)
 #define EX_ARGS colored, ntemplate_ext, hits, cplx, d.edc, d.f0, nwin_env, win, d.nchannel, d.maxnhar_e, \
     nch_active, d.frm_off, d.nfrm, out_off, out_len, d.thop, fs_syn, yexc
-  // $LLSM_GPU_EXCITE4=1: by template position, four samples per thread (k_excite_env4).  Measured and NOT the default:
-  // 0.625 ms against 0.587 - 0.596 ms for the per-sample kernel on the bench batch, with and without explicit FMAs
-  // (profiles/r05_b, r05_c kbench lines; LAB.md round 5) -- half the fetches and a third fewer instructions, but 4
-  // instead of 8 wavefronts per SIMD and three dependent table / LDS rounds per tile.  Kept for its test and as a base.
-  const char* e4 = std::getenv("LLSM_GPU_EXCITE4");   // (read per launch: tests switch it)
-  const bool by_template = e4 && e4[0] == '1';
   if(! cplx) {
     if(nunits == 0) return 0;
     if(d.maxnhar_e <= 4) {
@@ -4745,12 +4373,6 @@ int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int
       LAUNCH("k_excite_units", (k_excite_units<4, 8>), dim3(g), dim3(256), 0, units, nunits, colored, ntemplate_ext, hits,
         d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, nwin_env, win, d.nchannel, d.maxnhar_e, nch_active, d.thop, fs_syn, yexc);
     }
-    return 0;
-  }
-  if(by_template && d.nchannel <= 4 && d.maxnhar_e <= 8) {
-    const dim3 grid4((std::min(max_len, 20000) + 1023) / 1024, d.n_utt);
-    if(d.maxnhar_e <= 4) LAUNCH("k_excite_env4", (k_excite_env4<4, 4>), grid4, dim3(256), 0, EX_ARGS);
-    else LAUNCH("k_excite_env4", (k_excite_env4<4, 8>), grid4, dim3(256), 0, EX_ARGS);
     return 0;
   }
   const dim3 grid((max_len + 255) / 256, d.n_utt);

@@ -123,9 +123,6 @@ DEV lf::Solved lf_solve_cached(const lf::Model& m, int lane, const AlphaCache& c
 // Error budget: the open-phase denominator (alpha - jw)^2 + wg^2 is formed as alpha^2 + (wg - w)(wg + w) - j 2 alpha w,
 // whose relative error in 1 / den stays below ~10 ulp at every w (|den| >= 2 alpha w at the resonance, ~w^2 beyond);
 // the result agrees with the float64 form to ~1e-6 relative (tests/test_gpu_l1.py tolerances unchanged).
-#ifndef LF_FAST
-#define LF_FAST 1
-#endif
 struct LfFast { float wg, eps, alpha, sw, ea, ed, k0, kr, pc; double Te, D; };
 DEV LfFast lf_fast(const lf::Solved& s) {
   LfFast q; const double D = s.T0 - s.Te;
@@ -508,19 +505,11 @@ __global__ __launch_bounds__(WAVE) void k_l1_frame(
   // LF source amplitudes at the harmonics, normalised as layer1.c:104-107
   lf::Model m = lf::from_rd((double)rd[g], 1.0 / (double)f, 1.0, g_conv_l1.lf_rd_clamp);
   const lf::Solved s = lf_solve_cached(m, lane, acache, g, rd[g], f);
-#if LF_FAST
   const LfFast sf = lf_fast(s);
   const float vs0 = lf_mag_fast(sf, (double)f);
-#else
-  const double vs0 = lf::magnitude(s, (double)f);
-#endif
   for(int k = lane; k < n; k += WAVE) {
     const float fk = (float)((double)f * (k + 1.0));
-#if LF_FAST
     const float vs = k == 0 ? 1.0f : lf_mag_fast(sf, (double)fk) / ((1.0f + (float)k) * vs0);
-#else
-    const float vs = k == 0 ? 1.0f : (float)(lf::magnitude(s, (double)fk) / ((1.0 + k) * vs0));
-#endif
     float mag, arg; lip_resp(lip_radius, (float)((double)f * (1.0 + k) * 2.0 * 3.14159265358979323846), & mag, & arg);
     A[k] = ampl[(size_t)g * maxnhar + k] / mag / vs;
     Ph[k] = phse[(size_t)g * maxnhar + k] - arg;
@@ -839,20 +828,12 @@ __global__ __launch_bounds__(WAVE) void k_l1_to_l0(
   if(n <= 0) { if(lane == 0) { nhar[g] = 0; has_hm[g] = 1; } return; }
   lf::Model m = lf::from_rd((double)rd[g], 1.0 / (double)f, 1.0, g_conv_l1.lf_rd_clamp);
   const lf::Solved s = lf_solve_cached(m, lane, acache, g, rd[g], f);
-#if LF_FAST
   const LfFast sf = lf_fast(s);
   const float vs0 = lf_mag_fast(sf, (double)f);
-#else
-  const double vs0 = lf::magnitude(s, (double)f);
-#endif
   const float* env = vtmagn + (size_t)g * nspec;
   for(int k = lane; k < n; k += WAVE) {
     const float fk = (float)((double)f * (k + 1.0));
-#if LF_FAST
     const float vs = k == 0 ? 1.0f : lf_mag_fast(sf, (double)fk) / ((1.0f + (float)k) * vs0);
-#else
-    const float vs = k == 0 ? 1.0f : (float)(lf::magnitude(s, (double)fk) / ((1.0 + k) * vs0));
-#endif
     A[k] = expf(DB2LOG_F(interp_lin(env, nspec, fnyq, fk)));
     Ph[k] = vs;
   }
@@ -918,30 +899,18 @@ __global__ __launch_bounds__(NT, PBP_WPE) void k_pbp_pulse(
   // phase delta between the LF model and the stored source phases, per harmonic (llsmutils.c:69-86)
   lf::Model mo = lf::from_rd((double)rd[g], 1.0 / (double)f, 1.0, g_conv_l1.lf_rd_clamp);
   const lf::Solved so = lf_solve_cached(mo, wl, acache, g, rd[g], f);
-#if LF_FAST
   const LfFast sof = lf_fast(so);
   const float ph1 = lf_phase_fast(sof, (double)f);
-#else
-  const float ph1 = (float)lf::phase(so, (double)f);
-#endif
   const float vsshift = vsp[0] - (ph1 - 1.5707963267948966f);
   for(int i = lane; i <= n; i += NT) {
     float d = 0.0f;
     if(i >= 1) {
-#if LF_FAST
       const float ph = lf_phase_fast(sof, (double)i * (double)f) - 1.5707963267948966f;
-#else
-      const float ph = (float)lf::phase(so, (double)i * (double)f) - 1.5707963267948966f;
-#endif
       d = wrapf(vsp[i - 1] - ph - vsshift * (float)i) + VT[i - 1];
     }
     PC[i] = cosf(d); PS[i] = sinf(d);
   }
-#if LF_FAST
   const float lfmagnf0 = lf_mag_fast(sof, (double)f);
-#else
-  const float lfmagnf0 = (float)lf::magnitude(so, (double)f);
-#endif
   __syncthreads();
   // spectrum of the summed pulses (REAL: bins 0 .. size / 2 in natural order; else bit-reversed, all `size` bins)
   const int logN = ilog2_dev(size);
@@ -971,7 +940,6 @@ __global__ __launch_bounds__(NT, PBP_WPE) void k_pbp_pulse(
     // phase-delta term as a complex product -- no atan2 / polar round trip, no trigonometric call per bin.
     const double df = (double)fs / (double)size, tpi = 2.0 * 3.14159265358979323846;
     const float gscale = fnyq / lfmagnf0;
-#if LF_FAST
     // float32 per bin (lf_spec_fast): the phasors e^{-j w Te}, e^{-j w D} are seeded at this lane's first bin from
     // float64-reduced phases and rotated by NT bins per step in float32 (at most size / 2 / NT steps: 8 at 2048 points)
     const LfFast spf = lf_fast(sp);
@@ -981,16 +949,6 @@ __global__ __launch_bounds__(NT, PBP_WPE) void k_pbp_pulse(
       cs_turns((double)(1 + lane) * df * spf.D, & c, & sn); yc = c; ys = -sn;
       cs_turns((double)NT * df * spf.Te, & c, & sn); zrc = c; zrs = -sn;
       cs_turns((double)NT * df * spf.D, & c, & sn); yrc = c; yrs = -sn; }
-#else
-    const double Dd = sp.T0 - sp.Te;
-    const double ea = exp(-sp.alpha * sp.Te), ed = exp(-sp.eps * Dd);
-    double zc, zs, yc, ys;                             // e^{-j w Te}, e^{-j w D} at this lane's first bin
-    { double sn, cs; sincos(tpi * (double)(1 + lane) * df * sp.Te, & sn, & cs); zc = cs; zs = -sn;
-      sincos(tpi * (double)(1 + lane) * df * Dd, & sn, & cs); yc = cs; ys = -sn; }
-    double zrc, zrs, yrc, yrs;                         // their steps over NT bins
-    { double sn, cs; sincos(tpi * (double)NT * df * sp.Te, & sn, & cs); zrc = cs; zrs = -sn;
-      sincos(tpi * (double)NT * df * Dd, & sn, & cs); yrc = cs; yrs = -sn; }
-#endif
     for(int i = 1 + lane; i < halfsize; i += NT) {
       const double fqd = (double)i * df;
       const float fq = (float)fqd;
@@ -1003,11 +961,7 @@ __global__ __launch_bounds__(NT, PBP_WPE) void k_pbp_pulse(
       const float h2 = dc * dc + ds * ds;
       const float hinv = h2 > 0 ? __frsqrt_rn(h2) : 0.0f;
       const float ux = h2 > 0 ? dc * hinv : 1.0f, uy = ds * hinv;         // e^{j delta} (atan2(0, 0) = 0)
-#if LF_FAST
       float re, im; lf_spec_fast(spf, (float)(tpi * fqd), zc, zs, yc, ys, & re, & im);
-#else
-      double re, im; lf::spectrum_core(sp, tpi * fqd, zc, zs, yc, ys, ea, ed, & re, & im);
-#endif
       float ec, es; cs_turns((double)phase_shift * (double)i / (double)size - 0.25, & ec, & es);
       const float er = ec * ux - es * uy, ei = ec * uy + es * ux;
       const float g0 = gscale / fq;
@@ -1015,13 +969,8 @@ __global__ __launch_bounds__(NT, PBP_WPE) void k_pbp_pulse(
       float2 v = X[at(i)];
       v.x += vr * er - vi * ei; v.y += vr * ei + vi * er;
       X[at(i)] = v;
-#if LF_FAST
       { const float t = zc * zrc - zs * zrs; zs = zc * zrs + zs * zrc; zc = t; }
       { const float t = yc * yrc - ys * yrs; ys = yc * yrs + ys * yrc; yc = t; }
-#else
-      double t = zc * zrc - zs * zrs; zs = zc * zrs + zs * zrc; zc = t;
-      t = yc * yrc - ys * yrs; ys = yc * yrs + ys * yrc; yc = t;
-#endif
     }
     __syncthreads();
   }

@@ -17,8 +17,13 @@
 // write groups of the LAST exchange (rows of 4 / 8 float2 at stride 5 / 9) are two-way --
 // tools/fft_plan_sim.py models the index algebra and the gfx950 bank rules and reproduces the
 // measured SQ_LDS_BANK_CONFLICT to the cycle (320 per frame pair of k_spgm_env_wf<11, 1>).
-// A conflict-free layout exists (WF_SWZ below: packed rows, position XOR-ed by a function of
-// the sub-transform index) and was measured: it costs more VALU than the conflicts cost LDS.
+// A conflict-free layout exists (packed rows, position XOR-ed by a function of the sub-transform
+// index; fft_plan_sim.py models it) and was measured: SQ_LDS_BANK_CONFLICT 32.77 M -> 0 per launch
+// of k_spgm_env_wf, but the address arithmetic made k_psd_frames_wf 10 % slower and, applied to
+// every exchange, spilled (2.08 ms) -- it costs more VALU than the conflicts cost LDS.
+// Single ds_read_b64 exchange reads instead of the compiler's ds_read2_b64 pairs halve the LDS read
+// cycles and were slower too (k_spgm_env_wf 0.973 -> 1.035 ms): these kernels are bound by VALU
+// issue, not by the LDS (round 6, profiles/r06_b_kbench_fft_layouts.txt).
 // A 2048-point transform is 3 register passes and 2 exchanges (128 LDS instructions per
 // lane) instead of 6 LDS round trips of a radix-4 in-place FFT.
 //
@@ -27,30 +32,6 @@
 // Inverse transforms call the same code with the real and imaginary arrays swapped
 // (ifft(x) = swap(fft(swap(x))), unscaled).
 #pragma once
-
-// Build switches (tools/kbench.py ablations), both measured in round 6 on one box (profiles/r06_b_kbench_fft_layouts.txt):
-//   WF_RD64  1: the exchange reads are kept as single ds_read_b64 (64 banks, two 32-lane groups, 2 LDS cycles each);
-//            0 (default): the compiler pairs them into ds_read2_b64 (32 banks, 8 cycles per pair).  The single reads
-//            halve the LDS read cycles -- and the kernels got SLOWER (k_spgm_env_wf 0.973 -> 1.035 ms, k_psd_frames_wf
-//            0.189 -> 0.191): they are bound by VALU issue, not by the LDS, and the volatile loads cost scheduling freedom.
-//   WF_SWZ   the exchange layout (WfEx below).  1 / 2 remove EVERY bank conflict (SQ_LDS_BANK_CONFLICT 32.77 M -> 0 per
-//            launch of k_spgm_env_wf, as tools/fft_plan_sim.py predicts to the cycle) -- for address arithmetic that the
-//            padded layout's immediate offsets do not need: k_psd_frames_wf +10 %, k_spgm_env_wf +-0, and with 2 the
-//            hoisted XOR terms spill (2.08 ms).  0 (default): the padded strides of rounds 2 - 5, two-way conflicts on the
-//            writes of the last exchange (17 % of the LDS cycles of a kernel whose LDS is busy a third of the time).
-#ifndef WF_RD64
-#define WF_RD64 0
-#endif
-typedef float wf_v2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) wf_v2 wf_lds_v2;
-// one ds_read_b64 that the compiler will not pair with a neighbour into ds_read2_b64
-DEV float2 lds_rd64(const float2* p) {
-#if WF_RD64
-  const wf_v2 v = *(volatile wf_lds_v2*)p; return make_float2(v.x, v.y);
-#else
-  return *p;
-#endif
-}
 
 template <int LOGN> struct WfPlan;
 template <> struct WfPlan<8>  { static constexpr int NP = 4; static constexpr int r(int j) { return 4; } };
@@ -71,23 +52,12 @@ template <int LOGN> constexpr int wf_nseed_pass(int j) {
 }
 template <int LOGN> constexpr int wf_seed_base(int j) { return j == 0 ? 0 : wf_seed_base<LOGN>(j - 1) + wf_nseed_pass<LOGN>(j - 1); }
 template <int LOGN> constexpr int wf_nseed() { return wf_seed_base<LOGN>(WfPlan<LOGN>::NP); }
-#ifndef WF_SWZ
-#define WF_SWZ 0                                     // 0: padded strides everywhere (rounds 2 - 5); 1: XOR-swizzled packed rows below 32 points; 2: every exchange
-#endif
-// layout of the exchange after pass j: element `pos` of sub-transform `cc` (length NN) -> float2 index.
-// Packed rows (stride NN) with pos ^ f(cc): a read group (32 lanes) takes NBN consecutive positions of 32 / NBN
-// consecutive sub-transforms; min(NN, 32) / NBN of them share a residue class of the 32 float2 banks, and f sends those to
-// distinct NBN-blocks.  A write group (16 lanes) covers 16 consecutive float2 of one or more whole rows whatever f is.
+// layout of the exchange after pass j: element `pos` of sub-transform `cc` (length NN) -> float2 index, rows padded to
+// the stride NN + NN / RN (see the top of this file)
 template <int LOGN, int J> struct WfEx {
-  static constexpr int RN = WfPlan<LOGN>::r(J + 1), NN = wf_len<LOGN>(J + 1), NBN = NN / RN;
-  static constexpr bool SWZ = WF_SWZ == 2 || (WF_SWZ == 1 && NN < 32);
-  static constexpr int ST = SWZ ? NN : NN + NN / RN;
-  static constexpr int SH = (SWZ && NN < 32) ? wf_log2(32 / NN) : 0;
-  static constexpr int FM = SWZ ? (NN < 32 ? NN : 32) / NBN : 1;
-  DEV static int idx(int cc, int pos) {
-    if constexpr (SWZ) return cc * NN + (pos ^ (((cc >> SH) & (FM - 1)) * NBN));
-    else return cc * ST + pos;
-  }
+  static constexpr int RN = WfPlan<LOGN>::r(J + 1), NN = wf_len<LOGN>(J + 1);
+  static constexpr int ST = NN + NN / RN;
+  DEV static int idx(int cc, int pos) { return cc * ST + pos; }
   static constexpr int elems = ((1 << LOGN) / NN) * ST;
 };
 // LDS float2 needed by the exchanges of one transform
@@ -255,11 +225,7 @@ DEV void wf_exchange(float (&xr)[P], float (&xi)[P], float2* lds, int lane) {
     const int c = beta2 / NBN, b2 = beta2 % NBN;
 #pragma unroll
     for(int r2 = 0; r2 < RN; r2 ++) {
-#if WF_RD64
-      const wf_v2 v = *(volatile wf_lds_v2*)(lds + EX::idx(c, b2 + NBN * r2));
-#else
       const float2 v = lds[EX::idx(c, b2 + NBN * r2)];
-#endif
       xr[s2 + SN * r2] = v.x; xi[s2 + SN * r2] = v.y;
     }
   }

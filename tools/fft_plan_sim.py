@@ -15,7 +15,7 @@ WAVE = 64
 PLANS = {8: [4, 4, 4, 4], 9: [8, 8, 8], 10: [16, 16, 4], 11: [16, 16, 8], 12: [16, 16, 16]}
 
 
-SWZ = 2                     # wave_fft.h WF_SWZ: 0 padded strides, 1 XOR-swizzled packed rows below 32 points, 2 every exchange
+SWZ = 2                     # 0 padded strides (wave_fft.h), 1 XOR-swizzled packed rows below 32 points, 2 every exchange (measured slower)
 
 
 def layout(nn, rn):
@@ -111,7 +111,7 @@ def run(logn, verbose=True):
     return err
 
 
-READ_KIND = "r"             # "r2": what the compiler made of the reads before WF_RD64 (ds_read2_b64)
+READ_KIND = "r"             # "r2": what the compiler makes of the exchange reads (ds_read2_b64 pairs)
 
 if __name__ == "__main__":
     if "--padded" in sys.argv:

@@ -1,8 +1,9 @@
-"""Build the variants first (here, no GPU needed):  python tools/kbench.py --build --ablate HT_SCHED=1 HT_SCHED=1,HT_WPE=4
+"""Build the variants first (here, no GPU needed):  python tools/kbench.py --build --ablate NF_ABL=2 HT_WPE=2,HT_CHUNK=4
 Kernel-level timing of one analysis+synthesis step for one or more builds of the library
-(experiment helper: ablation builds via `-D`, selected with LLSM_AMD_LIB).
+(experiment helper: ablation builds via `-D`, selected with LLSM_AMD_LIB; libllsm2_amd/csrc/kernels.h lists the switches,
+which only these builds -- they add -DLLSM_KBENCH_EXPERIMENTS -- may set).
 
-    python tools/kbench.py [--utts 512] [--kernels k_spgm_env,...] [--ablate SPGM_ABLATE=1 ...]
+    python tools/kbench.py [--utts 512] [--ablate KAL_ABL=1 ...]
 """
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
