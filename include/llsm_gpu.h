@@ -117,6 +117,8 @@ enum {
   LLSM_GPU_NVSPHSE,      /* int   [F]                    length of VSPHSE; 0: no layer-1 members */
   LLSM_GPU_PBPSYN,       /* int   [F]                    LLSM_FRAME_PBPSYN       */
   LLSM_GPU_HAS_HM,       /* int   [F]                    AMPL / PHSE / NHAR rows valid (LLSM_FRAME_HM present) */
+  /* present after llsm_gpu_batch_enable_coder */
+  LLSM_GPU_CODE,         /* float [F][order_spec + order_bap + 3]  frame-coder vectors   */
   LLSM_GPU_NARRAYS
 };
 
@@ -289,6 +291,43 @@ void llsm_gpu_retime_uniform_positions(int nfrm_src, int nfrm_dst, FP_TYPE* pos)
  * narrows the harmonic band by rho; VSPHSE is not extended. */
 enum { LLSM_GPU_WARP_PSD = 1 };
 int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0_ratio, const FP_TYPE* formant_ratio, int flags);
+
+/* ---- frame coder of a device-resident layer-1 batch: every frame <-> the vector [voicing, f0, Rd, order_spec mel-spectrum
+ * points, order_bap band aperiodicities] of llsm_coder_encode_frames / llsm_coder_decode_frames (llsm.h), without leaving
+ * the device.  The vectors are one more flat array, LLSM_GPU_CODE: upload, download, device_ptr, array_bytes and
+ * transfer_many serve it like any other.  encode and decode are asynchronous on the context's stream; a refused call
+ * returns -1, sets llsm_gpu_last_error() and writes and launches nothing.
+ *
+ * enable_coder     needs layer 1 on the batch; takes nspec, the lip radius and fnyq from it; orders are checked as
+ *                  llsm_create_coder checks them (1 <= order_spec <= nspec - 1, order_bap >= 1, nspec - 1 a power of two
+ *                  >= 32).  Allocates LLSM_GPU_CODE (zeroed) and builds the mel axis, which lives with the batch: the same
+ *                  orders again do nothing, other orders reallocate the array.
+ * coder_dimension  order_spec + order_bap + 3; 0 before enable_coder.
+ * encode           reads F0, RD, PSD, VTMAGN, NVSPHSE; writes LLSM_GPU_CODE and nothing else.  A frame is voiced when
+ *                  F0 > 0 and NVSPHSE > 0.
+ * decode           writes, per frame, the rows that flattening the frame of llsm_coder_decode_frames(.., use_layer1, ..)
+ *                  gives (llsm_chunk_to_flat, llsm_chunk_to_flat_l1); nhar = fnyq / max(20, f0) on voiced vectors:
+ *                    F0, RD, PSD          always
+ *                    use_layer1 = 1       voiced: VTMAGN, VSPHSE written, NVSPHSE = nhar, NHAR = 0 and HAS_HM = 0 (so that
+ *                                         llsm_gpu_batch_tolayer0(b, 1) rebuilds the harmonics; AMPL and PHSE are not
+ *                                         written); unvoiced: NVSPHSE = 0, NHAR = 0, HAS_HM = 1, layer-1 rows not written
+ *                    use_layer1 = 0       NHAR = nhar, AMPL and PHSE the minimum-phase harmonics (zero beyond nhar),
+ *                                         NVSPHSE = 0, HAS_HM = 1; VTMAGN and VSPHSE are not written
+ *                    what llsm_create_frame leaves: EDC = 1e-5 on every channel, NHAR_E = maxnhar_e with EENV_AMPL and
+ *                    EENV_PHSE zero, HAS_PSDRES = 0, PBPSYN = 0.  X, XRES, PSDRES, WHITE and the outputs are not written.
+ *                  The lf_rd_clamp convention is honoured.  Afterwards the batch's lowest-F0 bound is unknown, as after a
+ *                  partial upload.
+ * A frame's vector and rows depend on that frame alone: not on its neighbours, the batch or its place in it.
+ * Refused: a NULL batch, a batch without layer 1, coder not enabled, orders out of range, use_layer1 not 0 or 1, rows too
+ * long for the kernels' LDS (three float rows of nspec bins, for decode also two rows of maxnhar harmonics and the
+ * minimum-phase transform of maxnhar harmonics, within 160 KiB = 163840 bytes: every nspec enable_layer1 accepts fits with
+ * maxnhar up to 1024).
+ * Known limit: nhar is capped at the batch's maxnhar (the host decoder sizes its rows to the largest count instead), so a
+ * vector whose f0 lies below fnyq / maxnhar loses its top harmonics. */
+int llsm_gpu_batch_enable_coder(llsm_gpu_batch* b, int order_spec, int order_bap);
+int llsm_gpu_batch_coder_dimension(llsm_gpu_batch* b);
+int llsm_gpu_batch_encode(llsm_gpu_batch* b);
+int llsm_gpu_batch_decode(llsm_gpu_batch* b, int use_layer1);
 
 /* chunk <-> flat layer-1 rows (same row indexing as llsm_flat_params) */
 typedef struct {

@@ -82,7 +82,7 @@ HMPP, HMCZT = 0, 1
 # flat array ids (llsm_gpu.h)
 (A_X, A_F0, A_NHAR, A_AMPL, A_PHSE, A_PSD, A_PSDRES, A_EDC, A_NHAR_E, A_EENV_AMPL,
  A_EENV_PHSE, A_XRES, A_Y, A_YSIN, A_YNOISE, A_WHITE, A_HAS_PSDRES,
- A_RD, A_VTMAGN, A_VSPHSE, A_NVSPHSE, A_PBPSYN, A_HAS_HM, A_NARRAYS) = range(24)
+ A_RD, A_VTMAGN, A_VSPHSE, A_NVSPHSE, A_PBPSYN, A_HAS_HM, A_CODE, A_NARRAYS) = range(25)
 
 _INT_ARRAYS = {A_NHAR, A_NHAR_E, A_HAS_PSDRES, A_NVSPHSE, A_PBPSYN, A_HAS_HM}
 
@@ -130,6 +130,7 @@ llsm_create_rtsynth_group llsm_delete_rtsynth_group llsm_rtsynth_group_getlatenc
 llsm_rtsynth_group_numoutput llsm_rtsynth_group_feed llsm_rtsynth_group_feed_many llsm_rtsynth_group_fetch llsm_rtsynth_group_fetch_all llsm_gpu_rt_graph llsm_gpu_rt_graph_hops llsm_gpu_rt_fused llsm_gpu_rt_direct llsm_gpu_rt_pipeline llsm_gpu_analysis_overlap llsm_slab_stats llsm_slab_trim llsm_delete_chunks llsm_gpu_release_cached_batches llsm_gpu_device_numa_node llsm_gpu_bind_thread_to_device llsm_gpu_batch_packed_words llsm_gpu_batch_download_packed llsm_gpu_batch_upload_packed llsm_gpu_batch_download_outputs llsm_gpu_batch_download_packed_block llsm_gpu_batch_upload_packed_block llsm_gpu_batch_transfer_many llsm_gpu_batch_params_layout llsm_gpu_batch_transfer_params llsm_gpu_shared_f0_tiles llsm_gpu_synth_tables llsm_gpu_pbp_real_ifft llsm_frame_compute_snr
 llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime llsm_gpu_retime_uniform_positions
 llsm_gpu_batch_pitch_formant
+llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode llsm_gpu_batch_decode
 """.split()
 
 _lib = None
@@ -191,6 +192,14 @@ def load():
     L.llsm_gpu_retime_uniform_positions.argtypes = [C.c_int, C.c_int, P_fp]
     L.llsm_gpu_retime_uniform_positions.restype = None
     L.llsm_gpu_batch_pitch_formant.argtypes = [vp, P_fp, P_fp, C.c_int]
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the coder)
+        L.llsm_gpu_batch_enable_coder.argtypes = [vp, C.c_int, C.c_int]
+        L.llsm_gpu_batch_coder_dimension.argtypes = [vp]
+        L.llsm_gpu_batch_encode.argtypes = [vp]
+        L.llsm_gpu_batch_decode.argtypes = [vp, C.c_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
     L.llsm_chunk_to_flat_l1.argtypes = [C.POINTER(Chunk), C.POINTER(FlatL1), C.c_int]
     L.llsm_flat_l1_to_chunk.argtypes = [C.POINTER(FlatL1), C.c_int, C.POINTER(Chunk)]
     L.llsm_chunk_tolayer1.argtypes = [C.POINTER(Chunk), C.c_int]
@@ -420,6 +429,7 @@ class Batch:
         F, me = l.total_frames, max(l.maxnhar_e, 1)
         ns = getattr(self, "nspec", 0)
         return {A_RD: (F,), A_VTMAGN: (F, ns), A_VSPHSE: (F, l.maxnhar), A_NVSPHSE: (F,), A_PBPSYN: (F,), A_HAS_HM: (F,),
+                A_CODE: (F, self.coder_dimension),
                 A_X: (l.total_samples,), A_XRES: (l.total_samples,), A_F0: (F,), A_NHAR: (F,),
                 A_NHAR_E: (F,), A_HAS_PSDRES: (F,), A_AMPL: (F, l.maxnhar), A_PHSE: (F, l.maxnhar),
                 A_PSD: (F, l.npsd), A_PSDRES: (F, l.npsd), A_EDC: (F, l.nchannel),
@@ -511,6 +521,20 @@ class Batch:
         _check(self.L.llsm_gpu_batch_pitch_formant(self.h, None if r is None else r.ctypes.data_as(P_fp),
                                                    None if a is None else a.ctypes.data_as(P_fp),
                                                    WARP_PSD if warp_psd else 0), "pitch_formant")
+
+    # ---- frame coder (llsm_gpu.h): rows <-> LLSM_GPU_CODE, [total_frames][coder_dimension] float32
+    def enable_coder(self, order_spec, order_bap):
+        _check(self.L.llsm_gpu_batch_enable_coder(self.h, int(order_spec), int(order_bap)), "enable_coder")
+
+    @property
+    def coder_dimension(self):
+        return int(self.L.llsm_gpu_batch_coder_dimension(self.h))
+
+    def encode(self):
+        _check(self.L.llsm_gpu_batch_encode(self.h), "encode")
+
+    def decode(self, use_layer1):
+        _check(self.L.llsm_gpu_batch_decode(self.h, int(use_layer1)), "decode")
 
     def synthesize(self, sopt, seed=0, injected_white=False):
         _check(self.L.llsm_gpu_batch_synthesize(self.h, C.byref(sopt), seed, int(injected_white)), "synthesize")

@@ -174,6 +174,9 @@ struct llsm_gpu_batch {
   // in page-locked memory that mod_ev says the copies have left
   DevBuf<float> mod_theta, mod_pos, mod_ratio; DevBuf<int> mod_res;
   PinVec<int> mod_stage; hipEvent_t mod_ev = nullptr;
+  // frame coder (batch_coder.cpp): the orders of LLSM_GPU_CODE (0: not enabled) and the mel axis, built once per batch
+  int coder_os = 0, coder_ob = 0; float coder_mel_floor = 0, coder_mel_ceil = 0;
+  DevBuf<float> coder_mel;
 };
 
 
@@ -190,5 +193,22 @@ template <class T> inline int upload_vec(DevBuf<T>& d, const std::vector<T>& h) 
   return 0;
 }
 
+// every parameter row of the batch as the edit kernels take them (modify.cpp, batch_coder.cpp)
+inline ModRows mod_rows(llsm_gpu_batch* b) {
+  ModRows r;
+  r.nframes = b -> lay.total_frames; r.maxnhar = b -> lay.maxnhar; r.maxnhar_e = b -> lay.maxnhar_e;
+  r.npsd = b -> lay.npsd; r.nchannel = b -> lay.nchannel; r.nspec = b -> l1_nspec;
+  r.f0 = (float*)b -> arr[LLSM_GPU_F0]; r.nhar = (int*)b -> arr[LLSM_GPU_NHAR];
+  r.ampl = (float*)b -> arr[LLSM_GPU_AMPL]; r.phse = (float*)b -> arr[LLSM_GPU_PHSE];
+  r.psd = (float*)b -> arr[LLSM_GPU_PSD]; r.psdres = (float*)b -> arr[LLSM_GPU_PSDRES];
+  r.has_psdres = (int*)b -> arr[LLSM_GPU_HAS_PSDRES]; r.edc = (float*)b -> arr[LLSM_GPU_EDC];
+  r.nhar_e = (int*)b -> arr[LLSM_GPU_NHAR_E];
+  r.eenv_ampl = (float*)b -> arr[LLSM_GPU_EENV_AMPL]; r.eenv_phse = (float*)b -> arr[LLSM_GPU_EENV_PHSE];
+  const bool l1 = b -> l1_nspec > 0;
+  r.rd = l1 ? (float*)b -> arr[LLSM_GPU_RD] : nullptr; r.vtmagn = l1 ? (float*)b -> arr[LLSM_GPU_VTMAGN] : nullptr;
+  r.vsphse = l1 ? (float*)b -> arr[LLSM_GPU_VSPHSE] : nullptr; r.nvsphse = l1 ? (int*)b -> arr[LLSM_GPU_NVSPHSE] : nullptr;
+  r.pbpsyn = l1 ? (int*)b -> arr[LLSM_GPU_PBPSYN] : nullptr; r.has_hm = l1 ? (int*)b -> arr[LLSM_GPU_HAS_HM] : nullptr;
+  return r;
+}
 
 #endif

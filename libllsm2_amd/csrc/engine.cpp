@@ -600,6 +600,7 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> l1_proj.release(); b -> l1_alpha.release(); b -> l1_alpha_key.release();
   b -> mod_theta.release(); b -> mod_pos.release(); b -> mod_ratio.release(); b -> mod_res.release();
   if(b -> mod_ev) { (void)hipEventDestroy(b -> mod_ev); b -> mod_ev = nullptr; }
+  b -> coder_mel.release();
   delete b;
 }
 

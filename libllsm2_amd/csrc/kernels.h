@@ -291,4 +291,8 @@ int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const Re
 int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, const float* rho, const float* alpha,
   int warp_psd);
 
+// ---- frame coder of a device-resident batch (batch_coder.cpp): launch_coder_encode / launch_coder_decode above on the batch's
+// rows, then the members the host decoder leaves at their llsm_create_frame values (coder_kernels.hip)
+int launch_batch_decode_rest(LaunchCtx* P, const ModRows& r, int use_l1);
+
 #endif

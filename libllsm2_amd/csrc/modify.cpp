@@ -18,23 +18,6 @@
 namespace {
 const double kPi = 3.14159265358979323846;
 
-ModRows mod_rows(llsm_gpu_batch* b) {
-  ModRows r;
-  r.nframes = b -> lay.total_frames; r.maxnhar = b -> lay.maxnhar; r.maxnhar_e = b -> lay.maxnhar_e;
-  r.npsd = b -> lay.npsd; r.nchannel = b -> lay.nchannel; r.nspec = b -> l1_nspec;
-  r.f0 = (float*)b -> arr[LLSM_GPU_F0]; r.nhar = (int*)b -> arr[LLSM_GPU_NHAR];
-  r.ampl = (float*)b -> arr[LLSM_GPU_AMPL]; r.phse = (float*)b -> arr[LLSM_GPU_PHSE];
-  r.psd = (float*)b -> arr[LLSM_GPU_PSD]; r.psdres = (float*)b -> arr[LLSM_GPU_PSDRES];
-  r.has_psdres = (int*)b -> arr[LLSM_GPU_HAS_PSDRES]; r.edc = (float*)b -> arr[LLSM_GPU_EDC];
-  r.nhar_e = (int*)b -> arr[LLSM_GPU_NHAR_E];
-  r.eenv_ampl = (float*)b -> arr[LLSM_GPU_EENV_AMPL]; r.eenv_phse = (float*)b -> arr[LLSM_GPU_EENV_PHSE];
-  const bool l1 = b -> l1_nspec > 0;
-  r.rd = l1 ? (float*)b -> arr[LLSM_GPU_RD] : nullptr; r.vtmagn = l1 ? (float*)b -> arr[LLSM_GPU_VTMAGN] : nullptr;
-  r.vsphse = l1 ? (float*)b -> arr[LLSM_GPU_VSPHSE] : nullptr; r.nvsphse = l1 ? (int*)b -> arr[LLSM_GPU_NVSPHSE] : nullptr;
-  r.pbpsyn = l1 ? (int*)b -> arr[LLSM_GPU_PBPSYN] : nullptr; r.has_hm = l1 ? (int*)b -> arr[LLSM_GPU_HAS_HM] : nullptr;
-  return r;
-}
-
 int launch_failed(const char* what, int rc) {
   llsm_set_error(std::string(what) + ": launch failed: " + hipGetErrorString((hipError_t)rc));
   return -1;
