@@ -428,6 +428,32 @@ int         llsm_blob_view_l1(const void* blob, size_t bytes, llsm_flat_l1* view
 int         llsm_gpu_batch_upload_blob(llsm_gpu_batch* b, int utt, const void* blob, size_t bytes);
 /* utterances [utt0, utt0 + n) from blobs[0 .. n): rows gathered in page-locked staging, one copy per array and group */
 int         llsm_gpu_batch_upload_blobs(llsm_gpu_batch* b, int utt0, int n, const void* const* blobs, const size_t* bytes);
+/* The other direction: utterances of a resident batch as blobs, packed on the device (csrc/batch_blob.cpp) -- no row
+ * download at the batch's full widths, no container tree.  The blob of utterance u is byte for byte what
+ * llsm_chunk_to_blob writes for the chunk built from the utterance's downloaded rows the way llsm_blob_to_chunk builds one:
+ * conf from llsm_aoptions_toconf(batch options, batch fnyq) with NFRM (and LLSM_CONF_NSPEC when the batch has layer 1),
+ * llsm_flat_to_chunk, llsm_flat_l1_to_chunk with has_rd = 1 on every frame, HM removed where HAS_HM is 0.  So NHAR and the
+ * AMPL / PHSE rows survive on voiced frames with HAS_HM only, NHAR_E and the envelope rows on voiced frames only, VTMAGN /
+ * VSPHSE where NVSPHSE > 0, PSDRES where HAS_PSDRES is set, and the row widths are the largest surviving counts of the
+ * utterance, not the batch's maxnhar / maxnhar_e.  An utterance's bytes depend on its own rows alone.
+ *   llsm_blob_bytes                     host only: bytes of a version-2 blob of this shape (0 and a message on a negative
+ *                                       dimension)
+ *   llsm_gpu_batch_blob_sizes           sizes[k] = bytes of the blob of utterance utt0 + k as the batch stands now (the
+ *                                       widths are found on the device)
+ *   llsm_gpu_batch_download_blobs       utterance utt0 + k into dst[k]: capacity[k] bytes of any host memory, 8-byte aligned
+ *   llsm_gpu_batch_download_blob_block  the same blobs back to back in ONE host block (8-byte aligned): blob k at
+ *                                       offsets[k], offsets[n] = bytes used, every offset a multiple of 16, the bytes between
+ *                                       blobs zero; a page-locked block (llsm_gpu_alloc_host) is written by the copy engine
+ *                                       directly, any other goes through the batch's page-locked staging area
+ * Synchronous: on return the blobs are in the caller's memory.  The calls read the batch and write nothing in it (rows,
+ * lowest-F0 bound).  n == 0 returns 0.  Refused with -1 and a message, with no byte of any destination written: a NULL
+ * batch, a range outside the batch, a NULL or misaligned destination (all before anything is launched); a capacity that is
+ * too small (the message names the utterance and the bytes needed), a block that is too small, one utterance larger than
+ * the 64 MiB staging area (after the width reduction, before anything is packed). */
+size_t      llsm_blob_bytes(int nfrm, int maxnhar, int maxnhar_e, int npsd, int nchannel, int nchanfreq, int nspec);
+int         llsm_gpu_batch_blob_sizes(llsm_gpu_batch* b, int utt0, int n, size_t* sizes);
+int         llsm_gpu_batch_download_blobs(llsm_gpu_batch* b, int utt0, int n, void* const* dst, const size_t* capacity);
+int         llsm_gpu_batch_download_blob_block(llsm_gpu_batch* b, int utt0, int n, void* block, size_t capacity, size_t* offsets);
 
 /* ---- llsmrt stream groups (BASELINE.json config 4: many concurrent streams per GPU) ----
  * The reference's llsmrt buffer is one stream (llsmrt.h:33-54).  A group advances n_streams

@@ -131,6 +131,7 @@ llsm_rtsynth_group_numoutput llsm_rtsynth_group_feed llsm_rtsynth_group_feed_man
 llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime llsm_gpu_retime_uniform_positions
 llsm_gpu_batch_pitch_formant
 llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode llsm_gpu_batch_decode
+llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu_batch_download_blob_block
 """.split()
 
 _lib = None
@@ -197,6 +198,15 @@ def load():
         L.llsm_gpu_batch_coder_dimension.argtypes = [vp]
         L.llsm_gpu_batch_encode.argtypes = [vp]
         L.llsm_gpu_batch_decode.argtypes = [vp, C.c_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the blob export)
+        L.llsm_blob_bytes.restype = C.c_size_t
+        L.llsm_blob_bytes.argtypes = [C.c_int] * 7
+        L.llsm_gpu_batch_blob_sizes.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.llsm_gpu_batch_download_blobs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.llsm_gpu_batch_download_blob_block.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -535,6 +545,39 @@ class Batch:
 
     def decode(self, use_layer1):
         _check(self.L.llsm_gpu_batch_decode(self.h, int(use_layer1)), "decode")
+
+    # ---- export as chunk blobs (llsm_gpu.h): the wire format of csrc/wire.cpp, packed on the device
+    def _blob_range(self, utt0, n):
+        return int(utt0), int(self.layout.n_utt - utt0 if n is None else n)
+
+    def blob_sizes(self, utt0=0, n=None):
+        """bytes of the blobs of utterances [utt0, utt0 + n) as the batch stands now (llsm_gpu_batch_blob_sizes)"""
+        utt0, n = self._blob_range(utt0, n)
+        sizes = (C.c_size_t * max(n, 1))()
+        _check(self.L.llsm_gpu_batch_blob_sizes(self.h, utt0, n, sizes), "blob_sizes")
+        return [int(sizes[k]) for k in range(n)]
+
+    def download_blobs(self, utt0=0, n=None, as_bytes=False):
+        """the blobs of utterances [utt0, utt0 + n): a list of uint8 arrays (8-byte aligned: llsm_blob_view takes them), or
+        of bytes objects (llsm_gpu_batch_download_blobs)"""
+        utt0, n = self._blob_range(utt0, n)
+        sizes = self.blob_sizes(utt0, n)
+        words = [np.zeros((s + 7) // 8, np.uint64) for s in sizes]
+        ptrs = (C.c_void_p * max(n, 1))(*[w.ctypes.data for w in words])
+        caps = (C.c_size_t * max(n, 1))(*sizes)
+        _check(self.L.llsm_gpu_batch_download_blobs(self.h, utt0, n, ptrs, caps), "download_blobs")
+        out = [w.view(np.uint8)[:s] for w, s in zip(words, sizes)]
+        return [o.tobytes() for o in out] if as_bytes else out
+
+    def download_blob_block(self, block, utt0=0, n=None):
+        """the same blobs back to back in `block` (a uint8 array, page-locked or not): returns the n + 1 offsets
+        (llsm_gpu_batch_download_blob_block)"""
+        utt0, n = self._blob_range(utt0, n)
+        assert block.dtype == np.uint8 and block.flags.c_contiguous
+        offs = (C.c_size_t * (max(n, 0) + 1))()
+        _check(self.L.llsm_gpu_batch_download_blob_block(self.h, utt0, n, C.c_void_p(block.ctypes.data), block.nbytes, offs),
+               "download_blob_block")
+        return [int(o) for o in offs]
 
     def synthesize(self, sopt, seed=0, injected_white=False):
         _check(self.L.llsm_gpu_batch_synthesize(self.h, C.byref(sopt), seed, int(injected_white)), "synthesize")

@@ -177,6 +177,10 @@ struct llsm_gpu_batch {
   // frame coder (batch_coder.cpp): the orders of LLSM_GPU_CODE (0: not enabled) and the mel axis, built once per batch
   int coder_os = 0, coder_ob = 0; float coder_mel_floor = 0, coder_mel_ceil = 0;
   DevBuf<float> coder_mel;
+  // export as chunk blobs (batch_blob.cpp): the three widths per utterance, the table of blob headers and placements the
+  // pack kernel reads (followed by chanfreq), and the staging area the blobs are packed into -- all grow-only
+  DevBuf<int> blob_widths; DevBuf<char> blob_tab; DevBuf<unsigned char> blob_dev;
+  PinVec<int> blob_widths_h; PinVec<char> blob_tab_h;
 };
 
 

@@ -601,6 +601,7 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> mod_theta.release(); b -> mod_pos.release(); b -> mod_ratio.release(); b -> mod_res.release();
   if(b -> mod_ev) { (void)hipEventDestroy(b -> mod_ev); b -> mod_ev = nullptr; }
   b -> coder_mel.release();
+  b -> blob_widths.release(); b -> blob_tab.release(); b -> blob_dev.release();
   delete b;
 }
 

@@ -295,4 +295,14 @@ int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, con
 // rows, then the members the host decoder leaves at their llsm_create_frame values (coder_kernels.hip)
 int launch_batch_decode_rest(LaunchCtx* P, const ModRows& r, int use_l1);
 
+// ---- export of a device-resident batch as chunk blobs (batch_blob.cpp, blob_kernels.hip; byte layout: wire_layout.h)
+namespace llsm_wire { struct BlobEntry; }
+// widths[3 k + 0 / 1 / 2]: the largest NHAR, NVSPHSE and NHAR_E that survive in the blob of the utterance whose frames are
+// frm_off[k] .. frm_off[k] + nfrm[k] (k < n)
+int launch_blob_widths(LaunchCtx* P, const ModRows& r, const int* frm_off, const int* nfrm, int n, int* widths);
+// every byte of the n blobs of `tab` into `stage` (16-byte aligned): header, chanfreq (nchanfreq floats), rows at the
+// blob's own widths, zero padding, and the gap up to the next multiple of 16 behind each blob
+int launch_blob_pack(LaunchCtx* P, const ModRows& r, const llsm_wire::BlobEntry* tab, const float* chanfreq, int n,
+  int max_nfrm, unsigned char* stage);
+
 #endif

@@ -29,25 +29,12 @@
 
 #include "engine.h"
 #include "llsm_gpu.h"
+#include "wire_layout.h"
+
+using namespace llsm_wire;                               // array order, Header, Shape, layout(): wire_layout.h
 
 namespace {
-enum { A_CHANFREQ, A_F0, A_NHAR, A_AMPL, A_PHSE, A_PSD, A_PSDRES, A_HASRES, A_EDC, A_NHAR_E, A_EAMP, A_EPHS, NARR1,
-       A_RD = NARR1, A_HASRD, A_VTMAGN, A_VSPHSE, A_NVS, A_PBPSYN, A_HASHM, NARR };
-
-struct Header {
-  char magic[8];
-  uint32_t version, header_bytes;
-  int32_t nfrm, maxnhar, maxnhar_e, npsd, nchannel, nchanfreq;
-  float thop, fnyq, lip_radius; int32_t nspec;
-  uint64_t total_bytes;
-  uint64_t offset[NARR];                               // version 1 blobs carry the first NARR1 entries only
-};
-size_t header_bytes_of(uint32_t version) { return sizeof(Header) - (version == 1 ? sizeof(uint64_t) * (NARR - NARR1) : 0); }
 const char MAGIC[8] = {'L', 'L', 'S', 'M', '2', 'L', '0', '\0'};
-
-size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
-
-struct Shape { int nfrm, maxnhar, me, npsd, nch, ncf, nspec = 0; float thop, fnyq, lip; const FP_TYPE* chanfreq; };
 
 bool shape_of(llsm_chunk* c, Shape& s) {
   if(! c || ! c -> conf) return false;
@@ -75,30 +62,6 @@ bool shape_of(llsm_chunk* c, Shape& s) {
       if(nm -> eenv[k] && nm -> eenv[k] -> nhar > s.me) s.me = nm -> eenv[k] -> nhar;
   }
   return s.nfrm >= 0 && s.npsd > 0 && s.nch > 0;
-}
-
-// byte sizes of the arrays, in blob order
-void array_bytes(const Shape& s, size_t* b) {
-  const size_t F = (size_t)s.nfrm, me = (size_t)(s.me > 0 ? s.me : 1);
-  b[A_CHANFREQ] = sizeof(float) * (size_t)s.ncf;
-  b[A_F0] = sizeof(float) * F; b[A_NHAR] = sizeof(int32_t) * F;
-  b[A_AMPL] = b[A_PHSE] = sizeof(float) * F * (size_t)s.maxnhar;
-  b[A_PSD] = b[A_PSDRES] = sizeof(float) * F * (size_t)s.npsd;
-  b[A_HASRES] = sizeof(int32_t) * F;
-  b[A_EDC] = sizeof(float) * F * (size_t)s.nch;
-  b[A_NHAR_E] = sizeof(int32_t) * F;
-  b[A_EAMP] = b[A_EPHS] = sizeof(float) * F * (size_t)s.nch * me;
-  const size_t L1 = s.nspec > 0 ? 1 : 0;
-  b[A_RD] = sizeof(float) * F * L1; b[A_HASRD] = b[A_NVS] = b[A_PBPSYN] = b[A_HASHM] = sizeof(int32_t) * F * L1;
-  b[A_VTMAGN] = sizeof(float) * F * (size_t)s.nspec; b[A_VSPHSE] = sizeof(float) * F * (size_t)s.maxnhar * L1;
-}
-
-size_t layout(const Shape& s, uint64_t* off, uint32_t version = 2) {
-  size_t b[NARR]; array_bytes(s, b);
-  size_t at = pad8(header_bytes_of(version));
-  const int narr = version == 1 ? NARR1 : NARR;
-  for(int i = 0; i < narr; i ++) { if(off) off[i] = at; at += pad8(b[i]); }
-  return at;
 }
 
 llsm_flat_l1 l1_view_of(const Header& h, unsigned char* base) {
@@ -157,13 +120,9 @@ extern "C" size_t llsm_chunk_blob_size(llsm_chunk* src) {
 extern "C" long long llsm_chunk_to_blob(llsm_chunk* src, void* dst, size_t capacity) {
   Shape s;
   if(! shape_of(src, s)) { llsm_set_error("llsm_chunk_to_blob: chunk without NFRM/NPSD/NCHANNEL/THOP/FNYQ"); return -1; }
-  Header h; std::memset(& h, 0, sizeof(h));
-  const size_t total = layout(s, h.offset);
+  Header h;
+  const size_t total = fill_header(s, h);
   if(! dst || capacity < total) { llsm_set_error("llsm_chunk_to_blob: destination too small"); return -1; }
-  std::memcpy(h.magic, MAGIC, 8);
-  h.version = 2; h.header_bytes = (uint32_t)header_bytes_of(2); h.nspec = s.nspec;
-  h.nfrm = s.nfrm; h.maxnhar = s.maxnhar; h.maxnhar_e = s.me; h.npsd = s.npsd; h.nchannel = s.nch;
-  h.nchanfreq = s.ncf; h.thop = s.thop; h.fnyq = s.fnyq; h.lip_radius = s.lip; h.total_bytes = total;
   unsigned char* base = (unsigned char*)dst;
   std::memset(base, 0, total);
   std::memcpy(base, & h, sizeof(h));
