@@ -143,9 +143,18 @@ int  llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq);
  * over the link (llsm_synthesize{,_batch} do so internally). */
 void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noise, long long n);
 
-/* Diagnosis only: an intermediate plane of the batch's last analysis, [total_frames][nfft_psd / 2 + 1] float32 --
+/* Diagnosis only: an intermediate plane of the batch, float32.
  * which = 0: the log envelope behind the Kalman process variance (layer0.c:339-343), 1: the log periodogram of the
- * residual (layer0.c:354-360).  dst == NULL: only the size.  Returns the number of floats, -1 on error. */
+ * residual (layer0.c:354-360); both [total_frames][nfft_psd / 2 + 1], of the last analysis.
+ * which = 2: the squared band signals of the last analysis (llsm_subband_energy of x_res, or of x for a channel that
+ * starts above 6 kHz; layer0.c:440), [nchannel][total_samples].
+ * which = 3: the band-limited noise templates of the last synthesis (dsputils.c:385-394), [n_utt][nchannel][ntemplate_ext];
+ * utterance u uses the first min(20000, ny[u]) + 128 samples of a row, and the rows of channels that start at or above
+ * the synthesis Nyquist are never written (layer0.c:562 leaves such a channel out).
+ * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
+ * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
+ * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
+ * dst == NULL: only the size.  Returns the number of floats, -1 on error. */
 long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap);
 
 /* Page-locked host buffers for the copies below (optional: any host pointer works, but
@@ -552,7 +561,14 @@ void llsm_gpu_set_default_seed(unsigned long long seed);
  * utterance gets the same bits in every batch.  14 frames per unit of the
  * harmonic overlap-add for a one-utterance batch of i frames, maxnhar j.
  * 15 first output sample of unit j of the noise excitation in an utterance of
- * i samples, -1 past its last unit. */
+ * i samples, -1 past its last unit.  16 how the zero-phase band filter treats
+ * a signal of i samples in the band [f0, thop] Hz (the two arguments carry
+ * fmin and fmax) at fs; j selects: 0 M, the samples each end job of a fused
+ * band-pass writes, and 1 M' = 2 M + 64, the stretch it filters (0: the band
+ * is a single low- or high-pass); 2 whether i samples run fused (i >= 4 M');
+ * 3 the halo of a time segment; 4 the number of time segments; 5 and 6 the
+ * range [lo, hi) the main job or its segments write ([M, i - M) when fused);
+ * 100 + s the first sample segment s writes.  -1: no such quantity. */
 int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE thop,
   FP_TYPE fs, FP_TYPE rel_winsize);
 

@@ -610,13 +610,21 @@ extern "C" int llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq) {
   b -> fnyq = fnyq;
   return 0;
 }
-// Intermediate planes of the last analysis, for diagnosis (tools/psd_bisect.py --product): which = 0 the log envelope that
-// sets the Kalman process variance, 1 the log periodogram of the residual; both [total_frames][nspec_psd] float32.
-// dst == NULL: only the size.  Returns the number of floats of the plane, -1 without one.
+// Intermediate planes of the batch, for diagnosis (tools/psd_bisect.py --product, tests/test_gpu_filtfilt_samples.py):
+// which = 0 the log envelope that sets the Kalman process variance, 1 the log periodogram of the residual, both
+// [total_frames][nspec_psd] float32, of the last analysis; 2 the squared band signals of the last analysis (ce),
+// [nchannel][total_samples]; 3 the band-limited templates of the last synthesis (colored),
+// [n_utt][nchannel][ntemplate_ext], rows of channels from Nyquist up never written.  The later stages of analyze /
+// synthesize only read ce and colored, and no other call touches them: both hold the band filter's output until the next
+// analyze / synthesize of this batch.  dst == NULL: only the size.  Returns the number of floats of the plane, -1 without one.
 extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap) {
-  if(! b || (which != 0 && which != 1)) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
-  DevBuf<float>& src = which == 0 ? b -> env : b -> psd_log;
-  const long long n = (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1);
+  if(! b || which < 0 || which > 3) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
+  DevBuf<float>& src = which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : b -> colored;
+  const long long n = which <= 1 ? (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1) :
+                      which == 2 ? (long long)b -> lay.nchannel * b -> lay.total_samples :
+                                   (long long)b -> lay.n_utt * b -> lay.nchannel * b -> lay.ntemplate_ext;
+  if(which == 2 && ! b -> ce_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has filtered the bands of this batch"); return -1; }
+  if(which == 3 && ! b -> colored_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no synthesis has filtered the templates of this batch"); return -1; }
   if(! src.p || n <= 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has run on this batch"); return -1; }
   if(dst) {
     if(cap < n) { llsm_set_error("llsm_gpu_batch_debug_plane: destination too small"); return -1; }
@@ -898,6 +906,60 @@ static int filt_segments(int n, int w, int H) {
   return std::max(1, std::min(w / std::max(2048, 6 * H), 64));
 }
 
+// ... with the experiment switches of $LLSM_GPU_FILT_SEGMENTS: 0 no cut, N > 1 that many segments for every job long enough
+static int filt_job_segments(int n, int w, int H) {
+  static const bool seg_ok = [] { const char* e = std::getenv("LLSM_GPU_FILT_SEGMENTS"); return !(e && e[0] == '0'); }();
+  static const int seg_force = [] { const char* e = std::getenv("LLSM_GPU_FILT_SEGMENTS"); const int v = e ? std::atoi(e) : 0; return v > 1 ? v : 0; }();
+  int S = seg_ok ? filt_segments(n, w, H) : 1;
+  if(seg_force && H > 0 && w / std::max(2048, 6 * H) >= seg_force) S = seg_force;
+  return S;
+}
+// first sample segment sg of S writes, of an interior [lo, hi)
+static int filt_segment_start(int lo, int hi, int sg, int S) { return lo + (int)((long long)(hi - lo) * sg / S); }
+static bool filt_fuse_ok() {
+  static const bool ok = [] { const char* e = std::getenv("LLSM_GPU_FILT_FUSE"); return !(e && e[0] == '0'); }();
+  return ok;
+}
+// (M, M') of the fused band-pass of a two-section chain: M = the reach of the slower section's poles to 1e-9, in whole
+// groups of 32 samples; M' = 2 M + 64 = the stretch an end job filters to write its M samples
+static void filt_fused_geometry(float cut0, bool hp0, float cut1, bool hp1, int* M, int* Mp) {
+  const llsm_cheby::Section s0 = llsm_cheby::make_section_row(llsm_cheby::row_of(cut0), hp0);
+  const llsm_cheby::Section s1 = llsm_cheby::make_section_row(llsm_cheby::row_of(cut1), hp1);
+  const int L = std::max(decay_length(s0.a, 1e-9), decay_length(s1.a, 1e-9));
+  *M = (L + 31) & ~31; *Mp = 2 * *M + 64;
+}
+static int filt_section_reach(float cut, bool hp) { return decay_length(llsm_cheby::make_section_row(llsm_cheby::row_of(cut), hp).a, 1e-9); }
+static int filt_halo(int reach) { return reach > 0 ? ((reach + 31) & ~31) + 64 : 0; }
+
+// What build_jobs does with a signal of n samples in the band [fmin, fmax] Hz at fs (llsm_gpu_plan_index case 16), by
+// the same functions: q = 0 M and 1 M' of the fused band-pass (0: the band is one section), 2 whether n samples are
+// filtered fused (n >= 4 M'), 3 the halo H of a time segment, 4 the number of time segments S, 5 / 6 the interior
+// [lo, hi) the main job -- or its segments together -- write (fused: [M, n - M), the end jobs write the rest),
+// 100 + s the first sample segment s writes (s = S: hi).  -1: no such quantity.
+static int filt_plan_query(int n, int q, float fmin, float fmax, float fs) {
+  float c1 = fmin / fs, c2 = fmax / fs;                // channel_chain's arithmetic
+  if(c1 < 0) c1 = 0;
+  if(c2 > 0.5f) c2 = 0.5f;
+  const bool two = c1 != 0 && c2 < 0.5f;
+  int M = 0, Mp = 0;
+  if(two && filt_fuse_ok()) filt_fused_geometry(c1, true, c2, false, & M, & Mp);
+  const bool fused = two && M > 0 && n >= 4 * Mp;
+  const int reach = two ? (fused ? M : 0) : (c1 == 0 ? filt_section_reach(c2, false) : filt_section_reach(c1, true));
+  const int H = filt_halo(reach), lo = fused ? M : 0, hi = fused ? n - M : n;
+  const int S = (two && ! fused) ? 1 : filt_job_segments(n, hi - lo, H);
+  switch(q) {
+    case 0: return M;
+    case 1: return Mp;
+    case 2: return fused ? 1 : 0;
+    case 3: return H;
+    case 4: return S;
+    case 5: return lo;
+    case 6: return hi;
+  }
+  if(q >= 100 && q <= 100 + S) return filt_segment_start(lo, hi, q - 100, S);
+  return -1;
+}
+
 static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
   const float* white) {
   const int U = b -> lay.n_utt, nch = b -> lay.nchannel;
@@ -914,16 +976,12 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
   std::vector<size_t> seg_tmp_off;                       // tmp offsets of the segment jobs inside iir_seg[which], by job index
   std::vector<int> seg_job;                              // ... and which entries of `jobs` they are
   size_t seg_need = 0;
-  static const bool seg_ok = [] { const char* e = std::getenv("LLSM_GPU_FILT_SEGMENTS"); return !(e && e[0] == '0'); }();
-  static const int seg_force = [] { const char* e = std::getenv("LLSM_GPU_FILT_SEGMENTS"); const int v = e ? std::atoi(e) : 0; return v > 1 ? v : 0; }();   // experiment: this many segments for every job
   auto push_job = [&](const FiltJob& j, int H) {
     const int lo = j.whi > j.wlo ? j.wlo : 0, hi = j.whi > j.wlo ? j.whi : j.n;
-    int S = 1;
-    if(seg_ok && !(j.sec1 >= 0 && ! j.fused)) S = filt_segments(j.n, hi - lo, H);
-    if(seg_force && H > 0 && !(j.sec1 >= 0 && ! j.fused) && (hi - lo) / std::max(2048, 6 * H) >= seg_force) S = seg_force;
+    const int S = (j.sec1 >= 0 && ! j.fused) ? 1 : filt_job_segments(j.n, hi - lo, H);
     if(S <= 1) { jobs.push_back(j); return; }
     for(int sg = 0; sg < S; sg ++) {
-      const int w0 = lo + (int)((long long)(hi - lo) * sg / S), w1 = lo + (int)((long long)(hi - lo) * (sg + 1) / S);
+      const int w0 = filt_segment_start(lo, hi, sg, S), w1 = filt_segment_start(lo, hi, sg + 1, S);
       const int a0 = std::max(0, w0 - H), a1 = std::min(j.n, w1 + H);
       FiltJob e = j;
       e.src = j.src + a0; e.dst = j.dst + a0; e.n = a1 - a0; e.wlo = w0 - a0; e.whi = w1 - a0;
@@ -932,17 +990,14 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
       jobs.push_back(e);
     }
   };
-  static const bool fuse_ok = [] { const char* e = std::getenv("LLSM_GPU_FILT_FUSE"); return !(e && e[0] == '0'); }();
+  const bool fuse_ok = filt_fuse_ok();
   // scratch of the short end jobs of fused band-pass jobs (below): sized in a first pass over the channels
   size_t edge_need = 0;
   std::vector<int> edge_M(nch, 0), edge_Mp(nch, 0);
   for(int c = 0; c < nch && fuse_ok; c ++) {
     bool hp0 = false, hp1 = false, from_x = false; float cut0 = 0, cut1 = 0;
     if(channel_chain(b, fs, c, & hp0, & cut0, & hp1, & cut1, & from_x) != 2) continue;
-    const llsm_cheby::Section s0 = llsm_cheby::make_section_row(llsm_cheby::row_of(cut0), hp0);
-    const llsm_cheby::Section s1 = llsm_cheby::make_section_row(llsm_cheby::row_of(cut1), hp1);
-    const int L = std::max(decay_length(s0.a, 1e-9), decay_length(s1.a, 1e-9));
-    edge_M[c] = (L + 31) & ~31; edge_Mp[c] = 2 * edge_M[c] + 64;
+    filt_fused_geometry(cut0, hp0, cut1, hp1, & edge_M[c], & edge_Mp[c]);
     edge_need += (size_t)U * 2 * (2 * (size_t)edge_Mp[c] + 32);
   }
   DevBuf<float>& edge_buf = b -> iir_edge[which];       // one per stage: the job tables keep pointers into it
@@ -983,7 +1038,7 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
       // M = the reach of the slowest pole to 1e-9 (k_filtfilt; measured against scipy: identical to 1e-13 beyond M)
       const int M = edge_M[c], Mp = edge_Mp[c];
       int reach = 0;                                      // of this job's slowest pole (0: not a job that is cut into segments)
-      if(ns == 1) reach = decay_length(llsm_cheby::make_section_row(llsm_cheby::row_of(cut0), hp0).a, 1e-9);
+      if(ns == 1) reach = filt_section_reach(cut0, hp0);
       if(ns == 2 && M > 0 && j.n >= 4 * Mp) {
         reach = M;
         j.fused = 1; j.wlo = M; j.whi = j.n - M;
@@ -997,7 +1052,7 @@ static int build_jobs(llsm_gpu_batch* b, int which, float fs, const float* xres,
           edge_jobs.push_back(e);
         }
       }
-      push_job(j, reach > 0 ? ((reach + 31) & ~31) + 64 : 0);
+      push_job(j, filt_halo(reach));
     }
   }
   if(tmp_off > b -> iir_tmp.n || edge_off > edge_buf.n) { llsm_set_error("internal: IIR scratch too small"); return -1; }
@@ -1213,6 +1268,7 @@ extern "C" int llsm_gpu_batch_analyze(llsm_gpu_batch* b) {
   }
   if(! forked) RUN(launch_kalman(P, d, b -> env.p, b -> psd_log.p, b -> pbuf.p, (int)nspec));
   RUN(launch_filtfilt(P, b -> jobs_ana.p, b -> njobs_ana, b -> sections.p));
+  b -> ce_filled = true;
   RUN(launch_harm_env(P, d, b -> ce.p, X));          // edc for every frame (+ CZT envelopes)
   if(hmpp && L.maxnhar_e > 0)                         // HMPP: envelopes by peak picking instead
     if(run_harm_pp(c, P, d, b, b -> ce.p, X, L.nchannel, L.maxnhar_e, pp_lds_n, pp_nmax, d.nhar_e, d.eenv_ampl, d.eenv_phse)) return -1;
@@ -1384,6 +1440,7 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
   float* ysin = (float*)b -> arr[LLSM_GPU_YSIN];
   if(! use_injected_white) RUN(launch_white(P, d, white, L.ntemplate_ext, b -> d_ny.p, seed));
   RUN(launch_filtfilt(P, b -> jobs_syn.p, b -> njobs_syn, b -> sections.p));
+  b -> colored_filled = true;
   // noise excitation: persistent units (k_excite_units) where the geometry allows and $LLSM_GPU_EXCITE4 is unset; set,
   // it selects the per-sample kernel after k_env_params
   const char* e4 = std::getenv("LLSM_GPU_EXCITE4");   // (read per call: tests switch it)
@@ -1542,6 +1599,7 @@ extern "C" int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE 
     case 13: return filt_segments(i, i, j);
     case 14: return sin_unit_frames(i, i, lp::nwin_sin(thop, fs), j);
     case 15: return excite_unit_start(i, excite_unit_samples(), j);
+    case 16: return filt_plan_query(i, j, f0, thop, fs);
   }
   return -1;
 }
