@@ -273,6 +273,44 @@ int  llsm_gpu_batch_phasepropagate(llsm_gpu_batch* b, int sign);
 int  llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* src, const FP_TYPE* pos, const int* psdres_src);
 void llsm_gpu_retime_uniform_positions(int nfrm_src, int nfrm_dst, FP_TYPE* pos);
 
+/* ---- splice: a gather of frames across the utterances of another batch with a two-sided blend -- retiming, unit selection,
+ * concatenation with cross-fades and morphing between two voices from index lists, without leaving the device.
+ * Asynchronous on the context's stream; a refused call returns -1, sets llsm_gpu_last_error() (the message starts with
+ * "llsm_gpu_batch_splice:" and names the frame at fault) and writes and launches nothing.
+ *
+ * src and dst share options, sampling rate, channel frequencies and context, as for retime; their utterance counts may
+ * differ.  src has layer 1 and is only read.  dst gets layer 1 with src's nfft, takes over src's fnyq and maxnhar_conf,
+ * and its lowest-F0 bound becomes unknown.  All arrays of the map are host arrays of dst.total_frames entries in dst's
+ * flat frame order.
+ *
+ * With S[u][i] frame i of utterance u of src and P(fa, fb, r) the pair rule of retime above (r == 0: a bit-exact copy of
+ * fa, r == 1: of fb, otherwise the both-voiced / one-voiced / neither rules with fa in the place of frame a), output
+ * frame g is
+ *     A = P(S[ua][a], S[ua][a + 1], ra)   ua = utt_a[g], and a = min(floor(t), n - 2), ra = t - a (float32) from
+ *                                         t = pos_a[g] and the n frames of utterance ua, as retime forms them (n == 1: S[ua][0])
+ *     B = the same from utt_b[g], pos_b[g]
+ *     out = P(A, B, mix[g])
+ *   so mix[g] == 0, or a map without a second side, gives A bit for bit -- AMPL, PHSE, NHAR and HAS_HM of an exactly copied
+ *   frame included -- and mix[g] == 1 gives B bit for bit; a side the output does not use is not read.  In between, A and B
+ *   enter P as the frames retime would have written for them (voiced blends with NHAR = 0, HAS_HM = 0 and zero AMPL /
+ *   PHSE rows, NVSPHSE and NHAR_E clamped to the row widths).
+ *   PSDRES and HAS_PSDRES are those of source frame min(floor(pos_a[g]), n - 1) of utt_a[g] when there is no second side
+ *   or mix[g] < 0.5, else of the corresponding frame of utt_b[g].
+ *   Per-frame effects are not carried over.  An output frame depends on its own map entries and the at most four source
+ *   frames they name, not on its place in dst nor on anything else in either batch.
+ * Refused: a NULL batch or map; pos_a NULL; a second side given in part; src == dst; different contexts, options or
+ * sampling rates; src without layer 1; dst with layer 1 of another size; utt_a NULL while dst has more utterances than
+ * src; an utterance index outside src; a named utterance without frames; a position that is NaN or outside
+ * [0, nfrm - 1] of its utterance; a mix that is NaN or outside [0, 1].  A dst without frames returns 0. */
+typedef struct {
+  const int*     utt_a;  /* dst.total_frames source-utterance indices; NULL: the output frame's own utterance index */
+  const FP_TYPE* pos_a;  /* dst.total_frames positions, in frames of utterance utt_a; required */
+  const int*     utt_b;  /* the second side; utt_b, pos_b and mix are all NULL or all given */
+  const FP_TYPE* pos_b;
+  const FP_TYPE* mix;    /* weight of side b, in [0, 1] */
+} llsm_gpu_splice_map;
+int llsm_gpu_batch_splice(llsm_gpu_batch* dst, const llsm_gpu_batch* src, const llsm_gpu_splice_map* map);
+
 /* ---- pitch and formant edit of a device-resident layer-1 batch: the middle of the reference's pitch-shift recipe
  * (analyse, tolayer1, phasepropagate(-1), F0 *= ratio and VTMAGN -= 20 log10(ratio) with HM dropped, tolayer0,
  * phasepropagate(+1), synthesise), with an optional formant warp of VTMAGN and PSD.  Asynchronous; a refused call returns

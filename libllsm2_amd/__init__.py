@@ -71,6 +71,10 @@ class FlatL1(C.Structure):
                 ("vsphse", P_fp), ("nvsphse", P_int), ("pbpsyn", P_int), ("has_hm", P_int)]
 
 
+class SpliceMap(C.Structure):                              # llsm_gpu_splice_map
+    _fields_ = [("utt_a", P_int), ("pos_a", P_fp), ("utt_b", P_int), ("pos_b", P_fp), ("mix", P_fp)]
+
+
 # frame / conf member indices (llsm.h)
 FRAME_F0, FRAME_HM, FRAME_NM, FRAME_PSDRES = 0, 1, 2, 3
 FRAME_PBPEFF, FRAME_PBPSYN, FRAME_RD, FRAME_VTMAGN, FRAME_VSPHSE = 8, 9, 10, 11, 12
@@ -129,7 +133,7 @@ llsm_chunk_blob_size llsm_chunk_to_blob llsm_blob_view llsm_blob_to_chunk llsm_b
 llsm_create_rtsynth_group llsm_delete_rtsynth_group llsm_rtsynth_group_getlatency
 llsm_rtsynth_group_numoutput llsm_rtsynth_group_feed llsm_rtsynth_group_feed_many llsm_rtsynth_group_fetch llsm_rtsynth_group_fetch_all llsm_gpu_rt_graph llsm_gpu_rt_graph_hops llsm_gpu_rt_fused llsm_gpu_rt_direct llsm_gpu_rt_pipeline llsm_gpu_analysis_overlap llsm_slab_stats llsm_slab_trim llsm_delete_chunks llsm_gpu_release_cached_batches llsm_gpu_device_numa_node llsm_gpu_bind_thread_to_device llsm_gpu_batch_packed_words llsm_gpu_batch_download_packed llsm_gpu_batch_upload_packed llsm_gpu_batch_download_outputs llsm_gpu_batch_download_packed_block llsm_gpu_batch_upload_packed_block llsm_gpu_batch_transfer_many llsm_gpu_batch_params_layout llsm_gpu_batch_transfer_params llsm_gpu_shared_f0_tiles llsm_gpu_synth_tables llsm_gpu_pbp_real_ifft llsm_frame_compute_snr
 llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime llsm_gpu_retime_uniform_positions
-llsm_gpu_batch_pitch_formant
+llsm_gpu_batch_pitch_formant llsm_gpu_batch_splice
 llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode llsm_gpu_batch_decode
 llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu_batch_download_blob_block
 """.split()
@@ -193,6 +197,7 @@ def load():
     L.llsm_gpu_retime_uniform_positions.argtypes = [C.c_int, C.c_int, P_fp]
     L.llsm_gpu_retime_uniform_positions.restype = None
     L.llsm_gpu_batch_pitch_formant.argtypes = [vp, P_fp, P_fp, C.c_int]
+    L.llsm_gpu_batch_splice.argtypes = [vp, vp, C.POINTER(SpliceMap)]
     try:                                                 # (as above: an experiment build of an earlier commit lacks the coder)
         L.llsm_gpu_batch_enable_coder.argtypes = [vp, C.c_int, C.c_int]
         L.llsm_gpu_batch_coder_dimension.argtypes = [vp]
@@ -521,6 +526,25 @@ class Batch:
             assert r.shape == (self.layout.total_frames,), r.shape
         _check(self.L.llsm_gpu_batch_retime(self.h, src.h, None if p is None else p.ctypes.data_as(P_fp),
                                             None if r is None else r.ctypes.data_as(P_int)), "retime")
+        self.nspec = src.nspec
+
+    def splice(self, src, pos_a, utt_a=None, utt_b=None, pos_b=None, mix=None):
+        """this batch's rows <- frames gathered from any utterances of batch `src` and blended between two sides
+        (llsm_gpu_batch_splice); every argument is None or total_frames values in this batch's frame order: pos_a / pos_b
+        float32 positions in frames of utterance utt_a / utt_b (utt_a None: the output frame's own utterance), mix the
+        weight of side b; utt_b, pos_b and mix go together"""
+        F = self.layout.total_frames
+
+        def arr(v, dt):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dt)
+            assert v.shape == (F,), v.shape
+            return v
+        keep = [arr(utt_a, np.int32), arr(pos_a, np.float32), arr(utt_b, np.int32), arr(pos_b, np.float32),
+                arr(mix, np.float32)]
+        m = SpliceMap(*[None if v is None else v.ctypes.data_as(P_int if v.dtype == np.int32 else P_fp) for v in keep])
+        _check(self.L.llsm_gpu_batch_splice(self.h, src.h, C.byref(m)), "splice")
         self.nspec = src.nspec
 
     def pitch_formant(self, f0_ratio=None, formant_ratio=None, warp_psd=False):

@@ -286,6 +286,11 @@ int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int l
 int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, const int* nfrm, const float* f0,
   double k2pi, float* theta);
 int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m);
+// Map of llsm_gpu_batch_splice with the utterances resolved on the host: side A of output frame g is the pair rule of retime
+// on src's frames ga[g] and ga[g] + 1 (flat frame indices) at weight ra[g] -- the second is read only where ra[g] != 0 --,
+// side B the same of gb / rb, and the output the pair rule on (A, B) at weight mix[g].  gb, rb and mix NULL: side A alone.
+struct SpliceMap { const int* ga; const float* ra; const int* gb; const float* rb; const float* mix; };
+int launch_splice(LaunchCtx* P, const ModRows& src, const ModRows& dst, const SpliceMap& m);
 // llsm_gpu_batch_pitch_formant over frames [g_lo, g_hi) (every edited frame): rho / alpha are per-frame F0 and formant
 // ratios (NULL: 1), warp_psd the PSD warp; LDS: 16 (nspec + npsd) bytes per workgroup
 int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, const float* rho, const float* alpha,

@@ -5,6 +5,8 @@
 //   llsm_gpu_batch_retime            the frame-blending step of the reference's time-stretch recipe, onto the frame grid
 //                                    of another batch (rules: llsm_gpu.h)
 //   llsm_gpu_retime_uniform_positions  the map retime uses when it is given none
+//   llsm_gpu_batch_splice            retime's pair rule across utterances and between two sides: unit selection, joins with
+//                                    cross-fades and morphs from index lists (rules: llsm_gpu.h)
 //   llsm_gpu_batch_pitch_formant     F0 and formant ratios per frame on a layer-1 batch, the edit of the reference's
 //                                    pitch-shift recipe (rules: llsm_gpu.h)
 #include <hip/hip_runtime.h>
@@ -117,6 +119,94 @@ extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* 
   m.src_off = src -> d_frm_off.p; m.src_nfrm = src -> d_nfrm.p;
   const int rc = launch_retime(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
   return rc ? launch_failed("llsm_gpu_batch_retime", rc) : 0;
+}
+
+namespace {
+int refuse_sp(const std::string& why) { llsm_set_error("llsm_gpu_batch_splice: " + why); return -1; }
+
+// One side of a splice map resolved into `ga` (flat source frame a) and `r`, formed from the position exactly as k_retime
+// forms them; utt NULL: the output frame's own utterance.  Returns false (error set) at the first bad entry.
+bool stage_side(const llsm_gpu_batch* src, const llsm_gpu_batch* dst, const char* side, const int* utt, const float* pos,
+  int* ga, float* r) {
+  const int n_src = src -> lay.n_utt;
+  for(int u = 0; u < dst -> lay.n_utt; u ++)
+    for(int g = dst -> frm_off[u]; g < dst -> frm_off[u] + dst -> nfrm[u]; g ++) {
+      const int v = utt ? utt[g] : u;
+      const std::string where = std::string(side) + "[" + std::to_string(g) + "]";
+      if(v < 0 || v >= n_src) {
+        refuse_sp("utt_" + where + " = " + std::to_string(v) + " is not an utterance of src (" + std::to_string(n_src) + ")");
+        return false;
+      }
+      const int n = src -> nfrm[v];
+      if(n == 0) { refuse_sp("utt_" + where + " = " + std::to_string(v) + " names an utterance without frames"); return false; }
+      const float t = pos[g];
+      if(!(t >= 0.0f && t <= (float)(n - 1))) {
+        refuse_sp("pos_" + where + " (utterance " + std::to_string(v) + ") is NaN or outside [0, " + std::to_string(n - 1) + "]");
+        return false;
+      }
+      int a = 0; float ra = 0;
+      if(n > 1) { const int fl = (int)std::floor(t); a = fl < n - 2 ? fl : n - 2; ra = t - (float)a; }
+      ga[g] = src -> frm_off[v] + a; r[g] = ra;
+    }
+  return true;
+}
+}  // namespace
+
+extern "C" int llsm_gpu_batch_splice(llsm_gpu_batch* dst, const llsm_gpu_batch* src_c, const llsm_gpu_splice_map* map) {
+  llsm_gpu_batch* src = const_cast<llsm_gpu_batch*>(src_c);         // read only: the rows are not changed
+  if(! dst || ! src) return refuse_sp("NULL batch");
+  if(! map) return refuse_sp("NULL map");
+  if(! map -> pos_a) return refuse_sp("pos_a is NULL");
+  const bool two = map -> utt_b || map -> pos_b || map -> mix;
+  if(two && !(map -> utt_b && map -> pos_b && map -> mix))
+    return refuse_sp("the second side is given in part: utt_b, pos_b and mix are all NULL or all given");
+  if(src == dst) return refuse_sp("src and dst are the same batch");
+  if(src -> ctx != dst -> ctx) return refuse_sp("the two batches are on different contexts");
+  const llsm_aoptions& a = src -> opt; const llsm_aoptions& d = dst -> opt;
+  if(a.thop != d.thop || src -> fs != dst -> fs || a.nchannel != d.nchannel || a.npsd != d.npsd || a.maxnhar != d.maxnhar ||
+     a.maxnhar_e != d.maxnhar_e || src -> chanfreq != dst -> chanfreq)
+    return refuse_sp("the batches were created with different options or sampling rates");
+  if(src -> l1_nspec == 0) return refuse_sp("src has no layer 1 (llsm_gpu_batch_tolayer1)");
+  if(dst -> l1_nspec != 0 && dst -> l1_nspec != src -> l1_nspec) return refuse_sp("dst has layer 1 enabled with another size");
+  if(! map -> utt_a && dst -> lay.n_utt > src -> lay.n_utt)
+    return refuse_sp("utt_a is NULL and dst holds more utterances (" + std::to_string(dst -> lay.n_utt) + ") than src (" +
+      std::to_string(src -> lay.n_utt) + ")");
+  // the map: checked and resolved on the host, then staged in page-locked memory ([ga | ra] and, with a second side,
+  // [gb | rb | mix], Fd words each)
+  const int Fd = dst -> lay.total_frames;
+  const size_t words = (two ? 5 : 2) * (size_t)Fd;
+  if(dst -> mod_ev) HIP_OK(hipEventSynchronize(dst -> mod_ev));    // the previous call's copy has left the stage
+  if(! dst -> mod_stage.resize(words + 1)) return -1;
+  int* h = dst -> mod_stage.data();
+  if(! stage_side(src, dst, "a", map -> utt_a, map -> pos_a, h, (float*)h + Fd)) return -1;
+  if(two) {
+    if(! stage_side(src, dst, "b", map -> utt_b, map -> pos_b, h + 2 * (size_t)Fd, (float*)h + 3 * (size_t)Fd)) return -1;
+    float* hmix = (float*)h + 4 * (size_t)Fd;
+    for(int g = 0; g < Fd; g ++) {
+      const float w = map -> mix[g];
+      if(!(w >= 0.0f && w <= 1.0f)) return refuse_sp("mix[" + std::to_string(g) + "] is NaN or outside [0, 1]");
+      hmix[g] = w;
+    }
+  }
+  // accepted: from here on dst changes
+  hipSetDevice(dst -> ctx -> device);
+  if(llsm_gpu_batch_enable_layer1(dst, (src -> l1_nspec - 1) * 2)) return -1;
+  dst -> fnyq = src -> fnyq;
+  dst -> maxnhar_conf = src -> maxnhar_conf;
+  dst -> min_f0 = 0; dst -> f0_unknown = true;           // the F0 row is written on the device
+  if(Fd == 0) return 0;
+  hipStream_t st = dst -> ctx -> stream;
+  if(dst -> mod_splice.alloc(words)) return -1;
+  int* dm = dst -> mod_splice.p;
+  HIP_OK(hipMemcpyAsync(dm, h, words * sizeof(int), hipMemcpyHostToDevice, st));
+  if(! dst -> mod_ev) HIP_OK(hipEventCreateWithFlags(& dst -> mod_ev, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(dst -> mod_ev, st));
+  SpliceMap m;
+  m.ga = dm; m.ra = (const float*)dm + Fd;
+  m.gb = two ? dm + 2 * (size_t)Fd : nullptr; m.rb = two ? (const float*)dm + 3 * (size_t)Fd : nullptr;
+  m.mix = two ? (const float*)dm + 4 * (size_t)Fd : nullptr;
+  const int rc = launch_splice(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
+  return rc ? launch_failed("llsm_gpu_batch_splice", rc) : 0;
 }
 
 namespace {

@@ -9,6 +9,10 @@
 //   k_pitch_formant F0 scaling, VTMAGN amplitude compensation and formant warp (VTMAGN, optionally PSD) of
 //                   llsm_gpu_batch_pitch_formant; four consecutive frames per 256-thread workgroup, rows staged in LDS with
 //                   16-byte accesses, the warp a gather from LDS
+//   k_splice        llsm_gpu_batch_splice: every output frame is the pair rule of k_retime applied to two frames that are
+//                   themselves pair-rule blends of frames of any utterance of another batch; four consecutive output frames
+//                   per 256-thread workgroup, 16-byte stores, 16-byte loads at the source's own alignment, only the frames'
+//                   scalars in LDS
 //
 // No `#pragma clang fp contract(fast)` here: the phase kernels reproduce the host's float64 arithmetic bit for bit and the
 // blends are x_a + (x_b - x_a) r without contraction (the library is built with -ffp-contract=off).
@@ -43,6 +47,10 @@ DEV float lin(float a, float b, float r) { return a + (b - a) * r; }
 DEV float circ(float pa, float pb, float r) {
   return atan2f(lin(sinf(pa), sinf(pb), r), lin(cosf(pa), cosf(pb), r));
 }
+// the per-element pieces of the pair rule that k_retime and k_splice share: the -80 dB floor of VTMAGN and the fade of the
+// voiced side of a voicing change by the weight w
+DEV float floor80(float x) { return fmaxf(x, -80.0f); }
+DEV float fade_db(float w) { return 20.0f * log10f(fmaxf(1e-8f, w)); }
 DEV void copy_row(float* __restrict__ d, const float* __restrict__ s, int n, int lane) {
   for(int k = lane; k < n; k += 64) d[k] = s[k];
 }
@@ -64,6 +72,125 @@ DEV void pf_stage(float* __restrict__ d, const float* __restrict__ s, int n, int
   const int n4 = n >> 2;
   for(int q = tid; q < n4; q += kPfThreads) ((float4*)d)[q] = ((const float4*)s)[q];
   for(int e = (n4 << 2) + tid; e < n; e += kPfThreads) d[e] = s[e];
+}
+// k_splice: a workgroup takes output frames g0 .. g0 + 3 with g0 a multiple of 4 (k_pitch_formant's shape), so its spans
+// of VTMAGN, PSD, PSDRES, AMPL, PHSE and VSPHSE start on a 16-byte boundary and are stored as float4.  The source rows sit
+// wherever their frame index leaves them: they are read 16 bytes at float alignment (k_blob_pack's F4U), and as single
+// floats where four output elements straddle two frames.
+const int kSpFrames = 4, kSpThreads = 256;
+
+struct __attribute__((packed, aligned(4))) SpF4U { float x, y, z, w; };     // 16 bytes at float alignment
+template <int N> struct SpVec { float v[N]; };
+// circ as ONE function of k_splice: inlined at each of its uses (both levels, both row kinds, both widths) the kernel was
+// 126 KB of code, twice the instruction cache; the arithmetic and its bits are those of circ
+__device__ __attribute__((noinline)) float sp_circ(float pa, float pb, float r) { return circ(pa, pb, r); }
+template <int N> DEV SpVec<N> sp_ld(const float* p);
+template <> DEV SpVec<1> sp_ld<1>(const float* p) { SpVec<1> o; o.v[0] = p[0]; return o; }
+template <> DEV SpVec<4> sp_ld<4>(const float* p) {
+  const SpF4U t = *(const SpF4U*)p;
+  SpVec<4> o; o.v[0] = t.x; o.v[1] = t.y; o.v[2] = t.z; o.v[3] = t.w; return o;
+}
+
+// the scalars of one frame, stored or blended
+struct SpScal { float f0, rd; int nv, ne, nhar, has_hm, pbpsyn; };
+DEV SpScal sp_scal(const ModRows& s, size_t g) {
+  SpScal o;
+  o.f0 = s.f0[g]; o.rd = s.rd[g]; o.nv = s.nvsphse[g]; o.ne = s.nhar_e[g]; o.nhar = s.nhar[g]; o.has_hm = s.has_hm[g];
+  o.pbpsyn = s.pbpsyn[g];
+  return o;
+}
+// The pair rule P(A, B, r) of llsm_gpu_batch_retime as one plan per frame pair: which case applies and the counts its rows
+// need.  SP_VU: A is the voiced frame of a voicing change, SP_UV: B is.
+enum { SP_COPY_A, SP_COPY_B, SP_VV, SP_VU, SP_UV, SP_UU };
+struct SpPair { int mode; float r, fade; int nvmin, vlong, nemin, elong; };   // vlong / elong: the longer row is B's
+// plan and resulting scalars of P(A, B, r), as k_retime forms them (B is not looked at when r == 0, nor A when r == 1)
+DEV void sp_pair(const SpScal& A, const SpScal& B, float r, int mh, int mne, SpPair* p, SpScal* o) {
+  p -> r = r; p -> fade = 0.0f; p -> nvmin = p -> vlong = p -> nemin = p -> elong = 0;
+  if(r == 0.0f) { p -> mode = SP_COPY_A; *o = A; return; }
+  if(r == 1.0f) { p -> mode = SP_COPY_B; *o = B; return; }
+  const bool va = A.f0 > 0.0f, vb = B.f0 > 0.0f;
+  const int nva = clampi(A.nv, 0, mh), nvb = clampi(B.nv, 0, mh);
+  const int nea = clampi(A.ne, 0, mne), neb = clampi(B.ne, 0, mne);
+  p -> nvmin = min(nva, nvb); p -> vlong = nva >= nvb ? 0 : 1;
+  p -> nemin = min(nea, neb); p -> elong = nea >= neb ? 0 : 1;
+  if(va && vb) {
+    p -> mode = SP_VV; o -> f0 = lin(A.f0, B.f0, r); o -> rd = lin(A.rd, B.rd, r); o -> nv = max(nva, nvb);
+  } else if(va || vb) {
+    p -> mode = va ? SP_VU : SP_UV; p -> fade = fade_db(va ? 1.0f - r : r);
+    o -> f0 = va ? A.f0 : B.f0; o -> rd = va ? A.rd : B.rd; o -> nv = va ? nva : nvb;
+  } else {
+    p -> mode = SP_UU; o -> f0 = 0.0f; o -> rd = 1.0f; o -> nv = nva;
+  }
+  const bool voiced = va || vb;
+  o -> ne = max(nea, neb); o -> pbpsyn = A.pbpsyn;
+  o -> nhar = voiced ? 0 : A.nhar; o -> has_hm = voiced ? 0 : A.has_hm;
+}
+
+// the kinds of rows: VTMAGN; VSPHSE; PSD and EDC; EENV_AMPL; EENV_PHSE; AMPL and PHSE; PSDRES
+enum { SP_VT, SP_VS, SP_LIN, SP_EA, SP_EP, SP_HM, SP_RES };
+template <int ROW> DEV bool sp_needs_a(int m) {
+  if(ROW == SP_VT || ROW == SP_VS) return m != SP_COPY_B && m != SP_UV;
+  if(ROW == SP_HM) return m == SP_COPY_A || m == SP_UU;
+  return m != SP_COPY_B;
+}
+template <int ROW> DEV bool sp_needs_b(int m) {
+  if(ROW == SP_VT || ROW == SP_VS) return m == SP_COPY_B || m == SP_VV || m == SP_UV;
+  if(ROW == SP_HM) return m == SP_COPY_B;
+  return m != SP_COPY_A;
+}
+// elements k .. k + N - 1 of a row of kind ROW of P(A, B, r); la() / lb() give the two frames' elements and are called only
+// where the case reads that frame
+template <int N, int ROW, class LA, class LB>
+DEV SpVec<N> sp_blend(const SpPair& p, int k, int me, LA la, LB lb) {
+  SpVec<N> a = {}, b = {}, o;
+  const int m = p.mode;
+  if(sp_needs_a<ROW>(m)) a = la();
+  if(sp_needs_b<ROW>(m)) b = lb();
+  if(m == SP_COPY_A) return a;
+  if(m == SP_COPY_B) return b;
+  const float r = p.r;
+#pragma unroll
+  for(int j = 0; j < N; j ++) {
+    const float xa = a.v[j], xb = b.v[j];
+    float y;
+    if(ROW == SP_VT) y = floor80(m == SP_VV ? lin(xa, xb, r) : (m == SP_VU ? xa + p.fade : (m == SP_UV ? xb + p.fade : xa)));
+    else if(ROW == SP_VS) {
+      if(m == SP_VV) y = k + j < p.nvmin ? sp_circ(xa, xb, r) : (p.vlong ? xb : xa);
+      else y = m == SP_UV ? xb : xa;
+    }
+    else if(ROW == SP_LIN) y = lin(xa, xb, r);
+    else if(ROW == SP_EA) y = (k + j) % me < p.nemin ? lin(xa, xb, r) : (p.elong ? xb : xa);
+    else if(ROW == SP_EP) y = (k + j) % me < p.nemin ? sp_circ(xa, xb, r) : (p.elong ? xb : xa);
+    else y = m == SP_UU ? xa : 0.0f;                       // SP_HM: voiced output frames get zero rows
+    o.v[j] = y;
+  }
+  return o;
+}
+
+// one output frame of k_splice: sides A and B are P of source frames ga, ga + 1 and gb, gb + 1, the output P(A, B, mix);
+// gr: the source frame of its PSDRES row
+struct SpFrame { SpPair o, a, b; int ga, gb, gr; };
+template <int N, int ROW>
+DEV SpVec<N> sp_el(const SpFrame& F, const float* __restrict__ s, int W, int k, int me) {
+  if(ROW == SP_RES) return sp_ld<N>(s + (size_t)F.gr * W + k);
+  auto side = [&](const SpPair& p, int g) {
+    const float* x = s + (size_t)g * W + k;
+    return sp_blend<N, ROW>(p, k, me, [&] { return sp_ld<N>(x); }, [&] { return sp_ld<N>(x + W); });
+  };
+  return sp_blend<N, ROW>(F.o, k, me, [&] { return side(F.a, F.ga); }, [&] { return side(F.b, F.gb); });
+}
+// the span of one kind of row (W floats per frame) of the workgroup's nf frames, from source array s into d
+template <int ROW, bool VEC>
+DEV void sp_span(float* __restrict__ d, const float* __restrict__ s, int W, int nf, const SpFrame* F, int me, int tid) {
+  const int n = nf * W, n4 = VEC ? n >> 2 : 0;
+  for(int q = tid; q < n4; q += kSpThreads) {
+    int f = (4 * q) / W, k = 4 * q - f * W;
+    SpVec<4> o;
+    if(k + 4 <= W) o = sp_el<4, ROW>(F[f], s, W, k, me);
+    else for(int j = 0; j < 4; j ++) { o.v[j] = sp_el<1, ROW>(F[f], s, W, k, me).v[0]; if(++ k == W) { k = 0; f ++; } }
+    ((float4*)d)[q] = make_float4(o.v[0], o.v[1], o.v[2], o.v[3]);
+  }
+  for(int e = (n4 << 2) + tid; e < n; e += kSpThreads) { const int f = e / W; d[e] = sp_el<1, ROW>(F[f], s, W, e - f * W, me).v[0]; }
 }
 }  // namespace
 
@@ -154,21 +281,21 @@ __global__ __launch_bounds__(64) void k_retime(ModRows s, ModRows d, RetimeMap m
   float f0, rd; int nv;
   if(va && vb) {
     f0 = lin(fa, fb, r); rd = lin(s.rd[ga], s.rd[gb], r); nv = max(nva, nvb);
-    for(int k = lane; k < ns; k += 64) vt[k] = fmaxf(lin(vta[k], vtb[k], r), -80.0f);
+    for(int k = lane; k < ns; k += 64) vt[k] = floor80(lin(vta[k], vtb[k], r));
     const int nmin = min(nva, nvb);
     const float* lng = nva >= nvb ? vsa : vsb;
     for(int k = lane; k < mh; k += 64) vs[k] = k < nmin ? circ(vsa[k], vsb[k], r) : lng[k];
   } else if(va || vb) {                                   // voicing changes: the voiced side, faded in or out
     const size_t gv = va ? ga : gb;
     const float w = va ? 1.0f - r : r;
-    const float fade = 20.0f * log10f(fmaxf(1e-8f, w));
+    const float fade = fade_db(w);
     f0 = s.f0[gv]; rd = s.rd[gv]; nv = clampi(s.nvsphse[gv], 0, mh);
     const float* vtv = s.vtmagn + gv * ns;
-    for(int k = lane; k < ns; k += 64) vt[k] = fmaxf(vtv[k] + fade, -80.0f);
+    for(int k = lane; k < ns; k += 64) vt[k] = floor80(vtv[k] + fade);
     copy_row(vs, s.vsphse + gv * mh, mh, lane);
   } else {
     f0 = 0.0f; rd = 1.0f; nv = nva;
-    for(int k = lane; k < ns; k += 64) vt[k] = fmaxf(vta[k], -80.0f);
+    for(int k = lane; k < ns; k += 64) vt[k] = floor80(vta[k]);
     copy_row(vs, vsa, mh, lane);
   }
   const bool voiced = va || vb;
@@ -205,6 +332,55 @@ __global__ __launch_bounds__(64) void k_retime(ModRows s, ModRows d, RetimeMap m
     d.nhar[G] = voiced ? 0 : s.nhar[ga];
     d.has_hm[G] = voiced ? 0 : s.has_hm[ga];
   }
+}
+
+// Thread (f, j) of the first sixteen fetches the scalars of source frame j (a, a + 1 of side A; a, a + 1 of side B) of output
+// frame f where the map makes the frame read it; thread f then plans the frame and writes its scalars.
+__global__ __launch_bounds__(kSpThreads) void k_splice(ModRows s, ModRows d, SpliceMap m) {
+  __shared__ SpScal s_src[kSpFrames][4];
+  __shared__ SpFrame s_frm[kSpFrames];
+  const int g0 = xcd_frame(blockIdx.x, gridDim.x) * kSpFrames, tid = threadIdx.x;
+  const int nf = min(kSpFrames, d.nframes - g0);
+  const int mh = s.maxnhar, np = s.npsd, nch = s.nchannel, ns = s.nspec;
+  const int me = s.maxnhar_e > 0 ? s.maxnhar_e : 1;
+  if(tid < 4 * nf) {
+    const int g = g0 + (tid >> 2), j = tid & 3;
+    const float mix = m.mix ? m.mix[g] : 0.0f;
+    const bool side_b = j >= 2;
+    if(side_b ? mix != 0.0f : mix != 1.0f) {               // (a side the output does not use is not read)
+      const float r = side_b ? m.rb[g] : m.ra[g];
+      if(j & 1 ? r != 0.0f : r != 1.0f) s_src[tid >> 2][j] = sp_scal(s, (size_t)(side_b ? m.gb[g] : m.ga[g]) + (j & 1));
+    }
+  }
+  __syncthreads();
+  if(tid < nf) {
+    const int g = g0 + tid;
+    SpFrame F;
+    const float mix = m.mix ? m.mix[g] : 0.0f;
+    SpScal A = {}, B = {}, O;
+    F.ga = m.ga[g]; F.gb = m.mix ? m.gb[g] : 0;
+    F.a.mode = F.b.mode = SP_COPY_A;
+    float ra = 0.0f, rb = 0.0f;
+    if(mix != 1.0f) { ra = m.ra[g]; sp_pair(s_src[tid][0], s_src[tid][1], ra, mh, s.maxnhar_e, & F.a, & A); }
+    if(mix != 0.0f) { rb = m.rb[g]; sp_pair(s_src[tid][2], s_src[tid][3], rb, mh, s.maxnhar_e, & F.b, & B); }
+    sp_pair(A, B, mix, mh, s.maxnhar_e, & F.o, & O);
+    // PSDRES: the frame at floor(pos) of side A below mix 0.5, of side B from there on (r == 1 only at an utterance's end)
+    F.gr = mix < 0.5f ? F.ga + (ra == 1.0f) : F.gb + (rb == 1.0f);
+    s_frm[tid] = F;
+    d.f0[g] = O.f0; d.rd[g] = O.rd; d.nvsphse[g] = O.nv; d.nhar_e[g] = O.ne; d.nhar[g] = O.nhar; d.has_hm[g] = O.has_hm;
+    d.pbpsyn[g] = O.pbpsyn; d.has_psdres[g] = s.has_psdres[F.gr];
+  }
+  __syncthreads();
+  const size_t G0 = (size_t)g0;
+  sp_span<SP_VT, true>(d.vtmagn + G0 * ns, s.vtmagn, ns, nf, s_frm, me, tid);
+  sp_span<SP_LIN, true>(d.psd + G0 * np, s.psd, np, nf, s_frm, me, tid);
+  sp_span<SP_RES, true>(d.psdres + G0 * np, s.psdres, np, nf, s_frm, me, tid);
+  sp_span<SP_VS, true>(d.vsphse + G0 * mh, s.vsphse, mh, nf, s_frm, me, tid);
+  sp_span<SP_HM, true>(d.ampl + G0 * mh, s.ampl, mh, nf, s_frm, me, tid);
+  sp_span<SP_HM, true>(d.phse + G0 * mh, s.phse, mh, nf, s_frm, me, tid);
+  sp_span<SP_LIN, false>(d.edc + G0 * nch, s.edc, nch, nf, s_frm, me, tid);
+  sp_span<SP_EA, false>(d.eenv_ampl + G0 * nch * me, s.eenv_ampl, nch * me, nf, s_frm, me, tid);
+  sp_span<SP_EP, false>(d.eenv_phse + G0 * nch * me, s.eenv_phse, nch * me, nf, s_frm, me, tid);
 }
 
 // The span of VTMAGN (ns bins per frame) or PSD of one workgroup's frames, rewritten from its LDS image `x`: bin k of local
@@ -289,6 +465,13 @@ int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, co
 int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m) {
   if(dst.nframes <= 0) return 0;
   LAUNCH("k_retime", k_retime, dim3(dst.nframes), dim3(64), 0, src, dst, m);
+  return 0;
+}
+
+int launch_splice(LaunchCtx* P, const ModRows& src, const ModRows& dst, const SpliceMap& m) {
+  if(dst.nframes <= 0) return 0;
+  const int groups = (dst.nframes + kSpFrames - 1) / kSpFrames;
+  LAUNCH("k_splice", k_splice, dim3(groups), dim3(kSpThreads), 0, src, dst, m);
   return 0;
 }
 

@@ -7,11 +7,15 @@ nfft = 2048).  --edit stretch (the default) stretches 2x:
 
     phasepropagate(-1) -> pitch_formant(1.5, 1.2, warp_psd) -> tolayer0(1) -> phasepropagate(+1) -> synthesize
 
-and prints one JSON object: ms per call of each kernel of the chain (the context's per-launch HIP events), GB/s of the
+--edit splice times llsm_gpu_batch_splice alone, beside retime on the same 2x map in the same process: the degenerate map
+(no second side; its rows are compared bit for bit with retime's) and a full two-sided map (random utterances and
+positions on both sides, mix in (0, 1)).
+
+Each prints one JSON object: ms per call of each kernel of the chain (the context's per-launch HIP events), GB/s of the
 edit kernels on unique bytes, the wall time of the chain, and the host round trip the device edit replaces (the rows
 downloaded, edited in numpy by the same rules, uploaded again) on the same box.
 
-    python tools/bench_modify.py [--edit stretch|pitch] [--utts 1024] [--steps 5] [--warmup 2] [--nfft 2048] [--out FILE]
+    python tools/bench_modify.py [--edit stretch|pitch|splice] [--utts 1024] [--steps 5] [--warmup 2] [--nfft 2048] [--out FILE]
 """
 import argparse
 import json
@@ -204,9 +208,84 @@ def pitch_leg(a):
     return out
 
 
+def splice_leg(a):
+    n_utt, n2 = a.utts, 2 * NFRM
+    x = make_batch_inputs(list(range(n_utt)), lambda u: 120.0, "cuda:0")
+    ctx = llsm.Context(0)
+    ao = llsm.make_aoptions(f0_refine=0)
+    src = llsm.Batch(ctx, ao, FS, [NX] * n_utt, [NFRM] * n_utt)
+    src.upload(llsm.A_X, x.ravel()); src.upload(llsm.A_F0, np.full(n_utt * NFRM, 120.0, np.float32))
+    src.analyze(); src.tolayer1(a.nfft); src.phasepropagate(-1)
+    ref = llsm.Batch(ctx, ao, FS, [0] * n_utt, [n2] * n_utt)
+    dst = llsm.Batch(ctx, ao, FS, [0] * n_utt, [n2] * n_utt)
+    ctx.sync()
+    nspec = a.nfft // 2 + 1
+    Fs, Fd = n_utt * NFRM, n_utt * n2
+    rng = np.random.default_rng(1)
+    pos = np.tile(llsm.retime_uniform_positions(NFRM, n2), n_utt)
+    two = dict(utt_a=rng.integers(0, n_utt, Fd), pos_a=rng.uniform(0, NFRM - 1, Fd), utt_b=rng.integers(0, n_utt, Fd),
+               pos_b=rng.uniform(0, NFRM - 1, Fd), mix=rng.uniform(0.01, 0.99, Fd))
+    # a morph that keeps the locality of the stretch: both sides walk their utterances in order, side b one utterance on
+    morph = dict(utt_a=np.repeat(np.arange(n_utt), n2), pos_a=pos, utt_b=np.repeat((np.arange(n_utt) + 1) % n_utt, n2),
+                 pos_b=pos, mix=two["mix"])
+    legs = dict(retime=lambda: ref.retime(src, pos), splice_one_side=lambda: dst.splice(src, pos),
+                splice_morph=lambda: dst.splice(src, **morph), splice_two_sides_random=lambda: dst.splice(src, **two))
+    for _ in range(a.warmup):
+        for f in legs.values():
+            f()
+    ctx.sync()
+    rb = row_bytes(src, nspec)
+    out = dict(edit="splice", shape=dict(utterances=n_utt, frames_src=Fs, frames_dst=Fd, nfft=a.nfft, row_bytes=rb), legs={})
+    for name, f in legs.items():                            # alternating, each leg's launches bracketed by events
+        out["legs"][name] = dict(ms=[], wall_ms=[])
+    for _ in range(a.steps):
+        for name, f in legs.items():
+            ctx.set_profiling(True); ctx.reset_profile()
+            t0 = time.perf_counter(); f(); ctx.sync(); wall = (time.perf_counter() - t0) * 1e3
+            prof = ctx.profile(); ctx.set_profiling(False)
+            k = "k_retime" if name == "retime" else "k_splice"
+            out["legs"][name]["ms"].append(prof[k][0] / prof[k][1]); out["legs"][name]["wall_ms"].append(wall)
+    for name, d in out["legs"].items():
+        # unique bytes: every source row read once, every output row written once, the map; the random two-sided map also
+        # counts what it gathers (four source frames per output frame) since little of that is shared between neighbours
+        words = 1 if name == "retime" else (2 if name == "splice_one_side" else 5)
+        uniq = Fs * rb + Fd * rb + Fd * 4 * words
+        ms = float(np.median(d["ms"]))
+        d.update(ms_median=ms, ms_min=min(d["ms"]), unique_gb=uniq / 1e9, tbs=uniq / ms / 1e9,
+                 wall_ms_median=float(np.median(d["wall_ms"])))
+        if name == "splice_two_sides_random":
+            gath = 4 * Fd * rb + Fd * rb + Fd * 4 * words
+            d.update(gathered_gb=gath / 1e9, gathered_tbs=gath / ms / 1e9)
+    ref.retime(src, pos); dst.splice(src, pos); ctx.sync()
+    ref.nspec = nspec
+    out["one_side_equals_retime"] = all(np.array_equal(ref.download(aid).view(np.uint32), dst.download(aid).view(np.uint32))
+                                        for aid in ROWS)
+    if a.host_reps > 0:
+        # the host round trip the call replaces: rows down, the same blend in numpy, rows up
+        p1 = llsm.retime_uniform_positions(NFRM, n2)
+        hosts = []
+        for _ in range(a.host_reps):
+            t0 = time.perf_counter()
+            s = {aid: src.download(aid) for aid in ROWS}
+            t1 = time.perf_counter()
+            rows = numpy_retime(s, NFRM, n2, n_utt, p1)
+            t2 = time.perf_counter()
+            for aid in ROWS:
+                dst.upload(aid, rows[aid])
+            ctx.sync()
+            t3 = time.perf_counter()
+            hosts.append(dict(download_ms=(t1 - t0) * 1e3, blend_ms=(t2 - t1) * 1e3, upload_ms=(t3 - t2) * 1e3,
+                              total_ms=(t3 - t0) * 1e3))
+        out["host_round_trip"] = min(hosts, key=lambda h: h["total_ms"])
+    for b in (src, ref, dst):
+        b.close()
+    ctx.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--edit", choices=("stretch", "pitch"), default="stretch")
+    ap.add_argument("--edit", choices=("stretch", "pitch", "splice"), default="stretch")
     ap.add_argument("--utts", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -214,8 +293,8 @@ def main():
     ap.add_argument("--host-reps", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.edit == "pitch":
-        line = json.dumps(pitch_leg(a))
+    if a.edit in ("pitch", "splice"):
+        line = json.dumps(pitch_leg(a) if a.edit == "pitch" else splice_leg(a))
         print(line)
         if a.out:
             with open(a.out, "w") as f:
