@@ -598,7 +598,7 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> l1_prev.release(); b -> l1_next.release(); b -> l1_blk_off.release(); b -> l1_select.release();
   b -> l1_jobs.release(); b -> l1_pulses.release(); b -> l1_segs.release(); b -> l1_blk_jobs.release();
   b -> l1_proj.release(); b -> l1_alpha.release(); b -> l1_alpha_key.release();
-  b -> mod_theta.release(); b -> mod_pos.release(); b -> mod_ratio.release(); b -> mod_res.release(); b -> mod_splice.release();
+  b -> mod_theta.release(); b -> mod_ratio.release(); b -> mod_map.release();
   if(b -> mod_ev) { (void)hipEventDestroy(b -> mod_ev); b -> mod_ev = nullptr; }
   b -> coder_mel.release();
   b -> blob_widths.release(); b -> blob_tab.release(); b -> blob_dev.release();

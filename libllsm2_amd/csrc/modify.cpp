@@ -6,7 +6,8 @@
 //                                    of another batch (rules: llsm_gpu.h)
 //   llsm_gpu_retime_uniform_positions  the map retime uses when it is given none
 //   llsm_gpu_batch_splice            retime's pair rule across utterances and between two sides: unit selection, joins with
-//                                    cross-fades and morphs from index lists (rules: llsm_gpu.h)
+//                                    cross-fades and morphs from index lists (rules: llsm_gpu.h);
+//                                    retime and splice share their refusals and their path to the device (fit, blend_frames)
 //   llsm_gpu_batch_pitch_formant     F0 and formant ratios per frame on a layer-1 batch, the edit of the reference's
 //                                    pitch-shift recipe (rules: llsm_gpu.h)
 #include <hip/hip_runtime.h>
@@ -25,7 +26,7 @@ int launch_failed(const char* what, int rc) {
   return -1;
 }
 
-int refuse(const std::string& why) { llsm_set_error("llsm_gpu_batch_retime: " + why); return -1; }
+int refuse(const char* fn, const std::string& why) { llsm_set_error(std::string(fn) + ": " + why); return -1; }
 }  // namespace
 
 extern "C" int llsm_gpu_batch_phasesync_rps(llsm_gpu_batch* b, int layer1_based) {
@@ -59,154 +60,153 @@ extern "C" void llsm_gpu_retime_uniform_positions(int nfrm_src, int nfrm_dst, FP
   }
 }
 
-extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* src_c, const FP_TYPE* pos,
-  const int* psdres_src) {
-  llsm_gpu_batch* src = const_cast<llsm_gpu_batch*>(src_c);         // read only: the rows are not changed
-  if(! dst || ! src) return refuse("NULL batch");
-  if(src == dst) return refuse("src and dst are the same batch");
-  if(src -> ctx != dst -> ctx) return refuse("the two batches are on different contexts");
+namespace {
+// What llsm_gpu_batch_retime and llsm_gpu_batch_splice refuse alike: two batches that do not fit each other.  `fn` words the
+// message.
+int fit(const char* fn, const llsm_gpu_batch* dst, const llsm_gpu_batch* src) {
+  if(! dst || ! src) return refuse(fn, "NULL batch");
+  if(src == dst) return refuse(fn, "src and dst are the same batch");
+  if(src -> ctx != dst -> ctx) return refuse(fn, "the two batches are on different contexts");
   const llsm_aoptions& a = src -> opt; const llsm_aoptions& d = dst -> opt;
   if(a.thop != d.thop || src -> fs != dst -> fs || a.nchannel != d.nchannel || a.npsd != d.npsd || a.maxnhar != d.maxnhar ||
      a.maxnhar_e != d.maxnhar_e || src -> chanfreq != dst -> chanfreq)
-    return refuse("the batches were created with different options or sampling rates");
-  if(src -> lay.n_utt != dst -> lay.n_utt) return refuse("the batches hold different numbers of utterances");
-  if(src -> l1_nspec == 0) return refuse("src has no layer 1 (llsm_gpu_batch_tolayer1)");
-  if(dst -> l1_nspec != 0 && dst -> l1_nspec != src -> l1_nspec) return refuse("dst has layer 1 enabled with another size");
-  const int n_utt = dst -> lay.n_utt, Fd = dst -> lay.total_frames;
-  for(int u = 0; u < n_utt; u ++)
-    if((src -> nfrm[u] == 0) != (dst -> nfrm[u] == 0))
-      return refuse("utterance " + std::to_string(u) + " has frames on one side only");
-  // the map: positions checked (and formed, without one) on the host, then staged in page-locked memory
+    return refuse(fn, "the batches were created with different options or sampling rates");
+  if(src -> l1_nspec == 0) return refuse(fn, "src has no layer 1 (llsm_gpu_batch_tolayer1)");
+  if(dst -> l1_nspec != 0 && dst -> l1_nspec != src -> l1_nspec) return refuse(fn, "dst has layer 1 enabled with another size");
+  return 0;
+}
+
+// The rest of what the two calls share, for batches that fit: the caller's map of `words` words, checked and written into
+// the page-locked stage by resolve(h) (-1 with the error set: refused, dst untouched); dst made ready for src's frames; one
+// copy of the map into mod_map; launch(dm) on the device copy.
+template <class Resolve, class Launch>
+int blend_frames(const char* fn, llsm_gpu_batch* dst, const llsm_gpu_batch* src, size_t words, Resolve resolve, Launch launch) {
   if(dst -> mod_ev) HIP_OK(hipEventSynchronize(dst -> mod_ev));    // the previous call's copy has left the stage
-  if(! dst -> mod_stage.resize(2 * (size_t)Fd + 1)) return -1;
-  float* hpos = (float*)dst -> mod_stage.data(); int* hres = dst -> mod_stage.data() + Fd;
-  for(int u = 0; u < n_utt; u ++) {
-    const int n = src -> nfrm[u], m = dst -> nfrm[u], o = dst -> frm_off[u];
-    if(pos) {
-      const float last = (float)(n - 1);
-      for(int i = 0; i < m; i ++) {
-        const float t = pos[o + i];
-        if(!(t >= 0.0f && t <= last))
-          return refuse("position " + std::to_string(o + i) + " (utterance " + std::to_string(u) + ") is NaN or outside [0, " +
-            std::to_string(n - 1) + "]");
-        hpos[o + i] = t;
-      }
-    } else llsm_gpu_retime_uniform_positions(n, m, hpos + o);
-    if(psdres_src)
-      for(int i = 0; i < m; i ++) {
-        const int k = psdres_src[o + i];
-        if(k < 0 || k >= n)
-          return refuse("psdres_src[" + std::to_string(o + i) + "] = " + std::to_string(k) + " is not a frame of utterance " +
-            std::to_string(u));
-        hres[o + i] = k;
-      }
-  }
+  if(! dst -> mod_stage.resize(words + 1)) return -1;
+  if(resolve(dst -> mod_stage.data())) return -1;
   // accepted: from here on dst changes
   hipSetDevice(dst -> ctx -> device);
   if(llsm_gpu_batch_enable_layer1(dst, (src -> l1_nspec - 1) * 2)) return -1;
   dst -> fnyq = src -> fnyq;
   dst -> maxnhar_conf = src -> maxnhar_conf;
   dst -> min_f0 = 0; dst -> f0_unknown = true;           // the F0 row is written on the device
-  if(Fd == 0) return 0;
+  if(dst -> lay.total_frames == 0) return 0;
   hipStream_t st = dst -> ctx -> stream;
-  if(dst -> mod_pos.alloc((size_t)Fd) || (psdres_src && dst -> mod_res.alloc((size_t)Fd))) return -1;
-  HIP_OK(hipMemcpyAsync(dst -> mod_pos.p, hpos, (size_t)Fd * sizeof(float), hipMemcpyHostToDevice, st));
-  if(psdres_src) HIP_OK(hipMemcpyAsync(dst -> mod_res.p, hres, (size_t)Fd * sizeof(int), hipMemcpyHostToDevice, st));
+  if(dst -> mod_map.alloc(words)) return -1;
+  HIP_OK(hipMemcpyAsync(dst -> mod_map.p, dst -> mod_stage.data(), words * sizeof(int), hipMemcpyHostToDevice, st));
   if(! dst -> mod_ev) HIP_OK(hipEventCreateWithFlags(& dst -> mod_ev, hipEventDisableTiming));
   HIP_OK(hipEventRecord(dst -> mod_ev, st));
-  RetimeMap m;
-  m.pos = dst -> mod_pos.p; m.res = psdres_src ? dst -> mod_res.p : nullptr; m.utt = dst -> d_frm_utt.p;
-  m.src_off = src -> d_frm_off.p; m.src_nfrm = src -> d_nfrm.p;
-  const int rc = launch_retime(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
-  return rc ? launch_failed("llsm_gpu_batch_retime", rc) : 0;
+  const int rc = launch(dst -> mod_map.p);
+  return rc ? launch_failed(fn, rc) : 0;
+}
+}  // namespace
+
+extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* src_c, const FP_TYPE* pos,
+  const int* psdres_src) {
+  const char* fn = "llsm_gpu_batch_retime";
+  llsm_gpu_batch* src = const_cast<llsm_gpu_batch*>(src_c);         // read only: the rows are not changed
+  if(fit(fn, dst, src)) return -1;
+  if(src -> lay.n_utt != dst -> lay.n_utt) return refuse(fn, "the batches hold different numbers of utterances");
+  const int n_utt = dst -> lay.n_utt;
+  const size_t Fd = (size_t)dst -> lay.total_frames;
+  for(int u = 0; u < n_utt; u ++)
+    if((src -> nfrm[u] == 0) != (dst -> nfrm[u] == 0))
+      return refuse(fn, "utterance " + std::to_string(u) + " has frames on one side only");
+  // the map [positions | (PSDRES frames)], Fd words each: positions checked (and formed, without one) on the host
+  return blend_frames(fn, dst, src, (psdres_src ? 2 : 1) * Fd, [&](int* h) {
+    float* hpos = (float*)h; int* hres = h + Fd;
+    for(int u = 0; u < n_utt; u ++) {
+      const int n = src -> nfrm[u], m = dst -> nfrm[u], o = dst -> frm_off[u];
+      if(pos) {
+        const float last = (float)(n - 1);
+        for(int i = 0; i < m; i ++) {
+          const float t = pos[o + i];
+          if(!(t >= 0.0f && t <= last))
+            return refuse(fn, "position " + std::to_string(o + i) + " (utterance " + std::to_string(u) + ") is NaN or outside [0, " +
+              std::to_string(n - 1) + "]");
+          hpos[o + i] = t;
+        }
+      } else llsm_gpu_retime_uniform_positions(n, m, hpos + o);
+      if(psdres_src)
+        for(int i = 0; i < m; i ++) {
+          const int k = psdres_src[o + i];
+          if(k < 0 || k >= n)
+            return refuse(fn, "psdres_src[" + std::to_string(o + i) + "] = " + std::to_string(k) + " is not a frame of utterance " +
+              std::to_string(u));
+          hres[o + i] = k;
+        }
+    }
+    return 0;
+  }, [&](const int* dm) {
+    RetimeMap m;
+    m.pos = (const float*)dm; m.res = psdres_src ? dm + Fd : nullptr; m.utt = dst -> d_frm_utt.p;
+    m.src_off = src -> d_frm_off.p; m.src_nfrm = src -> d_nfrm.p;
+    return launch_retime(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
+  });
 }
 
 namespace {
-int refuse_sp(const std::string& why) { llsm_set_error("llsm_gpu_batch_splice: " + why); return -1; }
-
 // One side of a splice map resolved into `ga` (flat source frame a) and `r`, formed from the position exactly as k_retime
-// forms them; utt NULL: the output frame's own utterance.  Returns false (error set) at the first bad entry.
-bool stage_side(const llsm_gpu_batch* src, const llsm_gpu_batch* dst, const char* side, const int* utt, const float* pos,
-  int* ga, float* r) {
+// forms them; utt NULL: the output frame's own utterance.  Returns -1 (error set) at the first bad entry; the message is
+// built there and nowhere else.
+int stage_side(const char* fn, const llsm_gpu_batch* src, const llsm_gpu_batch* dst, const char* side, const int* utt,
+  const float* pos, int* ga, float* r) {
   const int n_src = src -> lay.n_utt;
+  auto at = [&](const char* what, int g) { return std::string(what) + "_" + side + "[" + std::to_string(g) + "]"; };
   for(int u = 0; u < dst -> lay.n_utt; u ++)
     for(int g = dst -> frm_off[u]; g < dst -> frm_off[u] + dst -> nfrm[u]; g ++) {
       const int v = utt ? utt[g] : u;
-      const std::string where = std::string(side) + "[" + std::to_string(g) + "]";
-      if(v < 0 || v >= n_src) {
-        refuse_sp("utt_" + where + " = " + std::to_string(v) + " is not an utterance of src (" + std::to_string(n_src) + ")");
-        return false;
-      }
+      if(v < 0 || v >= n_src)
+        return refuse(fn, at("utt", g) + " = " + std::to_string(v) + " is not an utterance of src (" + std::to_string(n_src) + ")");
       const int n = src -> nfrm[v];
-      if(n == 0) { refuse_sp("utt_" + where + " = " + std::to_string(v) + " names an utterance without frames"); return false; }
+      if(n == 0) return refuse(fn, at("utt", g) + " = " + std::to_string(v) + " names an utterance without frames");
       const float t = pos[g];
-      if(!(t >= 0.0f && t <= (float)(n - 1))) {
-        refuse_sp("pos_" + where + " (utterance " + std::to_string(v) + ") is NaN or outside [0, " + std::to_string(n - 1) + "]");
-        return false;
-      }
+      if(!(t >= 0.0f && t <= (float)(n - 1)))
+        return refuse(fn, at("pos", g) + " (utterance " + std::to_string(v) + ") is NaN or outside [0, " + std::to_string(n - 1) + "]");
       int a = 0; float ra = 0;
       if(n > 1) { const int fl = (int)std::floor(t); a = fl < n - 2 ? fl : n - 2; ra = t - (float)a; }
       ga[g] = src -> frm_off[v] + a; r[g] = ra;
     }
-  return true;
+  return 0;
 }
 }  // namespace
 
 extern "C" int llsm_gpu_batch_splice(llsm_gpu_batch* dst, const llsm_gpu_batch* src_c, const llsm_gpu_splice_map* map) {
+  const char* fn = "llsm_gpu_batch_splice";
   llsm_gpu_batch* src = const_cast<llsm_gpu_batch*>(src_c);         // read only: the rows are not changed
-  if(! dst || ! src) return refuse_sp("NULL batch");
-  if(! map) return refuse_sp("NULL map");
-  if(! map -> pos_a) return refuse_sp("pos_a is NULL");
+  if(! dst || ! src) return refuse(fn, "NULL batch");              // (fit's first refusal, named before a NULL map)
+  if(! map) return refuse(fn, "NULL map");
+  if(! map -> pos_a) return refuse(fn, "pos_a is NULL");
   const bool two = map -> utt_b || map -> pos_b || map -> mix;
   if(two && !(map -> utt_b && map -> pos_b && map -> mix))
-    return refuse_sp("the second side is given in part: utt_b, pos_b and mix are all NULL or all given");
-  if(src == dst) return refuse_sp("src and dst are the same batch");
-  if(src -> ctx != dst -> ctx) return refuse_sp("the two batches are on different contexts");
-  const llsm_aoptions& a = src -> opt; const llsm_aoptions& d = dst -> opt;
-  if(a.thop != d.thop || src -> fs != dst -> fs || a.nchannel != d.nchannel || a.npsd != d.npsd || a.maxnhar != d.maxnhar ||
-     a.maxnhar_e != d.maxnhar_e || src -> chanfreq != dst -> chanfreq)
-    return refuse_sp("the batches were created with different options or sampling rates");
-  if(src -> l1_nspec == 0) return refuse_sp("src has no layer 1 (llsm_gpu_batch_tolayer1)");
-  if(dst -> l1_nspec != 0 && dst -> l1_nspec != src -> l1_nspec) return refuse_sp("dst has layer 1 enabled with another size");
+    return refuse(fn, "the second side is given in part: utt_b, pos_b and mix are all NULL or all given");
+  if(fit(fn, dst, src)) return -1;
   if(! map -> utt_a && dst -> lay.n_utt > src -> lay.n_utt)
-    return refuse_sp("utt_a is NULL and dst holds more utterances (" + std::to_string(dst -> lay.n_utt) + ") than src (" +
+    return refuse(fn, "utt_a is NULL and dst holds more utterances (" + std::to_string(dst -> lay.n_utt) + ") than src (" +
       std::to_string(src -> lay.n_utt) + ")");
-  // the map: checked and resolved on the host, then staged in page-locked memory ([ga | ra] and, with a second side,
-  // [gb | rb | mix], Fd words each)
-  const int Fd = dst -> lay.total_frames;
-  const size_t words = (two ? 5 : 2) * (size_t)Fd;
-  if(dst -> mod_ev) HIP_OK(hipEventSynchronize(dst -> mod_ev));    // the previous call's copy has left the stage
-  if(! dst -> mod_stage.resize(words + 1)) return -1;
-  int* h = dst -> mod_stage.data();
-  if(! stage_side(src, dst, "a", map -> utt_a, map -> pos_a, h, (float*)h + Fd)) return -1;
-  if(two) {
-    if(! stage_side(src, dst, "b", map -> utt_b, map -> pos_b, h + 2 * (size_t)Fd, (float*)h + 3 * (size_t)Fd)) return -1;
-    float* hmix = (float*)h + 4 * (size_t)Fd;
-    for(int g = 0; g < Fd; g ++) {
+  // the map resolved into flat source frames and weights: [ga | ra] and, with a second side, [gb | rb | mix], Fd words each;
+  // the rows of the stage and of its device copy are named in one place
+  const size_t Fd = (size_t)dst -> lay.total_frames;
+  struct Rows { int* ga; float* ra; int* gb; float* rb; float* mix; };
+  auto rows = [&](int* p) { return Rows{p, (float*)p + Fd, p + 2 * Fd, (float*)p + 3 * Fd, (float*)p + 4 * Fd}; };
+  return blend_frames(fn, dst, src, (two ? 5 : 2) * Fd, [&](int* stage) {
+    const Rows h = rows(stage);
+    if(stage_side(fn, src, dst, "a", map -> utt_a, map -> pos_a, h.ga, h.ra)) return -1;
+    if(! two) return 0;
+    if(stage_side(fn, src, dst, "b", map -> utt_b, map -> pos_b, h.gb, h.rb)) return -1;
+    for(size_t g = 0; g < Fd; g ++) {
       const float w = map -> mix[g];
-      if(!(w >= 0.0f && w <= 1.0f)) return refuse_sp("mix[" + std::to_string(g) + "] is NaN or outside [0, 1]");
-      hmix[g] = w;
+      if(!(w >= 0.0f && w <= 1.0f)) return refuse(fn, "mix[" + std::to_string(g) + "] is NaN or outside [0, 1]");
+      h.mix[g] = w;
     }
-  }
-  // accepted: from here on dst changes
-  hipSetDevice(dst -> ctx -> device);
-  if(llsm_gpu_batch_enable_layer1(dst, (src -> l1_nspec - 1) * 2)) return -1;
-  dst -> fnyq = src -> fnyq;
-  dst -> maxnhar_conf = src -> maxnhar_conf;
-  dst -> min_f0 = 0; dst -> f0_unknown = true;           // the F0 row is written on the device
-  if(Fd == 0) return 0;
-  hipStream_t st = dst -> ctx -> stream;
-  if(dst -> mod_splice.alloc(words)) return -1;
-  int* dm = dst -> mod_splice.p;
-  HIP_OK(hipMemcpyAsync(dm, h, words * sizeof(int), hipMemcpyHostToDevice, st));
-  if(! dst -> mod_ev) HIP_OK(hipEventCreateWithFlags(& dst -> mod_ev, hipEventDisableTiming));
-  HIP_OK(hipEventRecord(dst -> mod_ev, st));
-  SpliceMap m;
-  m.ga = dm; m.ra = (const float*)dm + Fd;
-  m.gb = two ? dm + 2 * (size_t)Fd : nullptr; m.rb = two ? (const float*)dm + 3 * (size_t)Fd : nullptr;
-  m.mix = two ? (const float*)dm + 4 * (size_t)Fd : nullptr;
-  const int rc = launch_splice(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
-  return rc ? launch_failed("llsm_gpu_batch_splice", rc) : 0;
+    return 0;
+  }, [&](int* dm) {
+    const Rows d = rows(dm);
+    SpliceMap m;
+    m.ga = d.ga; m.ra = d.ra;
+    m.gb = two ? d.gb : nullptr; m.rb = two ? d.rb : nullptr; m.mix = two ? d.mix : nullptr;
+    return launch_splice(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
+  });
 }
 
 namespace {
