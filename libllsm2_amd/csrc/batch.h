@@ -171,9 +171,9 @@ struct llsm_gpu_batch {
   DevBuf<double> l1_proj;                // next-cycle projection per frame (k_l1_projection), followed by the packed rows: 3.5 F doubles in all
   DevBuf<PbpJob> l1_jobs; DevBuf<PbpPulse> l1_pulses; DevBuf<PbpSeg> l1_segs; DevBuf<int2> l1_blk_jobs;
   // edits (modify.cpp): per-frame phase shifts of phasepropagate; the ratios of the last llsm_gpu_batch_pitch_formant
-  // ([2][F]: F0, formant) and the map of the last llsm_gpu_batch_retime ([1 or 2][F] words: positions, PSDRES frames) or
-  // llsm_gpu_batch_splice ([2 or 5][F] words, resolved: kernels.h SpliceMap) into this batch, staged in page-locked memory
-  // that mod_ev says the copies have left
+  // ([2][F]: F0, formant) and the resolved map (kernels.h SpliceMap) of the last llsm_gpu_batch_retime ([2 or 3][F] words) or
+  // llsm_gpu_batch_splice ([2 or 5][F] words) into this batch, staged in page-locked memory that mod_ev says the copies
+  // have left
   DevBuf<float> mod_theta, mod_ratio; DevBuf<int> mod_map;
   PinVec<int> mod_stage; hipEvent_t mod_ev = nullptr;
   // frame coder (batch_coder.cpp): the orders of LLSM_GPU_CODE (0: not enabled) and the mel axis, built once per batch

@@ -277,19 +277,17 @@ struct ModRows {
   float* eenv_ampl; float* eenv_phse;
   float* rd; float* vtmagn; float* vsphse; int* nvsphse; int* pbpsyn; int* has_hm;
 };
-// Frame-blending map of llsm_gpu_batch_retime: output frame g of utterance utt[g] sits at source position pos[g] of that
-// utterance (frames src_off[u] .. src_off[u] + src_nfrm[u]); res: source frame of its PSDRES row, NULL: floor(pos).
-struct RetimeMap { const float* pos; const int* res; const int* utt; const int* src_off; const int* src_nfrm; };
 // theta == NULL: each frame is shifted by minus its reference phase (llsm_frame_phasesync_rps); else by theta[frame]
 int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int layer1_based);
 // theta[frame] = (float)(running float32 sum of the utterance's F0 up to the frame x k2pi), llsm_chunk_phasepropagate
 int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, const int* nfrm, const float* f0,
   double k2pi, float* theta);
-int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m);
-// Map of llsm_gpu_batch_splice with the utterances resolved on the host: side A of output frame g is the pair rule of retime
-// on src's frames ga[g] and ga[g] + 1 (flat frame indices) at weight ra[g] -- the second is read only where ra[g] != 0 --,
-// side B the same of gb / rb, and the output the pair rule on (A, B) at weight mix[g].  gb, rb and mix NULL: side A alone.
-struct SpliceMap { const int* ga; const float* ra; const int* gb; const float* rb; const float* mix; };
+// Map of llsm_gpu_batch_retime and llsm_gpu_batch_splice with the utterances resolved on the host: side A of output frame g
+// is the pair rule (modify_kernels.hip) on src's frames ga[g] and ga[g] + 1 (flat frame indices) at weight ra[g] -- the second
+// is read only where ra[g] != 0 --, side B the same of gb / rb, and the output the pair rule on (A, B) at weight mix[g].  gb,
+// rb and mix NULL: side A alone.  gr[g]: the flat source frame of the PSDRES row, NULL: the frame at floor(pos) of side A below
+// mix 0.5, of side B from there on.
+struct SpliceMap { const int* ga; const float* ra; const int* gb; const float* rb; const float* mix; const int* gr; };
 int launch_splice(LaunchCtx* P, const ModRows& src, const ModRows& dst, const SpliceMap& m);
 // llsm_gpu_batch_pitch_formant over frames [g_lo, g_hi) (every edited frame): rho / alpha are per-frame F0 and formant
 // ratios (NULL: 1), warp_psd the PSD warp; LDS: 16 (nspec + npsd) bytes per workgroup

@@ -7,12 +7,12 @@
 //   llsm_gpu_retime_uniform_positions  the map retime uses when it is given none
 //   llsm_gpu_batch_splice            retime's pair rule across utterances and between two sides: unit selection, joins with
 //                                    cross-fades and morphs from index lists (rules: llsm_gpu.h);
-//                                    retime and splice share their refusals and their path to the device (fit, blend_frames)
+//                                    retime and splice share their refusals, their path to the device (fit, blend_frames)
+//                                    and their kernel (k_splice)
 //   llsm_gpu_batch_pitch_formant     F0 and formant ratios per frame on a layer-1 batch, the edit of the reference's
 //                                    pitch-shift recipe (rules: llsm_gpu.h)
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <string>
 #include <vector>
 
@@ -76,6 +76,13 @@ int fit(const char* fn, const llsm_gpu_batch* dst, const llsm_gpu_batch* src) {
   return 0;
 }
 
+// Position t of an utterance of n frames (0 <= t <= n - 1) as the pair rule takes it: frame *a and the weight *r of frame
+// a + 1, with a = min(floor(t), n - 2) so that the last frame is reached through r = 1; a one-frame utterance is its frame.
+inline void pair_at(float t, int n, int* a, float* r) {
+  *a = 0; *r = 0;
+  if(n > 1) { const int fl = (int)t; *a = fl < n - 2 ? fl : n - 2; *r = t - (float)*a; }   // (t >= 0: truncation is floor)
+}
+
 // The rest of what the two calls share, for batches that fit: the caller's map of `words` words, checked and written into
 // the page-locked stage by resolve(h) (-1 with the error set: refused, dst untouched); dst made ready for src's frames; one
 // copy of the map into mod_map; launch(dm) on the device copy.
@@ -112,11 +119,12 @@ extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* 
   for(int u = 0; u < n_utt; u ++)
     if((src -> nfrm[u] == 0) != (dst -> nfrm[u] == 0))
       return refuse(fn, "utterance " + std::to_string(u) + " has frames on one side only");
-  // the map [positions | (PSDRES frames)], Fd words each: positions checked (and formed, without one) on the host
-  return blend_frames(fn, dst, src, (psdres_src ? 2 : 1) * Fd, [&](int* h) {
-    float* hpos = (float*)h; int* hres = h + Fd;
+  // the map resolved into flat source frames and weights, [ga | ra] and with psdres_src [gr], Fd words each: positions
+  // checked (and formed, without one) on the host
+  return blend_frames(fn, dst, src, (psdres_src ? 3 : 2) * Fd, [&](int* h) {
+    int* ga = h; float* ra = (float*)h + Fd; int* gr = h + 2 * Fd;
     for(int u = 0; u < n_utt; u ++) {
-      const int n = src -> nfrm[u], m = dst -> nfrm[u], o = dst -> frm_off[u];
+      const int n = src -> nfrm[u], m = dst -> nfrm[u], o = dst -> frm_off[u], so = src -> frm_off[u];
       if(pos) {
         const float last = (float)(n - 1);
         for(int i = 0; i < m; i ++) {
@@ -124,30 +132,37 @@ extern "C" int llsm_gpu_batch_retime(llsm_gpu_batch* dst, const llsm_gpu_batch* 
           if(!(t >= 0.0f && t <= last))
             return refuse(fn, "position " + std::to_string(o + i) + " (utterance " + std::to_string(u) + ") is NaN or outside [0, " +
               std::to_string(n - 1) + "]");
-          hpos[o + i] = t;
+          ra[o + i] = t;
         }
-      } else llsm_gpu_retime_uniform_positions(n, m, hpos + o);
+      } else llsm_gpu_retime_uniform_positions(n, m, ra + o);
+      for(int i = 0; i < m; i ++) {                                  // the row of positions becomes the row of weights
+        int a;
+        pair_at(ra[o + i], n, & a, & ra[o + i]);
+        ga[o + i] = so + a;
+      }
       if(psdres_src)
         for(int i = 0; i < m; i ++) {
           const int k = psdres_src[o + i];
           if(k < 0 || k >= n)
             return refuse(fn, "psdres_src[" + std::to_string(o + i) + "] = " + std::to_string(k) + " is not a frame of utterance " +
               std::to_string(u));
-          hres[o + i] = k;
+          gr[o + i] = so + k;
         }
     }
     return 0;
   }, [&](const int* dm) {
-    RetimeMap m;
-    m.pos = (const float*)dm; m.res = psdres_src ? dm + Fd : nullptr; m.utt = dst -> d_frm_utt.p;
-    m.src_off = src -> d_frm_off.p; m.src_nfrm = src -> d_nfrm.p;
-    return launch_retime(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
+    // Without psdres_src gr stays NULL: the kernel's own ga + (ra == 1) is the frame at min(floor(t), n - 1).  For n > 1,
+    // ra == 1 only at t = n - 1, where a + 1 = n - 1 (t - (float)a is exact on [a, a + 1], so below it ra < 1 and
+    // a = floor(t)); for n == 1 both are 0.
+    SpliceMap m = {};
+    m.ga = dm; m.ra = (const float*)dm + Fd; m.gr = psdres_src ? dm + 2 * Fd : nullptr;
+    return launch_splice(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
   });
 }
 
 namespace {
-// One side of a splice map resolved into `ga` (flat source frame a) and `r`, formed from the position exactly as k_retime
-// forms them; utt NULL: the output frame's own utterance.  Returns -1 (error set) at the first bad entry; the message is
+// One side of a splice map resolved into `ga` (flat source frame a) and `r`, formed from the position by pair_at; utt NULL:
+// the output frame's own utterance.  Returns -1 (error set) at the first bad entry; the message is
 // built there and nowhere else.
 int stage_side(const char* fn, const llsm_gpu_batch* src, const llsm_gpu_batch* dst, const char* side, const int* utt,
   const float* pos, int* ga, float* r) {
@@ -163,9 +178,9 @@ int stage_side(const char* fn, const llsm_gpu_batch* src, const llsm_gpu_batch* 
       const float t = pos[g];
       if(!(t >= 0.0f && t <= (float)(n - 1)))
         return refuse(fn, at("pos", g) + " (utterance " + std::to_string(v) + ") is NaN or outside [0, " + std::to_string(n - 1) + "]");
-      int a = 0; float ra = 0;
-      if(n > 1) { const int fl = (int)std::floor(t); a = fl < n - 2 ? fl : n - 2; ra = t - (float)a; }
-      ga[g] = src -> frm_off[v] + a; r[g] = ra;
+      int a;
+      pair_at(t, n, & a, & r[g]);
+      ga[g] = src -> frm_off[v] + a;
     }
   return 0;
 }
@@ -202,9 +217,9 @@ extern "C" int llsm_gpu_batch_splice(llsm_gpu_batch* dst, const llsm_gpu_batch* 
     return 0;
   }, [&](int* dm) {
     const Rows d = rows(dm);
-    SpliceMap m;
+    SpliceMap m = {};                                              // (gr NULL: PSDRES by the kernel's own rule)
     m.ga = d.ga; m.ra = d.ra;
-    m.gb = two ? d.gb : nullptr; m.rb = two ? d.rb : nullptr; m.mix = two ? d.mix : nullptr;
+    if(two) { m.gb = d.gb; m.rb = d.rb; m.mix = d.mix; }
     return launch_splice(& dst -> ctx -> lc, mod_rows(src), mod_rows(dst), m);
   });
 }

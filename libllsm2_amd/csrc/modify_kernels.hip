@@ -4,15 +4,14 @@
 //                   or formed from the frame's reference phase (llsm_frame_phasesync_rps); one wavefront per frame
 //   k_prop_theta    the per-frame shifts of llsm_chunk_phasepropagate: float32 running sum of an utterance's F0 row, in
 //                   frame order, staged through LDS; one workgroup per utterance
-//   k_retime        the frame-blending step of the reference's time-stretch recipe onto a new frame grid; one wavefront per
-//                   output frame, lanes across the rows
 //   k_pitch_formant F0 scaling, VTMAGN amplitude compensation and formant warp (VTMAGN, optionally PSD) of
 //                   llsm_gpu_batch_pitch_formant; four consecutive frames per 256-thread workgroup, rows staged in LDS with
 //                   16-byte accesses, the warp a gather from LDS
-//   k_splice        llsm_gpu_batch_splice: every output frame is the pair rule of k_retime applied to two frames that are
-//                   themselves pair-rule blends of frames of any utterance of another batch; four consecutive output frames
-//                   per 256-thread workgroup, 16-byte stores, 16-byte loads at the source's own alignment, only the frames'
-//                   scalars in LDS
+//   k_splice        llsm_gpu_batch_retime and llsm_gpu_batch_splice: the frame-blending step of the reference's time-stretch
+//                   recipe as a pair rule P(A, B, r) on two frames; every output frame is P applied to two frames that are
+//                   themselves P of two frames of any utterance of another batch (retime: one side, the frame's own
+//                   utterance); four consecutive output frames per 256-thread workgroup, 16-byte stores, 16-byte loads at
+//                   the source's own alignment, only the frames' scalars in LDS
 //
 // No `#pragma clang fp contract(fast)` here: the phase kernels reproduce the host's float64 arithmetic bit for bit and the
 // blends are x_a + (x_b - x_a) r without contraction (the library is built with -ffp-contract=off).
@@ -47,13 +46,10 @@ DEV float lin(float a, float b, float r) { return a + (b - a) * r; }
 DEV float circ(float pa, float pb, float r) {
   return atan2f(lin(sinf(pa), sinf(pb), r), lin(cosf(pa), cosf(pb), r));
 }
-// the per-element pieces of the pair rule that k_retime and k_splice share: the -80 dB floor of VTMAGN and the fade of the
-// voiced side of a voicing change by the weight w
+// per-element pieces of the pair rule: the -80 dB floor of VTMAGN and the fade of the voiced side of a voicing change by the
+// weight w
 DEV float floor80(float x) { return fmaxf(x, -80.0f); }
 DEV float fade_db(float w) { return 20.0f * log10f(fmaxf(1e-8f, w)); }
-DEV void copy_row(float* __restrict__ d, const float* __restrict__ s, int n, int lane) {
-  for(int k = lane; k < n; k += 64) d[k] = s[k];
-}
 
 // k_pitch_formant: a workgroup takes frames g0 .. g0 + 3 with g0 a multiple of 4, so its spans of VTMAGN (4 nspec floats)
 // and PSD (4 npsd floats) start on a 16-byte boundary of the (256-byte aligned) rows and move as float4; only the batch's
@@ -99,11 +95,15 @@ DEV SpScal sp_scal(const ModRows& s, size_t g) {
   o.pbpsyn = s.pbpsyn[g];
   return o;
 }
-// The pair rule P(A, B, r) of llsm_gpu_batch_retime as one plan per frame pair: which case applies and the counts its rows
-// need.  SP_VU: A is the voiced frame of a voicing change, SP_UV: B is.
+// The pair rule P(A, B, r) (llsm_gpu.h) as one plan per frame pair: which case applies and the counts
+// its rows need.  r == 0 is A and r == 1 is B, bit for bit.  Otherwise: both voiced (SP_VV): F0, RD and VTMAGN lin, VSPHSE circ
+// over the shorter row, the rest from the longer; one voiced (SP_VU: A is, SP_UV: B is): that frame's F0, RD and VSPHSE, its
+// VTMAGN faded by its weight; neither (SP_UU): F0 = 0, RD = 1, A's layer-1 rows.  PSD and EDC lin; the envelopes lin / circ over
+// the shorter count, the rest from the longer.  A voiced output frame has no harmonic model (NHAR = HAS_HM = 0, zero rows:
+// llsm_gpu_batch_tolayer0(dst, 1) rebuilds it from layer 1), an unvoiced one keeps A's.  PSDRES is not blended (SpFrame::gr).
 enum { SP_COPY_A, SP_COPY_B, SP_VV, SP_VU, SP_UV, SP_UU };
 struct SpPair { int mode; float r, fade; int nvmin, vlong, nemin, elong; };   // vlong / elong: the longer row is B's
-// plan and resulting scalars of P(A, B, r), as k_retime forms them (B is not looked at when r == 0, nor A when r == 1)
+// plan and resulting scalars of P(A, B, r) (B is not looked at when r == 0, nor A when r == 1)
 DEV void sp_pair(const SpScal& A, const SpScal& B, float r, int mh, int mne, SpPair* p, SpScal* o) {
   p -> r = r; p -> fade = 0.0f; p -> nvmin = p -> vlong = p -> nemin = p -> elong = 0;
   if(r == 0.0f) { p -> mode = SP_COPY_A; *o = A; return; }
@@ -237,103 +237,6 @@ __global__ __launch_bounds__(256) void k_prop_theta(const int* __restrict__ frm_
   }
 }
 
-__global__ __launch_bounds__(64) void k_retime(ModRows s, ModRows d, RetimeMap m) {
-  const int g = xcd_frame(blockIdx.x, gridDim.x), lane = threadIdx.x;
-  const int u = m.utt[g], n = m.src_nfrm[u];
-  const float t = m.pos[g];
-  const int fl = (int)floorf(t);
-  int a = 0; float r = 0;
-  if(n > 1) { a = min(fl, n - 2); r = t - (float)a; }
-  const int b = n > 1 ? a + 1 : a;
-  const size_t o = (size_t)m.src_off[u], G = (size_t)g;
-  const size_t ga = o + a, gb = o + b, gr = o + (m.res ? m.res[g] : min(fl, n - 1));
-  const int mh = s.maxnhar, np = s.npsd, nch = s.nchannel, ns = s.nspec;
-  const int me = s.maxnhar_e > 0 ? s.maxnhar_e : 1;
-
-  // PSDRES follows its own source frame in every case
-  copy_row(d.psdres + G * np, s.psdres + gr * np, np, lane);
-  if(lane == 0) d.has_psdres[G] = s.has_psdres[gr];
-
-  if(r == 0.0f || r == 1.0f) {                            // on a source frame: a bit-exact copy of it
-    const size_t gc = r == 0.0f ? ga : gb;
-    if(lane == 0) {
-      d.f0[G] = s.f0[gc]; d.nhar[G] = s.nhar[gc]; d.nhar_e[G] = s.nhar_e[gc]; d.rd[G] = s.rd[gc];
-      d.nvsphse[G] = s.nvsphse[gc]; d.pbpsyn[G] = s.pbpsyn[gc]; d.has_hm[G] = s.has_hm[gc];
-    }
-    copy_row(d.ampl + G * mh, s.ampl + gc * mh, mh, lane);
-    copy_row(d.phse + G * mh, s.phse + gc * mh, mh, lane);
-    copy_row(d.psd + G * np, s.psd + gc * np, np, lane);
-    copy_row(d.edc + G * nch, s.edc + gc * nch, nch, lane);
-    copy_row(d.eenv_ampl + G * nch * me, s.eenv_ampl + gc * nch * me, nch * me, lane);
-    copy_row(d.eenv_phse + G * nch * me, s.eenv_phse + gc * nch * me, nch * me, lane);
-    copy_row(d.vtmagn + G * ns, s.vtmagn + gc * ns, ns, lane);
-    copy_row(d.vsphse + G * mh, s.vsphse + gc * mh, mh, lane);
-    return;
-  }
-
-  // ---- source-filter part: F0, RD, VTMAGN, VSPHSE
-  const float fa = s.f0[ga], fb = s.f0[gb];
-  const bool va = fa > 0.0f, vb = fb > 0.0f;
-  const int nva = clampi(s.nvsphse[ga], 0, mh), nvb = clampi(s.nvsphse[gb], 0, mh);
-  float* vt = d.vtmagn + G * ns; float* vs = d.vsphse + G * mh;
-  const float* vta = s.vtmagn + ga * ns; const float* vtb = s.vtmagn + gb * ns;
-  const float* vsa = s.vsphse + ga * mh; const float* vsb = s.vsphse + gb * mh;
-  float f0, rd; int nv;
-  if(va && vb) {
-    f0 = lin(fa, fb, r); rd = lin(s.rd[ga], s.rd[gb], r); nv = max(nva, nvb);
-    for(int k = lane; k < ns; k += 64) vt[k] = floor80(lin(vta[k], vtb[k], r));
-    const int nmin = min(nva, nvb);
-    const float* lng = nva >= nvb ? vsa : vsb;
-    for(int k = lane; k < mh; k += 64) vs[k] = k < nmin ? circ(vsa[k], vsb[k], r) : lng[k];
-  } else if(va || vb) {                                   // voicing changes: the voiced side, faded in or out
-    const size_t gv = va ? ga : gb;
-    const float w = va ? 1.0f - r : r;
-    const float fade = fade_db(w);
-    f0 = s.f0[gv]; rd = s.rd[gv]; nv = clampi(s.nvsphse[gv], 0, mh);
-    const float* vtv = s.vtmagn + gv * ns;
-    for(int k = lane; k < ns; k += 64) vt[k] = floor80(vtv[k] + fade);
-    copy_row(vs, s.vsphse + gv * mh, mh, lane);
-  } else {
-    f0 = 0.0f; rd = 1.0f; nv = nva;
-    for(int k = lane; k < ns; k += 64) vt[k] = floor80(vta[k]);
-    copy_row(vs, vsa, mh, lane);
-  }
-  const bool voiced = va || vb;
-
-  // ---- noise part: PSD, EDC, envelopes
-  for(int k = lane; k < np; k += 64) d.psd[G * np + k] = lin(s.psd[ga * np + k], s.psd[gb * np + k], r);
-  for(int k = lane; k < nch; k += 64) d.edc[G * nch + k] = lin(s.edc[ga * nch + k], s.edc[gb * nch + k], r);
-  const int nea = clampi(s.nhar_e[ga], 0, s.maxnhar_e), neb = clampi(s.nhar_e[gb], 0, s.maxnhar_e);
-  const int nemin = min(nea, neb);
-  const size_t gle = nea >= neb ? ga : gb;
-  for(int k = lane; k < nch * me; k += 64) {
-    const int j = k % me;
-    const size_t ia = ga * nch * me + k, ib = gb * nch * me + k, il = gle * nch * me + k;
-    if(j < nemin) {
-      d.eenv_ampl[G * nch * me + k] = lin(s.eenv_ampl[ia], s.eenv_ampl[ib], r);
-      d.eenv_phse[G * nch * me + k] = circ(s.eenv_phse[ia], s.eenv_phse[ib], r);
-    } else {
-      d.eenv_ampl[G * nch * me + k] = s.eenv_ampl[il];
-      d.eenv_phse[G * nch * me + k] = s.eenv_phse[il];
-    }
-  }
-
-  // ---- harmonic model: rebuilt from layer 1 on voiced output frames (llsm_gpu_batch_tolayer0(dst, 1)), frame a's
-  // rows on unvoiced ones
-  if(voiced) {
-    for(int k = lane; k < mh; k += 64) { d.ampl[G * mh + k] = 0.0f; d.phse[G * mh + k] = 0.0f; }
-  } else {
-    copy_row(d.ampl + G * mh, s.ampl + ga * mh, mh, lane);
-    copy_row(d.phse + G * mh, s.phse + ga * mh, mh, lane);
-  }
-  if(lane == 0) {
-    d.f0[G] = f0; d.rd[G] = rd; d.nvsphse[G] = nv; d.nhar_e[G] = max(nea, neb);
-    d.pbpsyn[G] = s.pbpsyn[ga];
-    d.nhar[G] = voiced ? 0 : s.nhar[ga];
-    d.has_hm[G] = voiced ? 0 : s.has_hm[ga];
-  }
-}
-
 // Thread (f, j) of the first sixteen fetches the scalars of source frame j (a, a + 1 of side A; a, a + 1 of side B) of output
 // frame f where the map makes the frame read it; thread f then plans the frame and writes its scalars.
 __global__ __launch_bounds__(kSpThreads) void k_splice(ModRows s, ModRows d, SpliceMap m) {
@@ -364,8 +267,9 @@ __global__ __launch_bounds__(kSpThreads) void k_splice(ModRows s, ModRows d, Spl
     if(mix != 1.0f) { ra = m.ra[g]; sp_pair(s_src[tid][0], s_src[tid][1], ra, mh, s.maxnhar_e, & F.a, & A); }
     if(mix != 0.0f) { rb = m.rb[g]; sp_pair(s_src[tid][2], s_src[tid][3], rb, mh, s.maxnhar_e, & F.b, & B); }
     sp_pair(A, B, mix, mh, s.maxnhar_e, & F.o, & O);
-    // PSDRES: the frame at floor(pos) of side A below mix 0.5, of side B from there on (r == 1 only at an utterance's end)
-    F.gr = mix < 0.5f ? F.ga + (ra == 1.0f) : F.gb + (rb == 1.0f);
+    // PSDRES: the map's frame; without one the frame at floor(pos) of side A below mix 0.5, of side B from there on (r == 1
+    // only at an utterance's end)
+    F.gr = m.gr ? m.gr[g] : (mix < 0.5f ? F.ga + (ra == 1.0f) : F.gb + (rb == 1.0f));
     s_frm[tid] = F;
     d.f0[g] = O.f0; d.rd[g] = O.rd; d.nvsphse[g] = O.nv; d.nhar_e[g] = O.ne; d.nhar[g] = O.nhar; d.has_hm[g] = O.has_hm;
     d.pbpsyn[g] = O.pbpsyn; d.has_psdres[g] = s.has_psdres[F.gr];
@@ -459,12 +363,6 @@ int launch_phase_propagate_theta(LaunchCtx* P, int n_utt, const int* frm_off, co
   double k2pi, float* theta) {
   if(n_utt <= 0) return 0;
   LAUNCH("k_prop_theta", k_prop_theta, dim3(n_utt), dim3(256), 0, frm_off, nfrm, f0, k2pi, theta);
-  return 0;
-}
-
-int launch_retime(LaunchCtx* P, const ModRows& src, const ModRows& dst, const RetimeMap& m) {
-  if(dst.nframes <= 0) return 0;
-  LAUNCH("k_retime", k_retime, dim3(dst.nframes), dim3(64), 0, src, dst, m);
   return 0;
 }
 

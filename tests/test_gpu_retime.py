@@ -476,6 +476,25 @@ def test_retime_is_batch_invariant(ctx):
     want, aux = ref_retime(rows, src.frm_off, sn, dst.frm_off, dn, pos, res)
     assert_retime_rows(whole, want, aux, "synthetic")
     dst.close(); src.close()
+    # and on the smallest shape: a one-frame source, and groups of four output frames that straddle utterances (boundaries
+    # at 3 and 8 of 14 frames), with psdres_src and without
+    sn, dn = np.array([1, 2, 5], np.int32), np.array([3, 5, 6], np.int32)
+    src, rows = synthetic_src(ctx, ao, sn, 2)
+    pos = []
+    for n, m in zip(sn, dn):
+        p = rng.uniform(0, n - 1, m).astype(np.float32)
+        p[:2] = [0, n - 1]                                   # both end points of every utterance
+        pos.append(rng.permutation(p))
+    pos = np.concatenate(pos)
+    res = np.concatenate([rng.integers(0, n, m) for n, m in zip(sn, dn)]).astype(np.int32)
+    for r in (res, None):
+        dst = llsm.Batch(ctx, ao, FS, [0] * 3, dn)
+        dst.retime(src, pos, r)
+        ctx.sync()
+        want, aux = ref_retime(rows, src.frm_off, sn, dst.frm_off, dn, pos, r)
+        assert_retime_rows(rows_of(dst), want, aux, "smallest" if r is None else "smallest, psdres_src")
+        dst.close()
+    src.close()
 
 
 def test_retime_refusals_leave_dst_untouched(ctx):
