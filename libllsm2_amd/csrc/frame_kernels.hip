@@ -17,6 +17,7 @@
 
 #pragma clang fp contract(fast)
 #include "dev_common.h"
+#include "launch.h"                                  // lds_opt_in; these launches carry no profiling hooks (FA_LAUNCH)
 
 namespace lp = llsm_plan;
 extern __shared__ __attribute__((aligned(16))) unsigned char fa_lds[];
@@ -189,8 +190,7 @@ int launch_fa_stft(LaunchCtx* P, const float* x, int nx, const int* center, cons
   if(nfrm <= 0) return 0;
   if(nfft > tw_nmax || nfft < 4 || (nfft & (nfft - 1))) return -1;
   const size_t lds = sizeof(float2) * ((size_t)nfft + nfft / 2);
-  if(lds > 64 * 1024 && hipFuncSetAttribute((const void*)k_fa_stft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return -1;
+  if(lds_opt_in((const void*)k_fa_stft, lds) != hipSuccess) return -1;
   FA_LAUNCH(k_fa_stft, dim3(nfrm), dim3(WAVE), lds, x, nx, center, winsize, nfft, blackman, mode, scale, tw, tw_nmax, spec, phse);
   return 0;
 }

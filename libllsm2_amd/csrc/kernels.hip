@@ -4017,19 +4017,14 @@ int launch_harm_speech(LaunchCtx* P, const BatchDev& d, float min_f0) {
 
 int launch_harm_env(LaunchCtx* P, const BatchDev& d, const float* ce, size_t ce_stride) {
   if(d.nframes == 0) return 0;
-#define HE_ARGS ce, ce_stride, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, d.thop, d.fs, \
-    d.rel_winsize, d.nchannel, d.maxnhar_e, d.nhar_e, d.edc, d.eenv_ampl, d.eenv_phse
-  if(d.nchannel <= 4 && d.maxnhar_e <= 4)
-    LAUNCH("k_harm_env", (k_harm_env<4, 4>), dim3(d.nframes), dim3(WAVE), 0, HE_ARGS);
-  else if(d.nchannel <= 4 && d.maxnhar_e <= 8)
-    LAUNCH("k_harm_env", (k_harm_env<4, 8>), dim3(d.nframes), dim3(WAVE), 0, HE_ARGS);
-  else if(d.nchannel <= 8 && d.maxnhar_e <= 8)
-    LAUNCH("k_harm_env", (k_harm_env<8, 8>), dim3(d.nframes), dim3(WAVE), 0, HE_ARGS);
-  else return -1001;
-#undef HE_ARGS
-  return 0;
+  if(d.nchannel > 8 || d.maxnhar_e > 8) return -1001;
+  return with_env_shape(d.nchannel, d.maxnhar_e, [&](auto nch, auto me) {
+    LAUNCH("k_harm_env", (k_harm_env<nch, me>), dim3(d.nframes), dim3(WAVE), 0,
+      ce, ce_stride, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, d.thop, d.fs,
+      d.rel_winsize, d.nchannel, d.maxnhar_e, d.nhar_e, d.edc, d.eenv_ampl, d.eenv_phse);
+    return 0;
+  });
 }
-
 
 int launch_filtfilt(LaunchCtx* P, const FiltJob* jobs, int njobs, const FiltSectionD* sections) {
   if(njobs == 0) return 0;
@@ -4044,24 +4039,15 @@ static int fft_grid(int np) { return np < 2048 ? np : 2048; }
 // 1024-point ones -- a fixed 2048 left half the slots of the latter empty: k_psd_frames_wf 0.248 -> 0.194 ms), at least 2048.
 template <class K>
 static int persistent_grid(K kernel, size_t lds, int np) {
-  static std::mutex mx; static std::map<std::pair<const void*, size_t>, int> cache;
-  int resident = 0;
-  {
-    std::lock_guard<std::mutex> lock(mx);
-    auto it = cache.find({(const void*)kernel, lds});
-    if(it != cache.end()) resident = it -> second;
-    else {
-      int per_cu = 0, dev = 0, cus = 0;
-      if(hipOccupancyMaxActiveBlocksPerMultiprocessor(& per_cu, kernel, WAVE, lds) != hipSuccess) { per_cu = 0; (void)hipGetLastError(); }
-      if(hipGetDevice(& dev) != hipSuccess || hipDeviceGetAttribute(& cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { cus = 0; (void)hipGetLastError(); }
-      resident = per_cu * cus;
-      cache[{(const void*)kernel, lds}] = resident;
-    }
-  }
-  const int g = resident > 2048 ? resident : 2048;
-  return np < g ? np : g;
+  return std::min(np, std::max(resident_blocks((const void*)kernel, WAVE, lds), 2048));
 }
 static int npairs_of(const BatchDev& d) { return d.pairs ? d.npairs : (d.nframes + 1) / 2; }
+// The transforms with a register-resident form that the frame kernels instantiate (4096 points = 128 data VGPRs per
+// lane spill at 2 waves / SIMD: the LDS kernels serve those): f(int_c<logN>), or `miss` without calling f.  A launcher
+// returns 0, a hipError_t or a small negative value: NO_WF is none of them, for launchers that go on to another kernel.
+constexpr int NO_WF = INT_MIN;
+template <class F>
+static int with_wf(int logN, int miss, F&& f) { return pick_int<8, 9, 10, 11>(logN, miss, f); }
 
 int launch_spgm_env(LaunchCtx* P, const BatchDev& d, int nwin_psd, int N, int logN,
   int nfft_psd, float norm_base, const float2* tw, int tw_nmax, float* env_out, int2* fix_list, int* fix_count, int which) {
@@ -4072,71 +4058,67 @@ int launch_spgm_env(LaunchCtx* P, const BatchDev& d, int nwin_psd, int N, int lo
   // (4096 points = 128 data VGPRs per lane spill at 2 waves / SIMD: the LDS kernel serves those)
   int logF = -1;
   if(nfft_psd <= N && N % nfft_psd == 0) { logF = 0; while((nfft_psd << logF) < N) logF ++; }
-#define WF_CASE(LN, LF) \
-  if(logN == LN && logF == LF) { \
-    constexpr int e1 = wf_lds_elems<LN>(), e2 = wf_lds_elems<LN - LF>(); \
-    if(which & 1) \
-    LAUNCH("k_spgm_env_wf", (k_spgm_env_wf<LN, LF, false>), dim3(persistent_grid(k_spgm_env_wf<LN, LF, false>, sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS, npairs_of(d))), dim3(WAVE), \
-      sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS, d.x, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, \
-      d.nframes, d.thop, d.fs, nwin_psd, norm_base, env_out, d.pairs, npairs_of(d), fix_list, fix_count); \
-    if((which & 2) && fix_list) /* the listed pairs again, exact edge bins (a few dozen wavefronts find work, if any) */ \
-      LAUNCH("k_spgm_env_fix", (k_spgm_env_wf<LN, LF, true>), dim3(npairs_of(d) < 256 ? npairs_of(d) : 256), dim3(WAVE), \
-        sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS, d.x, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, \
-        d.nframes, d.thop, d.fs, nwin_psd, norm_base, env_out, d.pairs, npairs_of(d), fix_list, fix_count); \
-    return 0; \
-  }
-  WF_CASE(9, 0) WF_CASE(9, 1)
-  WF_CASE(10, 0) WF_CASE(10, 1) WF_CASE(10, 2)
-  WF_CASE(11, 0) WF_CASE(11, 1) WF_CASE(11, 2)
-#undef WF_CASE
+  const int np = npairs_of(d);
+  const int rc = pick_int<9, 10, 11>(logN, NO_WF, [&](auto ln) { return pick_int<0, 1, 2>(logF, NO_WF, [&](auto lf) {
+    constexpr int LN = decltype(ln)::value, LF = decltype(lf)::value;
+    if constexpr(LN == 9 && LF == 2) return NO_WF;    // a 128-point half has no instantiation: the LDS kernel below
+    else {
+      constexpr int e1 = wf_lds_elems<LN>(), e2 = wf_lds_elems<LN - LF>();
+      const size_t lds = sizeof(float2) * (e1 > e2 ? e1 : e2) + SPGM_SEED_LDS;
+      auto pass = [&](const char* name, auto fix, int grid) {
+        LAUNCH(name, (k_spgm_env_wf<LN, LF, fix>), dim3(grid), dim3(WAVE), lds, d.x, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0,
+          d.nframes, d.thop, d.fs, nwin_psd, norm_base, env_out, d.pairs, np, fix_list, fix_count);
+        return 0;
+      };
+      int e = 0;
+      if(which & 1) e = pass("k_spgm_env_wf", std::false_type{}, persistent_grid(k_spgm_env_wf<LN, LF, false>, lds, np));
+      // the listed pairs again, exact edge bins (a few dozen wavefronts find work, if any)
+      if(! e && (which & 2) && fix_list) e = pass("k_spgm_env_fix", std::true_type{}, np < 256 ? np : 256);
+      return e;
+    }
+  }); });
+  if(rc != NO_WF) return rc;
   if(!(which & 1)) return 0;
   size_t lds = (size_t)(N + N / 2) * sizeof(float2);
-  LAUNCH("k_spgm_env", k_spgm_env, dim3(fft_grid(npairs_of(d))), dim3(WAVE), lds,
+  LAUNCH("k_spgm_env", k_spgm_env, dim3(fft_grid(np)), dim3(WAVE), lds,
     d.x, d.x_off, d.nx, d.frm_utt, d.frm_off, d.f0, d.nframes, d.thop, d.fs, nwin_psd,
-    N, logN, nfft_psd, norm_base, tw, tw_nmax, env_out, d.pairs, npairs_of(d));
+    N, logN, nfft_psd, norm_base, tw, tw_nmax, env_out, d.pairs, np);
   return 0;
 }
 
 int launch_wf_selftest(LaunchCtx* P, int logN, const float2* in, float2* out, int count, int inverse) {
-#define WF_CASE(LN) \
-  if(logN == LN) { \
-    LAUNCH("k_wf_selftest", (k_wf_selftest<LN>), dim3(count), dim3(WAVE), \
-      sizeof(float2) * wf_lds_elems<LN>(), in, out, inverse); \
-    return 0; \
-  }
-  WF_CASE(8) WF_CASE(9) WF_CASE(10) WF_CASE(11) WF_CASE(12)
-#undef WF_CASE
-  return -1;
+  return pick_int<8, 9, 10, 11, 12>(logN, -1, [&](auto ln) {
+    LAUNCH("k_wf_selftest", (k_wf_selftest<ln>), dim3(count), dim3(WAVE), sizeof(float2) * wf_lds_elems<ln>(), in, out, inverse);
+    return 0;
+  });
 }
 
 int launch_psd_frames(LaunchCtx* P, const BatchDev& d, const float* xres, int nwin,
   const float* win, float inv_wpow, int N, int logN, const float2* tw, int tw_nmax,
   float* psd_log) {
   if(d.nframes == 0) return 0;
-#define WF_CASE(LN) \
-  if(logN == LN) { \
-    LAUNCH("k_psd_frames_wf", (k_psd_frames_wf<LN>), dim3(persistent_grid(k_psd_frames_wf<LN>, sizeof(float2) * wf_lds_elems<LN>(), npairs_of(d))), dim3(WAVE), \
-      sizeof(float2) * wf_lds_elems<LN>(), xres, d.x_off, d.nx, d.frm_utt, d.frm_off, d.nframes, \
-      d.thop, d.fs, nwin, win, inv_wpow, psd_log, d.pairs, npairs_of(d)); \
-    return 0; \
-  }
-  WF_CASE(8) WF_CASE(9) WF_CASE(10) WF_CASE(11)
-#undef WF_CASE
-  if(N > LLSM_LDS_FFT_MAX) {                          // beyond the LDS: global scratch + the big twiddle table (engine.cpp)
-    const int grid = std::min(fft_grid(npairs_of(d)), llsm_big_fft_grid((size_t)N));
-    if(! P -> tw_big || N > P -> tw_big_nmax || P -> big_scratch_elems < (size_t)grid * N) return -1;
-    LAUNCH("k_psd_frames", k_psd_frames, dim3(grid), dim3(WAVE), 64,
-      xres, d.x_off, d.nx, d.frm_utt, d.frm_off, d.nframes, d.thop, d.fs, nwin, win, inv_wpow,
-      N, logN, P -> tw_big, P -> tw_big_nmax, psd_log, d.pairs, npairs_of(d), P -> big_scratch);
+  const int np = npairs_of(d);
+  const int rc = with_wf(logN, NO_WF, [&](auto ln) {
+    const size_t lds = sizeof(float2) * wf_lds_elems<ln>();
+    LAUNCH("k_psd_frames_wf", (k_psd_frames_wf<ln>), dim3(persistent_grid(k_psd_frames_wf<ln>, lds, np)), dim3(WAVE), lds,
+      xres, d.x_off, d.nx, d.frm_utt, d.frm_off, d.nframes, d.thop, d.fs, nwin, win, inv_wpow, psd_log, d.pairs, np);
     return 0;
+  });
+  if(rc != NO_WF) return rc;
+  auto lds_form = [&](int grid, size_t lds, const float2* t, int t_nmax, float2* scratch) {
+    LAUNCH("k_psd_frames", k_psd_frames, dim3(grid), dim3(WAVE), lds,
+      xres, d.x_off, d.nx, d.frm_utt, d.frm_off, d.nframes, d.thop, d.fs, nwin, win, inv_wpow,
+      N, logN, t, t_nmax, psd_log, d.pairs, np, scratch);
+    return 0;
+  };
+  if(N > LLSM_LDS_FFT_MAX) {                          // beyond the LDS: global scratch + the big twiddle table (engine.cpp)
+    const int grid = std::min(fft_grid(np), llsm_big_fft_grid((size_t)N));
+    if(! P -> tw_big || N > P -> tw_big_nmax || P -> big_scratch_elems < (size_t)grid * N) return -1;
+    return lds_form(grid, 64, P -> tw_big, P -> tw_big_nmax, P -> big_scratch);
   }
-  size_t lds = (size_t)(N + N / 2) * sizeof(float2);
-  if(lds > 64 * 1024 &&
-     hipFuncSetAttribute((const void*)k_psd_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-  LAUNCH("k_psd_frames", k_psd_frames, dim3(fft_grid(npairs_of(d))), dim3(WAVE), lds,
-    xres, d.x_off, d.nx, d.frm_utt, d.frm_off, d.nframes, d.thop, d.fs, nwin, win, inv_wpow,
-    N, logN, tw, tw_nmax, psd_log, d.pairs, npairs_of(d), (float2*)nullptr);
-  return 0;
+  const size_t lds = (size_t)(N + N / 2) * sizeof(float2);
+  if(lds_opt_in((const void*)k_psd_frames, lds) != hipSuccess) return -1;
+  return lds_form(fft_grid(np), lds, tw, tw_nmax, nullptr);
 }
 
 int launch_kalman(LaunchCtx* P, const BatchDev& d, const float* env, const float* psd_log,
@@ -4159,15 +4141,11 @@ int launch_white(LaunchCtx* P, const BatchDev& d, float* white, int ntemplate_ex
 int launch_env_frames(LaunchCtx* P, const BatchDev& d, float fs_syn, int nwin,
   const float* win, float* envf) {
   if(d.nframes == 0) return 0;
-#define EF_ARGS d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, fs_syn, nwin, win, envf
-  if(d.nchannel <= 4 && d.maxnhar_e <= 4)
-    LAUNCH("k_env_frames", (k_env_frames<4, 4>), dim3(d.nframes), dim3(WAVE), 0, EF_ARGS);
-  else if(d.nchannel <= 4)
-    LAUNCH("k_env_frames", (k_env_frames<4, 8>), dim3(d.nframes), dim3(WAVE), 0, EF_ARGS);
-  else
-    LAUNCH("k_env_frames", (k_env_frames<8, 8>), dim3(d.nframes), dim3(WAVE), 0, EF_ARGS);
-#undef EF_ARGS
-  return 0;
+  return with_env_shape(d.nchannel, d.maxnhar_e, [&](auto nch, auto me) {
+    LAUNCH("k_env_frames", (k_env_frames<nch, me>), dim3(d.nframes), dim3(WAVE), 0,
+      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, fs_syn, nwin, win, envf);
+    return 0;
+  });
 }
 
 // The analysed rows of every frame gathered into ONE record per frame (packed.h): what the object path ships to the host so
@@ -4338,20 +4316,6 @@ bool excite_units_ok(const BatchDev& d, int nwin_env, float fs_syn) {
     256.0 * EXU_Q / hop + 6.0 <= EXU_SLOTS;
 }
 int excite_unit_samples() { return 256 * EXU_Q; }
-// Workgroups of k_excite_units: one per resident slot (the kernel is a loop over units), at most one per unit.
-template <class K>
-static int resident_blocks(K kernel, int block, size_t lds) {
-  static std::mutex mx; static std::map<const void*, int> cache;
-  std::lock_guard<std::mutex> lock(mx);
-  auto it = cache.find((const void*)kernel);
-  if(it != cache.end()) return it -> second;
-  int per_cu = 0, dev = 0, cus = 0;
-  if(hipOccupancyMaxActiveBlocksPerMultiprocessor(& per_cu, kernel, block, lds) != hipSuccess) { per_cu = 0; (void)hipGetLastError(); }
-  if(hipGetDevice(& dev) != hipSuccess || hipDeviceGetAttribute(& cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { cus = 0; (void)hipGetLastError(); }
-  const int r = std::max(per_cu * cus, 256);
-  cache[(const void*)kernel] = r;
-  return r;
-}
 
 int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int ntemplate_ext,
   const int2* hits, const float2* cplx, int nwin_env, const float* win, int nch_active,
@@ -4360,27 +4324,23 @@ int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int
   if(d.n_utt == 0 || max_len == 0) return 0;
   // default: persistent units (k_excite_units), which form the complex amplitudes themselves; $LLSM_GPU_EXCITE4 set: the
   // per-sample kernel after k_env_params (the caller launches it when cplx != NULL)
-#define EX_ARGS colored, ntemplate_ext, hits, cplx, d.edc, d.f0, nwin_env, win, d.nchannel, d.maxnhar_e, \
-    nch_active, d.frm_off, d.nfrm, out_off, out_len, d.thop, fs_syn, yexc
   if(! cplx) {
     if(nunits == 0) return 0;
-    if(d.maxnhar_e <= 4) {
-      const int g = std::min(nunits, resident_blocks(k_excite_units<4, 4>, 256, 0));
-      LAUNCH("k_excite_units", (k_excite_units<4, 4>), dim3(g), dim3(256), 0, units, nunits, colored, ntemplate_ext, hits,
+    // excite_units_ok admits up to 4 channels, so only the envelope harmonics choose here
+    return pick_int<4, 8>(d.maxnhar_e <= 4 ? 4 : 8, 0, [&](auto me) {
+      // one workgroup per resident slot (the kernel is a loop over units), at least 256, at most one per unit
+      const int g = std::min(nunits, std::max(resident_blocks((const void*)k_excite_units<4, me>, 256, 0), 256));
+      LAUNCH("k_excite_units", (k_excite_units<4, me>), dim3(g), dim3(256), 0, units, nunits, colored, ntemplate_ext, hits,
         d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, nwin_env, win, d.nchannel, d.maxnhar_e, nch_active, d.thop, fs_syn, yexc);
-    } else {
-      const int g = std::min(nunits, resident_blocks(k_excite_units<4, 8>, 256, 0));
-      LAUNCH("k_excite_units", (k_excite_units<4, 8>), dim3(g), dim3(256), 0, units, nunits, colored, ntemplate_ext, hits,
-        d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, nwin_env, win, d.nchannel, d.maxnhar_e, nch_active, d.thop, fs_syn, yexc);
-    }
-    return 0;
+      return 0;
+    });
   }
-  const dim3 grid((max_len + 255) / 256, d.n_utt);
-  if(d.nchannel <= 4 && d.maxnhar_e <= 4) LAUNCH("k_excite_env", (k_excite_env<4, 4>), grid, dim3(256), 0, EX_ARGS);
-  else if(d.nchannel <= 4) LAUNCH("k_excite_env", (k_excite_env<4, 8>), grid, dim3(256), 0, EX_ARGS);
-  else LAUNCH("k_excite_env", (k_excite_env<8, 8>), grid, dim3(256), 0, EX_ARGS);
-#undef EX_ARGS
-  return 0;
+  return with_env_shape(d.nchannel, d.maxnhar_e, [&](auto nch, auto me) {
+    LAUNCH("k_excite_env", (k_excite_env<nch, me>), dim3((max_len + 255) / 256, d.n_utt), dim3(256), 0,
+      colored, ntemplate_ext, hits, cplx, d.edc, d.f0, nwin_env, win, d.nchannel, d.maxnhar_e,
+      nch_active, d.frm_off, d.nfrm, out_off, out_len, d.thop, fs_syn, yexc);
+    return 0;
+  });
 }
 
 int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
@@ -4388,35 +4348,30 @@ int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
   const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax,
   float* nframes_out, int* live, int rt) {
   if(d.nframes == 0) return 0;
-#define WF_CASE(LN) \
-  if(logN == LN) { \
-    LAUNCH("k_noise_filter_wf", (k_noise_filter_wf<LN>), dim3(fft_grid(rt ? (d.nframes + 1) / 2 : npairs_of(d)) * (NF_WPE / 2)), dim3(WAVE), \
-      sizeof(float2) * (wf_lds_elems<LN>() + d.npsd) + (sizeof(float) << LN), yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes, \
-      d.psd, d.psdres, d.has_psdres, d.npsd, fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, \
-      nframes_out, live, rt, rt ? nullptr : d.pairs, rt ? (d.nframes + 1) / 2 : npairs_of(d)); \
-    return 0; \
-  }
-  WF_CASE(8) WF_CASE(9) WF_CASE(10) WF_CASE(11)      // 4096 and up: the LDS kernel (register budget)
-#undef WF_CASE
   const int np = rt ? (d.nframes + 1) / 2 : npairs_of(d);
+  const auto pairs = rt ? nullptr : d.pairs;
+  const int rc = with_wf(logN, NO_WF, [&](auto ln) {         // 4096 and up: the LDS kernel (register budget)
+    LAUNCH("k_noise_filter_wf", (k_noise_filter_wf<ln>), dim3(fft_grid(np) * (NF_WPE / 2)), dim3(WAVE),
+      sizeof(float2) * (wf_lds_elems<ln>() + d.npsd) + (sizeof(float) << ln), yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes,
+      d.psd, d.psdres, d.has_psdres, d.npsd, fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, nframes_out, live, rt, pairs, np);
+    return 0;
+  });
+  if(rc != NO_WF) return rc;
+  auto lds_form = [&](int grid, size_t lds, const float2* t, int t_nmax, float2* scratch) {
+    LAUNCH("k_noise_filter", k_noise_filter, dim3(grid), dim3(WAVE), lds,
+      yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes, d.psd, d.psdres, d.has_psdres,
+      d.npsd, fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, N, logN, t, t_nmax,
+      nframes_out, live, rt, pairs, np, scratch);
+    return 0;
+  };
   if(N > LLSM_LDS_FFT_MAX) {                          // beyond the LDS: global scratch + the big twiddle table (engine.cpp)
     const int grid = std::min(fft_grid(np), llsm_big_fft_grid((size_t)N + N / 2 + 1));
     if(! P -> tw_big || N > P -> tw_big_nmax || P -> big_scratch_elems < (size_t)grid * (N + N / 2 + 1)) return -1;
-    LAUNCH("k_noise_filter", k_noise_filter, dim3(grid), dim3(WAVE), 64,
-      yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes, d.psd, d.psdres, d.has_psdres,
-      d.npsd, fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, N, logN, P -> tw_big, P -> tw_big_nmax,
-      nframes_out, live, rt, rt ? nullptr : d.pairs, np, P -> big_scratch);
-    return 0;
+    return lds_form(grid, 64, P -> tw_big, P -> tw_big_nmax, P -> big_scratch);
   }
-  size_t lds = (size_t)(N + N / 2 + N / 2 + 1) * sizeof(float2) + 16 * sizeof(float);
-  lds = (lds + 15) / 16 * 16;
-  if(lds > 64 * 1024 &&
-     hipFuncSetAttribute((const void*)k_noise_filter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-  LAUNCH("k_noise_filter", k_noise_filter, dim3(fft_grid(np)), dim3(WAVE), lds,
-    yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes, d.psd, d.psdres, d.has_psdres,
-    d.npsd, fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, N, logN, tw, tw_nmax,
-    nframes_out, live, rt, rt ? nullptr : d.pairs, np, (float2*)nullptr);
-  return 0;
+  const size_t lds = nf_pair_lds(N, 0);
+  if(lds_opt_in((const void*)k_noise_filter, lds) != hipSuccess) return -1;
+  return lds_form(fft_grid(np), lds, tw, tw_nmax, nullptr);
 }
 
 // Fused noise filter + overlap-add; returns -2 when the transform size has no fused kernel
@@ -4425,29 +4380,22 @@ int launch_noise_filter_ola(LaunchCtx* P, const BatchDev& d, const int4* units, 
   const float* yexc, const int* out_off, const int* out_len, float fnyq_conf, float fs_syn, int nwin,
   const float* win, int wsym, float inv_wsqr, int logN, float* ynoise) {
   if(nunits == 0) return 0;
-#define NFO_ARGS units, nunits, halo, yexc, out_off, out_len, d.frm_off, d.nfrm, d.psd, d.psdres, d.has_psdres, d.npsd, fnyq_conf, \
-      d.thop, fs_syn, nwin, win, wsym, inv_wsqr, ynoise
-#define WF_CASE(LN) \
-  if(logN == LN) { \
-    /* target rows inside the exchange buffer when they fit there and in NF_TQ registers per lane */ \
-    if(wsym > 0 && d.npsd <= NF_TQ * WAVE && (1 << (LN - 1)) + 7 + d.npsd <= wf_lds_elems<LN>()) { \
-      if(d.npsd <= 2 * WAVE) { \
-        LAUNCH("k_noise_filter_ola", (k_noise_filter_ola<LN, true, 2>), dim3(nunits), dim3(WAVE), \
-          sizeof(float2) * wf_lds_elems<LN>() + (sizeof(float) << LN) + sizeof(float) * (wsym / 2 + 1), NFO_ARGS); \
-      } else { \
-        LAUNCH("k_noise_filter_ola", (k_noise_filter_ola<LN, true, NF_TQ>), dim3(nunits), dim3(WAVE), \
-          sizeof(float2) * wf_lds_elems<LN>() + (sizeof(float) << LN) + sizeof(float) * (wsym / 2 + 1), NFO_ARGS); \
-      } \
-    } else { \
-      LAUNCH("k_noise_filter_ola", (k_noise_filter_ola<LN, false, 1>), dim3(nunits), dim3(WAVE), \
-        sizeof(float2) * (wf_lds_elems<LN>() + d.npsd) + (sizeof(float) << LN), NFO_ARGS); \
-    } \
-    return 0; \
-  }
-  WF_CASE(8) WF_CASE(9) WF_CASE(10) WF_CASE(11)
-#undef WF_CASE
-#undef NFO_ARGS
-  return -2;
+  return with_wf(logN, -2, [&](auto ln) {
+    constexpr int LN = ln;
+    auto go = [&](auto alias, auto tq, size_t lds) {
+      LAUNCH("k_noise_filter_ola", (k_noise_filter_ola<LN, alias, tq>), dim3(nunits), dim3(WAVE), lds,
+        units, nunits, halo, yexc, out_off, out_len, d.frm_off, d.nfrm, d.psd, d.psdres, d.has_psdres, d.npsd, fnyq_conf,
+        d.thop, fs_syn, nwin, win, wsym, inv_wsqr, ynoise);
+      return 0;
+    };
+    const size_t lds = sizeof(float2) * wf_lds_elems<LN>() + (sizeof(float) << LN);
+    // target rows inside the exchange buffer when they fit there and in NF_TQ registers per lane
+    if(wsym > 0 && d.npsd <= NF_TQ * WAVE && (1 << (LN - 1)) + 7 + d.npsd <= wf_lds_elems<LN>()) {
+      const size_t lds_alias = lds + sizeof(float) * (wsym / 2 + 1);
+      return d.npsd <= 2 * WAVE ? go(std::true_type{}, int_c<2>{}, lds_alias) : go(std::true_type{}, int_c<NF_TQ>{}, lds_alias);
+    }
+    return go(std::false_type{}, int_c<1>{}, lds + sizeof(float2) * d.npsd);
+  });
 }
 
 int launch_ola_noise_mix(LaunchCtx* P, const BatchDev& d, const float* nframes_in,
@@ -4495,6 +4443,13 @@ int launch_rt_mix(LaunchCtx* P, int S, float* noiser, const float* sinr, int cap
   return 0;
 }
 
+// the <NCH, ME, NTS> instantiation of a hop kernel: the envelope shape of the streams and the column tiles of their frames
+template <class F>
+static int with_rt_shape(const BatchDev& d, const SynthTiles& t, F&& f) {
+  return with_env_shape(d.nchannel, d.maxnhar_e, [&](auto nch, auto me) {
+    return with_tiles(t.NT, [&](auto nts) { return f(nch, me, nts); });
+  });
+}
 // llsmrt, one hop in two launches (k_rt_front, k_rt_back).  d: the per-stream rows as a batch of S one-frame "utterances".
 int launch_rt_front(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, const float* f0_sin, const float* cyc_shift,
   float* envf, float* frames_sin, int lds_harmonics, float* mod, float* sinr, float* noiser, int cap, int mod_curr,
@@ -4506,27 +4461,15 @@ int launch_rt_front(LaunchCtx* P, const BatchDev& d, int nwin, const float* win,
   if(host) hr = *host;
   RtPbpArgs pa; std::memset(& pa, 0, sizeof(pa));
   if(pbp) pa = *pbp;
-  int T = ((nwin + 15) / 16 + 2 + 31) / 32;
-  int NT = T;
-  if(T > 4) { T = (T + 3) / 4 * 4; NT = 4; }
-  const int L = 32 * T - 2;
+  const SynthTiles t = synth_tiles(nwin);
   const size_t lds = (lds_harmonics + 4) * sizeof(float2);
-#define RF_ARGS d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, envf, \
-    f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, L, cyc_shift, frames_sin, mod, sinr, noiser, cap, mod_curr, sin_curr, \
-    noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame, hr, d.npsd, d.psd, pa
-#define RF_CASE(NCH, ME) \
-  switch(NT) { \
-    case 1: LAUNCH("k_rt_front", (k_rt_front<NCH, ME, 1>), dim3(S), dim3(256), lds, RF_ARGS); break; \
-    case 2: LAUNCH("k_rt_front", (k_rt_front<NCH, ME, 2>), dim3(S), dim3(256), lds, RF_ARGS); break; \
-    case 3: LAUNCH("k_rt_front", (k_rt_front<NCH, ME, 3>), dim3(S), dim3(256), lds, RF_ARGS); break; \
-    default: LAUNCH("k_rt_front", (k_rt_front<NCH, ME, 4>), dim3(S), dim3(256), lds, RF_ARGS); break; \
-  }
-  if(d.nchannel <= 4 && d.maxnhar_e <= 4) { RF_CASE(4, 4) }
-  else if(d.nchannel <= 4) { RF_CASE(4, 8) }
-  else { RF_CASE(8, 8) }
-#undef RF_CASE
-#undef RF_ARGS
-  return 0;
+  return with_rt_shape(d, t, [&](auto nch, auto me, auto nts) {
+    LAUNCH("k_rt_front", (k_rt_front<nch, me, nts>), dim3(S), dim3(256), lds,
+      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, envf,
+      f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, cyc_shift, frames_sin, mod, sinr, noiser, cap, mod_curr, sin_curr,
+      noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame, hr, d.npsd, d.psd, pa);
+    return 0;
+  });
 }
 int launch_rt_back(LaunchCtx* P, const BatchDev& d, const float* exc_frame, float fnyq_conf, float fs_syn, int nwin,
   const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax, float* nframes, int* live,
@@ -4534,9 +4477,7 @@ int launch_rt_back(LaunchCtx* P, const BatchDev& d, const float* exc_frame, floa
   float* out) {
   const int S = d.nframes;
   if(S == 0) return 0;
-  size_t lds = (size_t)(N + N / 2 + N / 2 + 1 + d.npsd) * sizeof(float2) + 16 * sizeof(float);
-  lds = (lds + 15) / 16 * 16;
-  LAUNCH("k_rt_back", k_rt_back, dim3((S + 1) / 2), dim3(256), lds, exc_frame, S, d.psd, d.psdres, d.has_psdres, d.npsd,
+  LAUNCH("k_rt_back", k_rt_back, dim3((S + 1) / 2), dim3(256), nf_pair_lds(N, d.npsd), exc_frame, S, d.psd, d.psdres, d.has_psdres, d.npsd,
     fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, N, logN, tw, tw_nmax, nframes, live, noiser, sinr, cap, noise_curr,
     sin_curr, sin_pos, next_nhop, out_stride, out);
   return 0;
@@ -4555,23 +4496,17 @@ int launch_rt_hop(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, c
   if(host) hr = *host;
   RtPbpArgs pa; std::memset(& pa, 0, sizeof(pa));
   if(pbp) pa = *pbp;
-  int T = ((nwin + 15) / 16 + 2 + 31) / 32;
-  int NT = T;
-  if(T > 4) { T = (T + 3) / 4 * 4; NT = 4; }
-  const int L = 32 * T - 2;
+  const SynthTiles t = synth_tiles(nwin);
   const int lds_half = lds_harmonics + 4;
-  size_t lds_back = (size_t)(N + N / 2 + N / 2 + 1 + d.npsd) * sizeof(float2) + 16 * sizeof(float);
-  size_t lds = std::max((size_t)2 * lds_half * sizeof(float2), lds_back);
-  lds = (lds + 15) / 16 * 16;
+  const size_t lds = std::max((size_t)2 * lds_half * sizeof(float2), nf_pair_lds(N, d.npsd));   // both multiples of 16
   if(lds > 64 * 1024) return -1002;
   // the on-chip form (k_rt_hop2) where its per-thread slots and its LDS fit
   const bool hop2_ok = on_chip;
   {
     const int nx0 = std::max(N, 2 * lds_half);
     const int me_rt = d.maxnhar_e > 0 ? d.maxnhar_e : 1;
-    size_t lds2 = (size_t)(nx0 + N / 2 + N / 2 + 1 + d.npsd) * sizeof(float2) + 16 * sizeof(float) +
-      ((size_t)2 * d.nchannel * nwin + 5 * (size_t)nwin + 2 * (size_t)(d.nchannel + 2 * d.nchannel * me_rt) + 8) * sizeof(float);
-    lds2 = (lds2 + 15) / 16 * 16;
+    const size_t lds2 = nf_pair_lds(N, d.npsd, (size_t)(nx0 - N) * sizeof(float2) +
+      ((size_t)2 * d.nchannel * nwin + 5 * (size_t)nwin + 2 * (size_t)(d.nchannel + 2 * d.nchannel * me_rt) + 8) * sizeof(float));
     const int nhop_now = nwin / 2;
     if(hop2_ok && nwin == 2 * nhop_now && nwin <= 256 * RT2_JW && nhop_now <= 512 && N <= 256 * 2 * RT2_JN && N > nhop_now &&
        next_nhop <= 512 && next_nhop <= N && N < cap && nwin < cap && nhop_now < ntemplate && d.nchannel * me_rt <= 256 &&
@@ -4584,42 +4519,24 @@ int launch_rt_hop(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, c
       RtRingBase rb;
       rb.mod0 = ring_host(mod_curr, -nwin); rb.sin0 = ring_host(sin_curr, -nwin); rb.exc0 = ring_host(exc_curr, -nwin);
       rb.noi0 = ring_host(noise_curr, -N); rb.out0 = ring_host(sin_curr, sin_pos); rb.tpl0 = exc_cycle % ntemplate;
-#define RH2_ARGS d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, \
-    f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, L, cyc_shift, mod, sinr, noiser, cap, mod_curr, sin_curr, \
-    noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, hr, d.npsd, d.psd, lds_half, \
-    S, d.psdres, d.has_psdres, fnyq_conf, inv_wsqr, N, logN, tw, tw_nmax, sin_pos, next_nhop, out_stride, out, pa, early_out, rb
-#define RH2_CASE(NCH, ME) \
-  switch(NT) { \
-    case 1: LAUNCH("k_rt_hop2", (k_rt_hop2<NCH, ME, 1>), dim3((S + 1) / 2), dim3(512), lds2, RH2_ARGS); break; \
-    case 2: LAUNCH("k_rt_hop2", (k_rt_hop2<NCH, ME, 2>), dim3((S + 1) / 2), dim3(512), lds2, RH2_ARGS); break; \
-    case 3: LAUNCH("k_rt_hop2", (k_rt_hop2<NCH, ME, 3>), dim3((S + 1) / 2), dim3(512), lds2, RH2_ARGS); break; \
-    default: LAUNCH("k_rt_hop2", (k_rt_hop2<NCH, ME, 4>), dim3((S + 1) / 2), dim3(512), lds2, RH2_ARGS); break; \
-  }
-      if(d.nchannel <= 4 && d.maxnhar_e <= 4) { RH2_CASE(4, 4) }
-      else if(d.nchannel <= 4) { RH2_CASE(4, 8) }
-      else { RH2_CASE(8, 8) }
-#undef RH2_CASE
-#undef RH2_ARGS
-      return 0;
+      return with_rt_shape(d, t, [&](auto nch, auto me, auto nts) {
+        LAUNCH("k_rt_hop2", (k_rt_hop2<nch, me, nts>), dim3((S + 1) / 2), dim3(512), lds2,
+          d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win,
+          f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, cyc_shift, mod, sinr, noiser, cap, mod_curr, sin_curr,
+          noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, hr, d.npsd, d.psd, lds_half,
+          S, d.psdres, d.has_psdres, fnyq_conf, inv_wsqr, N, logN, tw, tw_nmax, sin_pos, next_nhop, out_stride, out, pa, early_out, rb);
+        return 0;
+      });
     }
   }
-#define RH_ARGS d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, envf, \
-    f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, L, cyc_shift, frames_sin, mod, sinr, noiser, cap, mod_curr, sin_curr, \
-    noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame, hr, d.npsd, d.psd, lds_half, \
-    S, d.psdres, d.has_psdres, fnyq_conf, inv_wsqr, N, logN, tw, tw_nmax, nframes, live, sin_pos, next_nhop, out_stride, out, pa
-#define RH_CASE(NCH, ME) \
-  switch(NT) { \
-    case 1: LAUNCH("k_rt_hop", (k_rt_hop<NCH, ME, 1>), dim3((S + 1) / 2), dim3(512), lds, RH_ARGS); break; \
-    case 2: LAUNCH("k_rt_hop", (k_rt_hop<NCH, ME, 2>), dim3((S + 1) / 2), dim3(512), lds, RH_ARGS); break; \
-    case 3: LAUNCH("k_rt_hop", (k_rt_hop<NCH, ME, 3>), dim3((S + 1) / 2), dim3(512), lds, RH_ARGS); break; \
-    default: LAUNCH("k_rt_hop", (k_rt_hop<NCH, ME, 4>), dim3((S + 1) / 2), dim3(512), lds, RH_ARGS); break; \
-  }
-  if(d.nchannel <= 4 && d.maxnhar_e <= 4) { RH_CASE(4, 4) }
-  else if(d.nchannel <= 4) { RH_CASE(4, 8) }
-  else { RH_CASE(8, 8) }
-#undef RH_CASE
-#undef RH_ARGS
-  return 0;
+  return with_rt_shape(d, t, [&](auto nch, auto me, auto nts) {
+    LAUNCH("k_rt_hop", (k_rt_hop<nch, me, nts>), dim3((S + 1) / 2), dim3(512), lds,
+      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, envf,
+      f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, cyc_shift, frames_sin, mod, sinr, noiser, cap, mod_curr, sin_curr,
+      noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame, hr, d.npsd, d.psd, lds_half,
+      S, d.psdres, d.has_psdres, fnyq_conf, inv_wsqr, N, logN, tw, tw_nmax, nframes, live, sin_pos, next_nhop, out_stride, out, pa);
+    return 0;
+  });
 }
 
 int launch_utt_fftsize(LaunchCtx* P, const BatchDev& d, int nmax, int* nfft_u) {
@@ -4634,8 +4551,7 @@ int launch_harm_pp(LaunchCtx* P, const BatchDev& d, const float* sig, size_t sig
   if(d.nframes == 0) return 0;
   size_t lds = (size_t)(lds_n + lds_n / 2 + lds_n / 2 + 2) * sizeof(float2);
   if(lds > 160 * 1024) return -1;
-  if(lds > 64 * 1024 &&                                // 8192 points: 128 KB of the CU's 160 KB
-     hipFuncSetAttribute((const void*)k_harm_pp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+  if(lds_opt_in((const void*)k_harm_pp, lds) != hipSuccess) return -1;   // 8192 points: 128 KB of the CU's 160 KB
   LAUNCH("k_harm_pp", k_harm_pp, dim3(d.nframes), dim3(WAVE), lds, sig, sig_stride, nsig, d.x_off, d.nx,
     d.frm_utt, d.frm_off, d.f0, nfft_u, d.thop, d.fs, d.rel_winsize, maxnhar, norm_base, tw, tw_nmax,
     lds_n, nhar_out, ampl, phse);

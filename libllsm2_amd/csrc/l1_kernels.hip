@@ -26,6 +26,7 @@
 #pragma clang fp contract(fast)
 #include "dev_common.h"
 #include "wave_fft.h"
+#include "launch.h"
 
 namespace lf = llsm_lf;
 namespace lp = llsm_plan;
@@ -1301,23 +1302,12 @@ __global__ __launch_bounds__(WAVE) void k_coder_decode(CoderDev c, int nframes, 
 }
 
 // ---------------------------------------------------------------- launchers
-#define L1_LAUNCH(name, kern, grid, block, lds, ...)                                  \
-  do {                                                                                \
-    if(P -> prof_begin) P -> prof_begin(P -> prof_user, name, P -> stream);                        \
-    hipLaunchKernelGGL(kern, grid, block, lds, P -> stream, __VA_ARGS__);             \
-    if(P -> prof_end) P -> prof_end(P -> prof_user, P -> stream);                                  \
-    hipError_t e_ = hipGetLastError();                                                \
-    if(e_ != hipSuccess) return (int)e_;                                              \
-  } while(0)
-
 static size_t l1_lds_bytes(int maxnhar, int nmax, int extra_rows) {
   const int nh4 = (maxnhar + 3) & ~3;
   return sizeof(float) * (size_t)(nh4 * 3 + extra_rows) + sizeof(float2) * ((size_t)nmax + nmax / 2);
 }
-static int l1_set_lds(const void* fn, size_t bytes) {
-  if(bytes <= 64 * 1024) return 0;
-  if(bytes > 160 * 1024) return -1;
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
+static int l1_set_lds(const void* fn, size_t bytes) {       // no more than the CU's 160 KB
+  return bytes <= 160 * 1024 && lds_opt_in(fn, bytes) == hipSuccess ? 0 : -1;
 }
 static int pow2ge(int n) { int p = 1; while(p < n) p <<= 1; return p; }
 int l1_minphase_nmax(int maxnhar) { int n = pow2ge(maxnhar) * 4; return n < 64 ? 64 : n; }
@@ -1325,7 +1315,7 @@ int l1_minphase_nmax(int maxnhar) { int n = pow2ge(maxnhar) * 4; return n < 64 ?
 int launch_l1_rd_fit(LaunchCtx* P, const L1Dev& d, const float* model_power, const float* model_param,
   const double* inv_t, const double* cumlog_t, float* rd_raw) {
   if(d.nframes == 0) return 0;
-  L1_LAUNCH("k_l1_rd_fit", k_l1_rd_fit, dim3(d.nframes), dim3(WAVE), sizeof(float) * RD_NHAR,
+  LAUNCH("k_l1_rd_fit", k_l1_rd_fit, dim3(d.nframes), dim3(WAVE), sizeof(float) * RD_NHAR,
     d.nframes, d.f0, d.nhar, d.ampl, d.maxnhar, d.lip_radius, model_power, model_param, inv_t, cumlog_t, rd_raw);
   return 0;
 }
@@ -1337,7 +1327,7 @@ int launch_coder_encode(LaunchCtx* P, int order_spec, int order_bap, int ns, int
   c.liprad = liprad; c.melaxis = melaxis; c.mel_floor = 0; c.mel_ceil = 0;
   const size_t lds = sizeof(float) * 3 * (size_t)ns;
   if(order_spec > ns - 1 || l1_set_lds((const void*)k_coder_encode, lds)) return -1;
-  L1_LAUNCH("k_coder_encode", k_coder_encode, dim3(nframes), dim3(WAVE), lds, c, nframes, f0, rd, psd, vtmagn, nvsphse, enc);
+  LAUNCH("k_coder_encode", k_coder_encode, dim3(nframes), dim3(WAVE), lds, c, nframes, f0, rd, psd, vtmagn, nvsphse, enc);
   return 0;
 }
 int launch_coder_decode(LaunchCtx* P, int order_spec, int order_bap, int ns, int npsd, int maxnhar, float fnyq, float liprad,
@@ -1351,14 +1341,14 @@ int launch_coder_decode(LaunchCtx* P, int order_spec, int order_bap, int ns, int
   if(nmax > tw_nmax || order_spec > ns - 1) return -1;
   const size_t lds = sizeof(float) * (3 * (size_t)ns + 2 * (size_t)((maxnhar + 3) & ~3)) + sizeof(float2) * ((size_t)nmax + nmax / 2);
   if(l1_set_lds((const void*)k_coder_decode, lds)) return -1;
-  L1_LAUNCH("k_coder_decode", k_coder_decode, dim3(nframes), dim3(WAVE), lds, c, nframes, enc, use_l1, nmax, tw, tw_nmax, f0, rd,
+  LAUNCH("k_coder_decode", k_coder_decode, dim3(nframes), dim3(WAVE), lds, c, nframes, enc, use_l1, nmax, tw, tw_nmax, f0, rd,
     nhar, ampl, phse, psd, vtmagn, vsphse, nvsphse, has_hm);
   return 0;
 }
 int launch_fa_glottal_fit(LaunchCtx* P, const float* ampl, int nhar, const float* model_power, const float* model_param,
   int ncand, int nhm, float* out) {
   if(ncand < 1 || ncand > WAVE || nhm < 1) return -1;
-  L1_LAUNCH("k_fa_glottal_fit", k_fa_glottal_fit, dim3(1), dim3(WAVE), sizeof(float) * (size_t)nhm, ampl, nhar, model_power,
+  LAUNCH("k_fa_glottal_fit", k_fa_glottal_fit, dim3(1), dim3(WAVE), sizeof(float) * (size_t)nhm, ampl, nhar, model_power,
     model_param, ncand, nhm, out);
   return 0;
 }
@@ -1370,13 +1360,13 @@ int launch_fa_l1_frame(LaunchCtx* P, const float* ampl, int nhar, double f0d, in
   if(nmax > tw_nmax || (what != 0 && (nfft < 4 || (nfft & (nfft - 1))))) return -1;
   const size_t lds = sizeof(float) * (size_t)(((nhar + 3) & ~3) * 2) + sizeof(float2) * ((size_t)nmax + nmax / 2);
   if(l1_set_lds((const void*)k_fa_l1_frame, lds)) return -1;
-  L1_LAUNCH("k_fa_l1_frame", k_fa_l1_frame, dim3(1), dim3(WAVE), lds, ampl, nhar, f0d, nfft, what, nmax, tw, tw_nmax, out);
+  LAUNCH("k_fa_l1_frame", k_fa_l1_frame, dim3(1), dim3(WAVE), lds, ampl, nhar, f0d, nfft, what, nmax, tw, tw_nmax, out);
   return 0;
 }
 int launch_l1_rd_smooth(LaunchCtx* P, int n_utt, const int* frm_off, const int* nfrm, int order,
   const float* rd_raw, int* prev_idx, int* next_idx, float* cont, float* rd_out) {
   if(n_utt == 0) return 0;
-  L1_LAUNCH("k_l1_rd_smooth", k_l1_rd_smooth, dim3(n_utt), dim3(256), 0, frm_off, nfrm, order, rd_raw, prev_idx,
+  LAUNCH("k_l1_rd_smooth", k_l1_rd_smooth, dim3(n_utt), dim3(256), 0, frm_off, nfrm, order, rd_raw, prev_idx,
     next_idx, cont, rd_out);
   return 0;
 }
@@ -1386,38 +1376,27 @@ int launch_l1_frame(LaunchCtx* P, const L1Dev& d, int nfft, const float2* tw, in
   // the envelope on the register-resident FFT, two frames per transform, when there is a plan for nfft and the
   // caller brought the scratch rows; otherwise inside k_l1_frame on the LDS FFT
   const bool split = d.src_ampl && (1 << logn) == nfft && logn >= 10 && logn <= 11;   // 4096: 128 data registers per lane
-  if(! split) {
-    int nmax = l1_minphase_nmax(d.maxnhar); if(nfft > nmax) nmax = nfft;
-    if(nmax > tw_nmax) return -1;
-    const size_t lds = l1_lds_bytes(d.maxnhar, nmax, 0);
-    if(l1_set_lds((const void*)k_l1_frame, lds)) return -1;
-    L1_LAUNCH("k_l1_frame", k_l1_frame, dim3(d.nframes), dim3(WAVE), lds, d.nframes, d.f0, d.nhar, d.ampl, d.phse,
-      d.maxnhar, d.rd, d.lip_radius, d.fnyq, nfft, nmax, tw, tw_nmax, d.vtmagn, d.vsphse, d.nvsphse, (float*)nullptr, d.acache);
-    return 0;
-  }
   {
-    const int nmax = l1_minphase_nmax(d.maxnhar);
+    int nmax = l1_minphase_nmax(d.maxnhar); if(! split && nfft > nmax) nmax = nfft;   // split: the envelope's transform is not this kernel's
     if(nmax > tw_nmax) return -1;
     const size_t lds = l1_lds_bytes(d.maxnhar, nmax, 0);
     if(l1_set_lds((const void*)k_l1_frame, lds)) return -1;
-    L1_LAUNCH("k_l1_frame", k_l1_frame, dim3(d.nframes), dim3(WAVE), lds, d.nframes, d.f0, d.nhar, d.ampl, d.phse,
-      d.maxnhar, d.rd, d.lip_radius, d.fnyq, nfft, nmax, tw, tw_nmax, d.vtmagn, d.vsphse, d.nvsphse, d.src_ampl, d.acache);
+    LAUNCH("k_l1_frame", k_l1_frame, dim3(d.nframes), dim3(WAVE), lds, d.nframes, d.f0, d.nhar, d.ampl, d.phse,
+      d.maxnhar, d.rd, d.lip_radius, d.fnyq, nfft, nmax, tw, tw_nmax, d.vtmagn, d.vsphse, d.nvsphse, split ? d.src_ampl : nullptr, d.acache);
   }
+  if(! split) return 0;
   const int npair = d.pairs ? d.npairs : (d.nframes + 1) / 2;
   const int nh4 = (d.maxnhar + 3) & ~3;
   const int grid = npair < 4096 ? npair : 4096;
-#define ENV_CASE(LN) \
-  if(logn == LN) { \
-    const size_t lds = std::max(sizeof(float2) * (size_t)wf_lds_elems<LN>(), \
-      sizeof(double4) * 2 * (size_t)nh4 + sizeof(float) * 2 * (((size_t)1 << LN) / WAVE / 2 + 1) * WAVE) + sizeof(float) * 4 * (size_t)nh4; \
-    if(l1_set_lds((const void*)k_l1_env_wf<LN>, lds)) return -1; \
-    L1_LAUNCH("k_l1_env_wf", (k_l1_env_wf<LN>), dim3(grid), dim3(WAVE), lds, d.nframes, d.f0, d.nvsphse, d.src_ampl, \
-      d.maxnhar, d.fnyq, d.vtmagn, d.pairs, npair); \
-    return 0; \
-  }
-  ENV_CASE(10) ENV_CASE(11)
-#undef ENV_CASE
-  return -1;
+  return pick_int<10, 11>(logn, -1, [&](auto ln) {
+    constexpr int LN = ln;
+    const size_t lds = std::max(sizeof(float2) * (size_t)wf_lds_elems<LN>(),
+      sizeof(double4) * 2 * (size_t)nh4 + sizeof(float) * 2 * (((size_t)1 << LN) / WAVE / 2 + 1) * WAVE) + sizeof(float) * 4 * (size_t)nh4;
+    if(l1_set_lds((const void*)k_l1_env_wf<LN>, lds)) return -1;
+    LAUNCH("k_l1_env_wf", (k_l1_env_wf<LN>), dim3(grid), dim3(WAVE), lds, d.nframes, d.f0, d.nvsphse, d.src_ampl,
+      d.maxnhar, d.fnyq, d.vtmagn, d.pairs, npair);
+    return 0;
+  });
 }
 int launch_l1_to_l0(LaunchCtx* P, const L1Dev& d, int maxnhar_conf, int only_missing, const int* select,
   const float2* tw, int tw_nmax) {
@@ -1426,7 +1405,7 @@ int launch_l1_to_l0(LaunchCtx* P, const L1Dev& d, int maxnhar_conf, int only_mis
   if(nmax > tw_nmax) return -1;
   const size_t lds = l1_lds_bytes(d.maxnhar, nmax, 0);
   if(l1_set_lds((const void*)k_l1_to_l0, lds)) return -1;
-  L1_LAUNCH("k_l1_to_l0", k_l1_to_l0, dim3(d.nframes), dim3(WAVE), lds, d.nframes, d.f0, d.nhar, d.ampl, d.phse,
+  LAUNCH("k_l1_to_l0", k_l1_to_l0, dim3(d.nframes), dim3(WAVE), lds, d.nframes, d.f0, d.nhar, d.ampl, d.phse,
     d.maxnhar, d.rd, d.lip_radius, d.fnyq, d.nspec, maxnhar_conf, only_missing, select, nmax, tw, tw_nmax,
     d.vtmagn, d.vsphse, d.nvsphse, d.has_hm, d.acache);
   return 0;
@@ -1445,32 +1424,32 @@ int launch_pbp_pulse(LaunchCtx* P, const L1Dev& d, const PbpJob* jobs, int njobs
   const int xcap = real ? std::max(nmin, (size_max / 2 + 4) & ~3) : nmax;
   const int twcap = real ? std::max(nmin / 2, size_max / 4) : nmax / 2;
   const size_t lds = sizeof(float) * (size_t)(((d.maxnhar + 3) & ~3) * 4 + 8) + sizeof(float2) * ((size_t)xcap + twcap);
-#define PBP_GO(NTH, RL) do { \
-    if(l1_set_lds((const void*)k_pbp_pulse<NTH, RL>, lds)) return -1; \
-    L1_LAUNCH("k_pbp_pulse", (k_pbp_pulse<NTH, RL>), dim3(njobs), dim3(NTH), lds, jobs, pulses, d.f0, d.rd, d.vtmagn, d.nspec, \
-      d.vsphse, d.nvsphse, d.maxnhar, d.fnyq, d.lip_radius, fs, xcap, tw, tw_nmax, out, d.acache); } while(0)
+  auto go = [&](auto nth, auto rl) {
+    if(l1_set_lds((const void*)k_pbp_pulse<nth, rl>, lds)) return -1;
+    LAUNCH("k_pbp_pulse", (k_pbp_pulse<nth, rl>), dim3(njobs), dim3(nth), lds, jobs, pulses, d.f0, d.rd, d.vtmagn, d.nspec,
+      d.vsphse, d.nvsphse, d.maxnhar, d.fnyq, d.lip_radius, fs, xcap, tw, tw_nmax, out, d.acache);
+    return 0;
+  };
   // Fewer pulse groups than the device has compute units (a hop of llsmrt: at most one per stream): the launch waits for
   // the slowest group's chain, so a group gets four wavefronts; a batch of thousands is throughput-bound and keeps fewer.
-  if(njobs <= PBP_WIDE_BELOW) { if(real) PBP_GO(256, true); else PBP_GO(256, false); }
-  else { if(real) PBP_GO(PBP_NT, true); else PBP_GO(PBP_NT, false); }
-#undef PBP_GO
-  return 0;
+  if(njobs <= PBP_WIDE_BELOW) return real ? go(int_c<256>{}, std::true_type{}) : go(int_c<256>{}, std::false_type{});
+  return real ? go(int_c<PBP_NT>{}, std::true_type{}) : go(int_c<PBP_NT>{}, std::false_type{});
 }
 int launch_rt_pbp(LaunchCtx* P, int S, const RtPbpOp* ops, float* frwd, float* bkwd, int cap, int dual_curr,
   float* sinr, int sin_curr, int nhop, const float* win, const float* pulse_out, int pulse_stride) {
-  L1_LAUNCH("k_rt_pbp", k_rt_pbp, dim3(S), dim3(256), 0, ops, frwd, bkwd, cap, dual_curr, sinr, sin_curr, nhop, win,
+  LAUNCH("k_rt_pbp", k_rt_pbp, dim3(S), dim3(256), 0, ops, frwd, bkwd, cap, dual_curr, sinr, sin_curr, nhop, win,
     pulse_out, pulse_stride);
   return 0;
 }
 int launch_l1_projection(LaunchCtx* P, const L1Dev& d, double fs, double* proj) {
   if(d.nframes == 0) return 0;
-  L1_LAUNCH("k_l1_projection", k_l1_projection, dim3(d.nframes), dim3(WAVE), 0, d.nframes, d.f0, d.rd, d.vsphse, d.nvsphse,
+  LAUNCH("k_l1_projection", k_l1_projection, dim3(d.nframes), dim3(WAVE), 0, d.nframes, d.f0, d.rd, d.vsphse, d.nvsphse,
     d.maxnhar, fs, proj, d.acache);
   return 0;
 }
 int launch_l1_mixcurve(LaunchCtx* P, const PbpSeg* segs, int nsegs, float* mixw) {
   if(nsegs == 0) return 0;
-  L1_LAUNCH("k_l1_mixcurve", k_l1_mixcurve, dim3((nsegs + 63) / 64), dim3(64), 0, segs, nsegs, mixw);
+  LAUNCH("k_l1_mixcurve", k_l1_mixcurve, dim3((nsegs + 63) / 64), dim3(64), 0, segs, nsegs, mixw);
   return 0;
 }
 int launch_pbp_mix(LaunchCtx* P, int n_utt, int max_len, const int* out_off, const int* out_len, const int* frm_off,
@@ -1478,7 +1457,7 @@ int launch_pbp_mix(LaunchCtx* P, int n_utt, int max_len, const int* out_off, con
   const int2* blk_jobs, const int* blk_off, const float* pulse_buf, const float* mixw, const float* ynoise,
   float* ysin, float* y) {
   if(n_utt == 0 || max_len == 0) return 0;
-  L1_LAUNCH("k_pbp_mix", k_pbp_mix, dim3((max_len + 255) / 256, n_utt), dim3(256), 0, out_off, out_len, frm_off, nfrm,
+  LAUNCH("k_pbp_mix", k_pbp_mix, dim3((max_len + 255) / 256, n_utt), dim3(256), 0, out_off, out_len, frm_off, nfrm,
     thop, fs, nwin, hm_frames, f0_hm, jobs, blk_jobs, blk_off, pulse_buf, mixw, ynoise, ysin, y);
   return 0;
 }

@@ -378,10 +378,8 @@ int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, con
   if(g_hi <= g_lo) return 0;
   g_lo -= g_lo % kPfFrames;
   const size_t lds = (size_t)kPfFrames * (r.nspec + r.npsd) * sizeof(float);
-  if(lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_pitch_formant, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if(e != hipSuccess) return (int)e;
-  }
+  const hipError_t e = lds_opt_in((const void*)k_pitch_formant, lds);
+  if(e != hipSuccess) return (int)e;
   const int groups = (g_hi - g_lo + kPfFrames - 1) / kPfFrames;
   LAUNCH("k_pitch_formant", k_pitch_formant, dim3(groups), dim3(kPfThreads), lds, r, g_lo, rho, alpha, warp_psd);
   return 0;

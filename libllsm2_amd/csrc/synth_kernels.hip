@@ -353,31 +353,20 @@ __global__ __launch_bounds__(SO4_WAVES * WAVE, SO4_WPE) void k_synth_ola4(const 
 // wavefronts per SIMD resident (4096 on the chip), the one-wavefront kernel 8.  Measured on config 2 (tools/kbench.py,
 // LLSM_GPU_SIN_UNIT): 25-frame units 0.845, 50-frame units 0.812, 40-frame units 1.22 ms per step for the table kernel.
 static bool synth_ola_uses_groups(int nwin, int lds_harmonics) {
-  const int T = ((nwin + 15) / 16 + 2 + 31) / 32;
-  return T == 1 && lds_harmonics <= 4 * SYN_TAB_MAXKS;
+  return synth_tiles(nwin).T == 1 && lds_harmonics <= 4 * SYN_TAB_MAXKS;
 }
 int synth_ola_unit_div(int nwin, int lds_harmonics) { return synth_ola_uses_groups(nwin, lds_harmonics) ? 4096 : 8192; }
 int synth_ola_group_units(void) { return SO4_WAVES; }   // units per workgroup of k_synth_ola4: the host pads every utterance to groups
 int launch_synth_frames(LaunchCtx* P, const BatchDev& d, int nwin, const float* win,
   const float* cyc_shift, float* frames, int lds_harmonics) {
   if(d.nframes == 0) return 0;
-  // row length L = 32 T - 2 samples (16 rows cover nwin): L/2 + 1 = 16 T offsets from the row
-  // centre, in passes of NT <= 4 column tiles
-  int T = ((nwin + 15) / 16 + 2 + 31) / 32;
-  int NT = T;
-  if(T > 4) { T = (T + 3) / 4 * 4; NT = 4; }
-  const int L = 32 * T - 2;
+  const SynthTiles t = synth_tiles(nwin);
   const size_t lds = (lds_harmonics + 4) * sizeof(float2);
-#define SF_ARGS d.frm_utt, d.frm_off, d.f0, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, d.fs, nwin, L, win, \
-    cyc_shift, frames
-  switch(NT) {
-    case 1: LAUNCH("k_synth_frames", (k_synth_frames<1>), dim3(d.nframes), dim3(WAVE), lds, SF_ARGS); break;
-    case 2: LAUNCH("k_synth_frames", (k_synth_frames<2>), dim3(d.nframes), dim3(WAVE), lds, SF_ARGS); break;
-    case 3: LAUNCH("k_synth_frames", (k_synth_frames<3>), dim3(d.nframes), dim3(WAVE), lds, SF_ARGS); break;
-    default: LAUNCH("k_synth_frames", (k_synth_frames<4>), dim3(d.nframes), dim3(WAVE), lds, SF_ARGS); break;
-  }
-#undef SF_ARGS
-  return 0;
+  return with_tiles(t.NT, [&](auto nts) {
+    LAUNCH("k_synth_frames", (k_synth_frames<nts>), dim3(d.nframes), dim3(WAVE), lds,
+      d.frm_utt, d.frm_off, d.f0, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, d.fs, nwin, t.L, win, cyc_shift, frames);
+    return 0;
+  });
 }
 
 // Fused harmonic frames + overlap-add over the units of a batch (see k_synth_ola).
@@ -385,16 +374,13 @@ int launch_synth_ola(LaunchCtx* P, const BatchDev& d, const int4* units, int nun
   int nwin, const float* win, int lds_harmonics, const int* out_off, const int* out_len,
   const float* x, float* out, int mode, float* mix) {
   if(nunits == 0) return 0;
-  int T = ((nwin + 15) / 16 + 2 + 31) / 32;
-  int NT = T;
-  if(T > 4) { T = (T + 3) / 4 * 4; NT = 4; }
-  const int L = 32 * T - 2;
+  const SynthTiles t = synth_tiles(nwin);
   int R = 64; while(R < nwin) R <<= 1;
   if(synth_ola_uses_groups(nwin, lds_harmonics) && nunits % SO4_WAVES == 0) {
     So4Args a;
     a.units = units; a.halo = halo; a.R = R; a.frm_off = d.frm_off; a.nfrm = d.nfrm; a.out_off = out_off; a.out_len = out_len;
     a.f0 = d.f0; a.nhar = d.nhar; a.ampl = d.ampl; a.phse = d.phse; a.maxnhar = d.maxnhar; a.thop = d.thop; a.fs = d.fs;
-    a.nwin = nwin; a.L = L; a.win = win; a.lds_harmonics = lds_harmonics; a.nks_tab = (lds_harmonics + 3) / 4;
+    a.nwin = nwin; a.L = t.L; a.win = win; a.lds_harmonics = lds_harmonics; a.nks_tab = (lds_harmonics + 3) / 4;
     a.use_tab = d.synth_tables; a.x = x; a.out = out; a.mode = mode; a.mix = mix;
     const size_t lds4 = (size_t)a.nks_tab * WAVE * sizeof(float4)
       + SO4_WAVES * ((lds_harmonics + 4) * sizeof(float2) + R * sizeof(float));
@@ -402,14 +388,10 @@ int launch_synth_ola(LaunchCtx* P, const BatchDev& d, const int4* units, int nun
     return 0;
   }
   const size_t lds = (lds_harmonics + 4) * sizeof(float2) + R * sizeof(float);
-#define SO_ARGS units, halo, R, d.frm_off, d.nfrm, out_off, out_len, d.f0, d.nhar, d.ampl, d.phse, d.maxnhar, \
-    d.thop, d.fs, nwin, L, win, lds_harmonics, x, out, mode, mix
-  switch(NT) {
-    case 1: LAUNCH("k_synth_ola", (k_synth_ola<1>), dim3(nunits), dim3(WAVE), lds, SO_ARGS); break;
-    case 2: LAUNCH("k_synth_ola", (k_synth_ola<2>), dim3(nunits), dim3(WAVE), lds, SO_ARGS); break;
-    case 3: LAUNCH("k_synth_ola", (k_synth_ola<3>), dim3(nunits), dim3(WAVE), lds, SO_ARGS); break;
-    default: LAUNCH("k_synth_ola", (k_synth_ola<4>), dim3(nunits), dim3(WAVE), lds, SO_ARGS); break;
-  }
-#undef SO_ARGS
-  return 0;
+  return with_tiles(t.NT, [&](auto nts) {
+    LAUNCH("k_synth_ola", (k_synth_ola<nts>), dim3(nunits), dim3(WAVE), lds,
+      units, halo, R, d.frm_off, d.nfrm, out_off, out_len, d.f0, d.nhar, d.ampl, d.phse, d.maxnhar,
+      d.thop, d.fs, nwin, t.L, win, lds_harmonics, x, out, mode, mix);
+    return 0;
+  });
 }

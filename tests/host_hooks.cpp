@@ -89,3 +89,18 @@ extern "C" void hook_lf_spectrum(double rd, double T0, const double* freq, int n
   for(int i = 0; i < n; i ++) { magn[i] = llsm_lf::magnitude(s, freq[i]); phase[i] = llsm_lf::phase(s, freq[i]); }
   params[0] = m.te; params[1] = m.tp; params[2] = m.ta; params[3] = s.eps; params[4] = s.alpha;
 }
+
+// ---- dispatch.h (which kernel instantiation the launchers pick) ----
+#include "dispatch.h"
+extern "C" void hook_env_shape(int nch, int me, int* out /* NCH ME */) {
+  with_env_shape(nch, me, [&](auto NCH, auto ME) { out[0] = NCH; out[1] = ME; return 0; });
+}
+// pick_int<8, 9, 10, 11>: its return value; *calls counts the calls of f, *seen is the constant f received
+extern "C" int hook_pick_wf(int v, int miss, int* calls, int* seen) {
+  return pick_int<8, 9, 10, 11>(v, miss, [&](auto c) { (*calls) ++; *seen = c; return 100 + c; });
+}
+extern "C" void hook_synth_tiles(int nwin, int* out /* T NT L, the NTS with_tiles instantiates */) {
+  const SynthTiles t = synth_tiles(nwin);
+  out[0] = t.T; out[1] = t.NT; out[2] = t.L;
+  out[3] = with_tiles(t.NT, [](auto nts) { return (int)nts; });
+}

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 def hooks():
     so = os.path.join(HERE, "_host_hooks.so")
     src = os.path.join(HERE, "host_hooks.cpp")
-    hdrs = [os.path.join(ROOT, "libllsm2_amd", "csrc", h) for h in ("cheby.h", "lfmodel.h")]
+    hdrs = [os.path.join(ROOT, "libllsm2_amd", "csrc", h) for h in ("cheby.h", "lfmodel.h", "dispatch.h")]
     if not os.path.exists(so) or os.path.getmtime(so) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                                "-I" + os.path.join(ROOT, "libllsm2_amd", "csrc"), "-o", so, src])
@@ -56,6 +56,52 @@ def test_block_filtfilt_equals_scipy(hooks):
             ref = ss.filtfilt(B, A, x, padlen=min(15, n - 1))
             tol = 1e-7 if row == 0 else 2e-9          # row 0 (Wn = 0.02) is ill-conditioned even in float64
             assert np.abs(y - ref).max() < tol * max(1.0, np.abs(ref).max()), (n, row, hp)
+
+
+def test_env_shape_follows_the_rule_and_holds_the_batch(hooks):
+    """dispatch.h with_env_shape: the <NCH, ME> instantiation for every channel count and envelope-harmonic count a
+    batch can have is the one the three-branch rule names, and it is large enough for both."""
+    out = (C.c_int * 2)()
+    for nch in range(1, 9):
+        for me in range(0, 9):
+            hooks.hook_env_shape(nch, me, out)
+            if nch <= 4 and me <= 4:
+                want = (4, 4)
+            elif nch <= 4:
+                want = (4, 8)
+            else:
+                want = (8, 8)
+            assert tuple(out) == want, (nch, me)
+            assert out[0] >= nch and out[1] >= me, (nch, me)
+
+
+def test_pick_int_calls_the_match_once_and_nothing_on_a_miss(hooks):
+    """dispatch.h pick_int<8, 9, 10, 11>: a listed value reaches the functor exactly once, as that constant, and the
+    functor's result comes back; 7 and 12 give `miss` without a call."""
+    for v in (8, 9, 10, 11):
+        calls, seen = C.c_int(0), C.c_int(-1)
+        assert hooks.hook_pick_wf(v, -77, C.byref(calls), C.byref(seen)) == 100 + v
+        assert (calls.value, seen.value) == (1, v)
+    for v in (7, 12):
+        calls, seen = C.c_int(0), C.c_int(-1)
+        assert hooks.hook_pick_wf(v, -77, C.byref(calls), C.byref(seen)) == -77
+        assert (calls.value, seen.value) == (0, -1)
+
+
+# nwin: (T, NT, L) of the harmonic frame's column tiles, at both ends of every tile count and the first sizes past four tiles
+SYNTH_TILES = {1: (1, 1, 30), 480: (1, 1, 30), 481: (2, 2, 62), 992: (2, 2, 62), 993: (3, 3, 94), 1504: (3, 3, 94),
+               1505: (4, 4, 126), 2016: (4, 4, 126), 2017: (8, 4, 254), 4064: (8, 4, 254), 4065: (12, 4, 382)}
+
+
+def test_synth_tile_geometry(hooks):
+    """dispatch.h synth_tiles and with_tiles: the tile geometry at the edges of every tile count, and the NTS
+    instantiation taken is the NT computed."""
+    out = (C.c_int * 4)()
+    for nwin, want in SYNTH_TILES.items():
+        hooks.hook_synth_tiles(nwin, out)
+        assert tuple(out)[:3] == want, nwin
+        assert out[3] == want[1], nwin
+        assert 16 * out[2] >= nwin, nwin              # 16 rows of L samples cover the window
 
 
 def test_overlap_add_halo_covers_every_overlapping_frame():

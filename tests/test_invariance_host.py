@@ -42,7 +42,7 @@ def case_signal(case):
     return case["fs"], case["thop"], case["kw"], x, f0.astype(np.float32)
 
 
-# (log2 N, log2 fold) of the register-resident spectrogram kernel's instantiations (kernels.hip launch_spgm_env WF_CASE)
+# (log2 N, log2 fold) of the register-resident spectrogram kernel's instantiations (kernels.hip launch_spgm_env)
 WF_SHAPES = {(9, 0), (9, 1), (10, 0), (10, 1), (10, 2), (11, 0), (11, 1), (11, 2)}
 
 
