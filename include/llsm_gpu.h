@@ -151,6 +151,9 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * which = 3: the band-limited noise templates of the last synthesis (dsputils.c:385-394), [n_utt][nchannel][ntemplate_ext];
  * utterance u uses the first min(20000, ny[u]) + 128 samples of a row, and the rows of channels that start at or above
  * the synthesis Nyquist are never written (layer0.c:562 leaves such a channel out).
+ * which = 4: the CMNDF plane of the last llsm_gpu_batch_estimate_f0 of this batch that ran with keep_cmndf = 1 (rule 5
+ * below that call), [total_frames][lmax + 1] with that call's lmax; the row of a gated frame is all ones.  Refused until
+ * such a call has run; no other call writes it.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -338,6 +341,52 @@ int llsm_gpu_batch_splice(llsm_gpu_batch* dst, const llsm_gpu_batch* src, const 
  * narrows the harmonic band by rho; VSPHSE is not extended. */
 enum { LLSM_GPU_WARP_PSD = 1 };
 int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0_ratio, const FP_TYPE* formant_ratio, int flags);
+
+/* ---- F0 estimation: LLSM_GPU_X -> LLSM_GPU_F0 on the device, a YIN-style estimator (difference function, cumulative mean
+ * normalised difference "CMNDF", first dip below a threshold, parabolic fit, median of five).  It is the estimator of
+ * tests/golden/make_f0_track.py on the batch's frame grid; trackers with a path search (pYIN) are not provided.
+ * Asynchronous on the context's stream; a refused call returns -1, sets llsm_gpu_last_error() (the message starts with
+ * "llsm_gpu_batch_estimate_f0:") and writes and launches nothing.  The call reads LLSM_GPU_X and writes all total_frames
+ * entries of LLSM_GPU_F0 and nothing else; afterwards the batch's lowest-F0 bound is unknown, as after every call that
+ * writes the F0 row on the device (a full host upload of F0 makes it known again).
+ *
+ * The rules, per utterance with samples x[0, nx), nfrm frames and the batch's thop and fs; options enter as the float64
+ * values of their float32 members, arithmetic is float64 unless stated:
+ *  1. lmin = (int)(fs / fmax), lmax = (int)(fs / fmin); W = lmax + window_extra; nfft = the smallest power of two that is
+ *     >= 256 and >= W + lmax.
+ *  2. Frame i: c = round(i * thop * fs) as the analysis forms it (float32 products); s[n] = x[c - W / 2 + n] for n in
+ *     [0, W + lmax), integer division, zero outside [0, nx).
+ *  3. The frame is unvoiced (raw value 0) if sum_{n<W} s[n]^2 is 0 or sum_{n<W} s[n]^2 / W < silence_rel^2 * sum x^2 / nx; the
+ *     utterance's sum of squares is taken in an order fixed by nx alone.
+ *  4. d[tau] = sum_{n<W} (s[n] - s[n + tau])^2 for tau in [0, lmax] -- evaluated as E(0) + E(tau) - 2 r(tau) with
+ *     E(tau) = sum_{n<W} s[n + tau]^2 and r the cross-correlation of s[0, W) with s; r comes from float32 transforms.
+ *  5. cm[0] = 1, cm[tau] = d[tau] * tau / max(sum_{j=1..tau} d[j], 1e-12), kept as float32.
+ *  6. The first tau in [lmin, lmax) with cm[tau] < threshold (none: raw value 0); then while tau + 1 < lmax and
+ *     cm[tau + 1] < cm[tau]: tau ++.
+ *  7. y0, y1, y2 = cm[tau - 1], cm[tau], cm[tau + 1]; den = y0 - 2 y1 + y2; off = 0.5 (y0 - y2) / den if |den| > 1e-12, else
+ *     0; raw = (float)(fs / (tau + off)).
+ *  8. smooth = 1, over the raw values of the utterance: for 2 <= i < nfrm - 2 with nz non-zero entries among
+ *     raw[i - 2 .. i + 2]: raw[i] != 0 and nz >= 4: the median of the non-zero entries (of four: the float32 mean of the
+ *     middle two); raw[i] != 0 and nz <= 2: 0; otherwise raw[i].  The first and last two frames keep their raw values.
+ *     smooth = 0: the raw values.
+ * A frame's value depends on its own utterance only: not on the batch, the utterance's place in it, or any other call.
+ *
+ * Refused: a NULL batch; a NaN option; fmin <= 0; fmin >= fmax; lmin < 2; lmax <= lmin + 1; threshold outside (0, 1];
+ * silence_rel < 0; window_extra < 1; smooth or keep_cmndf not 0 or 1; W + lmax > 4096 (the largest transform); a batch
+ * with frames but no samples.  A batch without frames returns 0.
+ * llsm_gpu_f0_plan is host only: the sizes of rule 1 at fs (NULL pointers are skipped; opt NULL: the defaults); 0, or -1
+ * with the message llsm_gpu_batch_estimate_f0 would give when it would refuse the options. */
+typedef struct {
+  FP_TYPE fmin, fmax;      /* search range in Hz; defaults 50, 500 */
+  FP_TYPE threshold;       /* CMNDF threshold; default 0.15 */
+  FP_TYPE silence_rel;     /* gate: window RMS below silence_rel x utterance RMS -> unvoiced; default 0.05 */
+  int     window_extra;    /* integration window W = lmax + window_extra samples; default 200 */
+  int     smooth;          /* 1 (default): the median-of-5 pass of rule 8; 0: raw values */
+  int     keep_cmndf;      /* 1: keep the CMNDF plane for llsm_gpu_batch_debug_plane(b, 4, ...); default 0 */
+} llsm_gpu_f0_options;
+void llsm_gpu_f0_default_options(llsm_gpu_f0_options* dst);
+int  llsm_gpu_f0_plan(const llsm_gpu_f0_options* opt, FP_TYPE fs, int* lmin, int* lmax, int* W, int* nfft);
+int  llsm_gpu_batch_estimate_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt /* NULL: defaults */);
 
 /* ---- frame coder of a device-resident layer-1 batch: every frame <-> the vector [voicing, f0, Rd, order_spec mel-spectrum
  * points, order_bap band aperiodicities] of llsm_coder_encode_frames / llsm_coder_decode_frames (llsm.h), without leaving

@@ -75,6 +75,11 @@ class SpliceMap(C.Structure):                              # llsm_gpu_splice_map
     _fields_ = [("utt_a", P_int), ("pos_a", P_fp), ("utt_b", P_int), ("pos_b", P_fp), ("mix", P_fp)]
 
 
+class F0Options(C.Structure):                             # llsm_gpu_f0_options
+    _fields_ = [("fmin", fp), ("fmax", fp), ("threshold", fp), ("silence_rel", fp), ("window_extra", C.c_int),
+                ("smooth", C.c_int), ("keep_cmndf", C.c_int)]
+
+
 # frame / conf member indices (llsm.h)
 FRAME_F0, FRAME_HM, FRAME_NM, FRAME_PSDRES = 0, 1, 2, 3
 FRAME_PBPEFF, FRAME_PBPSYN, FRAME_RD, FRAME_VTMAGN, FRAME_VSPHSE = 8, 9, 10, 11, 12
@@ -136,6 +141,7 @@ llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime
 llsm_gpu_batch_pitch_formant llsm_gpu_batch_splice
 llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode llsm_gpu_batch_decode
 llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu_batch_download_blob_block
+llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
 """.split()
 
 _lib = None
@@ -198,6 +204,10 @@ def load():
     L.llsm_gpu_retime_uniform_positions.restype = None
     L.llsm_gpu_batch_pitch_formant.argtypes = [vp, P_fp, P_fp, C.c_int]
     L.llsm_gpu_batch_splice.argtypes = [vp, vp, C.POINTER(SpliceMap)]
+    L.llsm_gpu_f0_default_options.argtypes = [C.POINTER(F0Options)]
+    L.llsm_gpu_f0_default_options.restype = None
+    L.llsm_gpu_f0_plan.argtypes = [C.POINTER(F0Options), fp, P_int, P_int, P_int, P_int]
+    L.llsm_gpu_batch_estimate_f0.argtypes = [vp, C.POINTER(F0Options)]
     try:                                                 # (as above: an experiment build of an earlier commit lacks the coder)
         L.llsm_gpu_batch_enable_coder.argtypes = [vp, C.c_int, C.c_int]
         L.llsm_gpu_batch_coder_dimension.argtypes = [vp]
@@ -342,6 +352,26 @@ def retime_uniform_positions(nfrm_src, nfrm_dst):
     pos = np.zeros(max(int(nfrm_dst), 0), np.float32)
     load().llsm_gpu_retime_uniform_positions(int(nfrm_src), int(nfrm_dst), pos.ctypes.data_as(P_fp))
     return pos
+
+
+def make_f0_options(**kw):
+    """llsm_gpu_f0_default_options() with overrides"""
+    o = F0Options()
+    load().llsm_gpu_f0_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(F0Options._fields_):
+            raise TypeError("llsm_gpu_f0_options has no member " + k)
+        setattr(o, k, v)
+    return o
+
+
+def f0_plan(fs, **kw):
+    """the sizes the F0 options imply at fs, as a dict lmin, lmax, W, nfft (llsm_gpu_f0_plan); LlsmError where
+    llsm_gpu_batch_estimate_f0 would refuse them"""
+    o = make_f0_options(**kw)
+    v = [C.c_int() for _ in range(4)]
+    _check(load().llsm_gpu_f0_plan(C.byref(o), fs, *[C.byref(x) for x in v]), "f0_plan")
+    return dict(zip(("lmin", "lmax", "W", "nfft"), (x.value for x in v)))
 
 
 WARP_PSD = 1                                               # LLSM_GPU_WARP_PSD (llsm_gpu_batch_pitch_formant)
@@ -555,6 +585,24 @@ class Batch:
         _check(self.L.llsm_gpu_batch_pitch_formant(self.h, None if r is None else r.ctypes.data_as(P_fp),
                                                    None if a is None else a.ctypes.data_as(P_fp),
                                                    WARP_PSD if warp_psd else 0), "pitch_formant")
+
+    # ---- F0 estimation (llsm_gpu.h): LLSM_GPU_X -> LLSM_GPU_F0 on the device
+    def estimate_f0(self, **options):
+        """the F0 row from the uploaded waveforms (llsm_gpu_batch_estimate_f0); options: the members of
+        llsm_gpu_f0_options, defaults where not given"""
+        o = make_f0_options(**options)
+        _check(self.L.llsm_gpu_batch_estimate_f0(self.h, C.byref(o)), "estimate_f0")
+
+    def debug_plane(self, which):
+        """intermediate plane `which` as a flat float32 array (llsm_gpu_batch_debug_plane; 4: the CMNDF rows of the
+        last estimate_f0(keep_cmndf=1), total_frames x (lmax + 1))"""
+        n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
+        if n < 0:
+            raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
+        a = np.zeros(n, np.float32)
+        if self.L.llsm_gpu_batch_debug_plane(self.h, int(which), a.ctypes.data, n) != n:
+            raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
+        return a
 
     # ---- frame coder (llsm_gpu.h): rows <-> LLSM_GPU_CODE, [total_frames][coder_dimension] float32
     def enable_coder(self, order_spec, order_bap):

@@ -183,6 +183,9 @@ struct llsm_gpu_batch {
   // pack kernel reads (followed by chanfreq), and the staging area the blobs are packed into -- all grow-only
   DevBuf<int> blob_widths; DevBuf<char> blob_tab; DevBuf<unsigned char> blob_dev;
   PinVec<int> blob_widths_h; PinVec<char> blob_tab_h;
+  // F0 estimation (f0.cpp): the utterances' sums of squares, the raw row before the median pass, and the CMNDF plane of
+  // the last call that asked for one, [total_frames][f0_cm_cols] (0: none yet) -- all grow-only
+  DevBuf<double> f0_uss; DevBuf<float> f0_raw, f0_cmndf; int f0_cm_cols = 0;
 };
 
 

@@ -1,5 +1,6 @@
-// dev_common.h -- device helpers shared by kernels.hip and l1_kernels.hip: wavefront reductions,
-// exact-phase sincos, and the in-place LDS wavefront FFT (see the comment block above fft_dif in kernels.hip).
+// dev_common.h -- device helpers shared by kernels.hip, l1_kernels.hip and f0_kernels.hip: wavefront reductions,
+// range-checked loads through a buffer descriptor (buf_range / ld_range), exact-phase sincos, and the in-place LDS
+// wavefront FFT (see the comment block above fft_dif in kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,6 +19,30 @@ DEV float wave_max(float v) {
 #pragma unroll
   for(int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
   return v;
+}
+
+// Range-checked loads in hardware: a raw buffer descriptor that covers elements [lo, hi) of p;
+// every load outside it (including negative indices: the byte offset is unsigned) returns 0
+// without touching memory.  One instruction per load, no compare / select -- for the windowed
+// frame loads, where "inside the window" and "inside the signal" intersect to one range per frame.
+typedef __amdgpu_buffer_rsrc_t buf_t;
+DEV buf_t buf_range(const float* p, int lo, int hi) {
+  const int n = hi > lo ? hi - lo : 0;
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(p + lo), 0, n * 4, 0x00020000);
+}
+// The byte offset is made opaque so that the compiler cannot split it into register + immediate
+// offset: with a NEGATIVE register part (window clipped at the start of the signal) and a positive
+// immediate the hardware range check does not always see the in-range sum (measured: wrong zeros in
+// k_harm_env on the first frames of an utterance; tools/ubench/buf_wrap.hip covers only the
+// small-negative case, which works).
+DEV float ld_range(buf_t r, int idx_minus_lo) {
+  int off = idx_minus_lo * 4;
+  asm volatile("" : "+v"(off));
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+}
+DEV float ld_range_b(buf_t r, int byte_off) {       // the same with the byte offset formed by the caller
+  asm volatile("" : "+v"(byte_off));
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
 }
 
 // (cos, sin)(2*pi*turns), turns in float64.  The phase is reduced to [-1/2, 1/2] turns in

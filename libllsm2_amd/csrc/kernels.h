@@ -308,4 +308,20 @@ int launch_blob_widths(LaunchCtx* P, const ModRows& r, const int* frm_off, const
 int launch_blob_pack(LaunchCtx* P, const ModRows& r, const llsm_wire::BlobEntry* tab, const float* chanfreq, int n,
   int max_nfrm, unsigned char* stage);
 
+// ---- F0 estimation of a batch's waveforms (f0.cpp, f0_kernels.hip; rules: llsm_gpu.h)
+// The batch's tables and waveforms, the sizes of llsm_gpu_f0_plan and the two float options as the float64 values the
+// rules compare against: threshold, and gate = silence_rel^2
+struct F0Dev {
+  int n_utt, nframes; float thop, fs;
+  const int* x_off; const int* nx; const int* frm_off; const int* nfrm; const int* frm_utt;
+  const int2* pairs; int npairs;                       // BatchDev::pairs: the two frames of one transform
+  const float* x;
+  int lmin, lmax, W;
+  double threshold, gate;
+};
+int launch_f0_energy(LaunchCtx* P, const F0Dev& d, double* uss);            // uss[u] = sum of x^2 over utterance u, float64
+// raw[g]: rules 2 - 7 of frame g; cmndf (or NULL): [nframes][lmax + 1]; logN: log2 of the transform, 8 ... 12
+int launch_f0_cmndf(LaunchCtx* P, const F0Dev& d, int logN, const double* uss, float* raw, float* cmndf);
+int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);   // rule 8
+
 #endif

@@ -113,31 +113,7 @@ DEV float ld_guard(const float* __restrict__ p, int idx, int n, bool ok) {
   const float v = p[in ? idx : 0];
   return in ? v : 0.0f;
 }
-// Range-checked loads in hardware: a raw buffer descriptor that covers elements [lo, hi) of p;
-// every load outside it (including negative indices: the byte offset is unsigned) returns 0
-// without touching memory.  One instruction per load, no compare / select -- for the windowed
-// frame loads, where "inside the window" and "inside the signal" intersect to one range per frame.
-typedef __amdgpu_buffer_rsrc_t buf_t;
-DEV buf_t buf_range(const float* p, int lo, int hi) {
-  const int n = hi > lo ? hi - lo : 0;
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(p + lo), 0, n * 4, 0x00020000);
-}
-// The byte offset is made opaque so that the compiler cannot split it into register + immediate
-// offset: with a NEGATIVE register part (window clipped at the start of the signal) and a positive
-// immediate the hardware range check does not always see the in-range sum (measured: wrong zeros in
-// k_harm_env on the first frames of an utterance; tools/ubench/buf_wrap.hip covers only the
-// small-negative case, which works).
-DEV float ld_range(buf_t r, int idx_minus_lo) {
-  int off = idx_minus_lo * 4;
-  asm volatile("" : "+v"(off));
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-
-
-DEV float ld_range_b(buf_t r, int byte_off) {       // the same with the byte offset formed by the caller
-  asm volatile("" : "+v"(byte_off));
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
-}
+// (buf_range / ld_range, the range-checked loads in hardware: dev_common.h)
 
 DEV float blackman_at(int t, int n) {           // symmetric, DESIGN.md "windows"
   if(n == 1) return 1.0f;
