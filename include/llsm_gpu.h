@@ -151,9 +151,11 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * which = 3: the band-limited noise templates of the last synthesis (dsputils.c:385-394), [n_utt][nchannel][ntemplate_ext];
  * utterance u uses the first min(20000, ny[u]) + 128 samples of a row, and the rows of channels that start at or above
  * the synthesis Nyquist are never written (layer0.c:562 leaves such a channel out).
- * which = 4: the CMNDF plane of the last llsm_gpu_batch_estimate_f0 of this batch that ran with keep_cmndf = 1 (rule 5
- * below that call), [total_frames][lmax + 1] with that call's lmax; the row of a gated frame is all ones.  Refused until
- * such a call has run; no other call writes it.
+ * which = 4: the CMNDF plane of the last llsm_gpu_batch_estimate_f0 or llsm_gpu_batch_track_f0 of this batch that ran
+ * with keep_cmndf = 1 (rule 5 below the former), [total_frames][lmax + 1] with that call's lmax; the row of a gated frame
+ * is all ones.  Refused until such a call has run; no other call writes it.
+ * which = 5: the candidate plane of the last llsm_gpu_batch_track_f0 of this batch (rule T1 below that call),
+ * [total_frames][24]: f0[0..7], cost[0..7], l2[0..7] per frame.  Refused until such a call has run; no other call writes it.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -344,7 +346,8 @@ int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0_ratio, con
 
 /* ---- F0 estimation: LLSM_GPU_X -> LLSM_GPU_F0 on the device, a YIN-style estimator (difference function, cumulative mean
  * normalised difference "CMNDF", first dip below a threshold, parabolic fit, median of five).  It is the estimator of
- * tests/golden/make_f0_track.py on the batch's frame grid; trackers with a path search (pYIN) are not provided.
+ * tests/golden/make_f0_track.py on the batch's frame grid and decides every frame alone; llsm_gpu_batch_track_f0 below
+ * searches a path through the candidate dips of the same CMNDF rows.
  * Asynchronous on the context's stream; a refused call returns -1, sets llsm_gpu_last_error() (the message starts with
  * "llsm_gpu_batch_estimate_f0:") and writes and launches nothing.  The call reads LLSM_GPU_X and writes all total_frames
  * entries of LLSM_GPU_F0 and nothing else; afterwards the batch's lowest-F0 bound is unknown, as after every call that
@@ -387,6 +390,51 @@ typedef struct {
 void llsm_gpu_f0_default_options(llsm_gpu_f0_options* dst);
 int  llsm_gpu_f0_plan(const llsm_gpu_f0_options* opt, FP_TYPE fs, int* lmin, int* lmax, int* W, int* nfft);
 int  llsm_gpu_batch_estimate_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt /* NULL: defaults */);
+
+/* ---- F0 tracking: LLSM_GPU_X -> LLSM_GPU_F0 on the device, a minimum-cost path (Viterbi) per utterance through the
+ * candidate dips of the CMNDF rows of llsm_gpu_batch_estimate_f0.  The estimator above takes the first dip below its
+ * threshold, which is the octave above wherever the odd harmonics fade (a formant on 2 F0) for longer than its median
+ * reaches; here every dip below cand_threshold is a candidate and continuity decides between them.  pYIN's probabilistic
+ * thresholds and HMM are not provided.
+ * Asynchronous on the context's stream; a refused call returns -1, sets llsm_gpu_last_error() (the message starts with
+ * "llsm_gpu_batch_track_f0:") and writes and launches nothing.  The call reads LLSM_GPU_X and writes all total_frames
+ * entries of LLSM_GPU_F0, scratch of its own (the candidate plane, llsm_gpu_batch_debug_plane(b, 5, ...), always kept) and
+ * nothing else; afterwards the batch's lowest-F0 bound is unknown.
+ * opt supplies fmin, fmax, silence_rel, window_extra and keep_cmndf to rules 1 - 5 above; its threshold and smooth are
+ * checked as llsm_gpu_batch_estimate_f0 checks them and otherwise not read.  NULL: the defaults, for either struct.
+ *
+ * The rules, per utterance.  Rules 1 - 5 above give the float32 row cm[0 .. lmax] and the gate (rule 3) of each frame.
+ *  T1. Candidates of a frame that is not gated: every lag tau in [lmin, lmax) with cm[tau] < cm[tau - 1], cm[tau] <=
+ *      cm[tau + 1] and cm[tau] < cand_threshold (float32 comparisons).  The K = 7 of lowest cm[tau] are kept, ties to the
+ *      smaller tau, and stored in that order: cost = cm[tau]; f0 = (float)(fs / (tau + off)) with off of rule 7 in float64;
+ *      l2 = (float)log2((double)f0).  n <= 7 is their number; a gated frame has none.  L = (float)log2((double)fs / lmin).
+ *      Row g of the candidate plane: f0[0..7], cost[0..7], l2[0..7]; slots n .. 6 are zero, f0[7] = cost[7] = 0, l2[7] = L.
+ *  T2. Eight states per frame: the candidate slots 0 .. 6, and unvoiced (7).  From here on float32, one rounding per
+ *      operation, no contraction.  loc[k] = cost[k] + octave_cost * (L - l2[k]) for k < n, +inf for n <= k < 7;
+ *      loc[7] = unvoiced_cost if n > 0, else 0.
+ *  T3. Transition from state a of frame i - 1 to state j of frame i: both voiced jump_cost * |l2_i[j] - l2_{i-1}[a]|; both
+ *      unvoiced 0; otherwise switch_cost.
+ *  T4. acc_0 = loc_0.  For i >= 1: acc_i[j] = min_a(acc_{i-1}[a] + tr(a, j)) + loc_i[j] over the a with finite acc_{i-1}[a],
+ *      the back pointer of j the smallest a that attains the minimum; then the smallest acc_i[j] of the frame is
+ *      subtracted from every acc_i[j].  The path ends in the smallest state of least acc on the last frame and follows the
+ *      back pointers from there.
+ *  T5. The F0 of frame i is f0_i[state], 0 for the unvoiced state.  There is no median pass.
+ * A frame's value depends on its own utterance only: not on the batch, the utterance's place in it, or any other call.
+ *
+ * Refused: everything llsm_gpu_batch_estimate_f0 refuses; a NaN or infinite track option; cand_threshold outside (0, 1]; a
+ * negative cost.  A batch without frames returns 0.
+ * llsm_gpu_f0_track_check is host only: 0, or -1 with the message llsm_gpu_batch_track_f0 would give for these track
+ * options (NULL: the defaults). */
+typedef struct {
+  FP_TYPE cand_threshold;  /* a local minimum of the CMNDF is a candidate if below this; default 0.5; (0, 1] */
+  FP_TYPE unvoiced_cost;   /* local cost of the unvoiced state on a frame that has candidates; default 0.2; >= 0 */
+  FP_TYPE switch_cost;     /* voiced <-> unvoiced transition; default 0.05; >= 0 */
+  FP_TYPE jump_cost;       /* per octave between consecutive voiced frames; default 0.5; >= 0 */
+  FP_TYPE octave_cost;     /* per octave below fs / lmin, added to a candidate's local cost; default 0.02; >= 0 */
+} llsm_gpu_f0_track_options;
+void llsm_gpu_f0_track_default_options(llsm_gpu_f0_track_options* dst);
+int  llsm_gpu_f0_track_check(const llsm_gpu_f0_track_options* topt);
+int  llsm_gpu_batch_track_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt, const llsm_gpu_f0_track_options* topt);
 
 /* ---- frame coder of a device-resident layer-1 batch: every frame <-> the vector [voicing, f0, Rd, order_spec mel-spectrum
  * points, order_bap band aperiodicities] of llsm_coder_encode_frames / llsm_coder_decode_frames (llsm.h), without leaving

@@ -80,6 +80,10 @@ class F0Options(C.Structure):                             # llsm_gpu_f0_options
                 ("smooth", C.c_int), ("keep_cmndf", C.c_int)]
 
 
+class F0TrackOptions(C.Structure):                        # llsm_gpu_f0_track_options
+    _fields_ = [("cand_threshold", fp), ("unvoiced_cost", fp), ("switch_cost", fp), ("jump_cost", fp), ("octave_cost", fp)]
+
+
 # frame / conf member indices (llsm.h)
 FRAME_F0, FRAME_HM, FRAME_NM, FRAME_PSDRES = 0, 1, 2, 3
 FRAME_PBPEFF, FRAME_PBPSYN, FRAME_RD, FRAME_VTMAGN, FRAME_VSPHSE = 8, 9, 10, 11, 12
@@ -142,6 +146,7 @@ llsm_gpu_batch_pitch_formant llsm_gpu_batch_splice
 llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode llsm_gpu_batch_decode
 llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu_batch_download_blob_block
 llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
+llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f0
 """.split()
 
 _lib = None
@@ -208,6 +213,14 @@ def load():
     L.llsm_gpu_f0_default_options.restype = None
     L.llsm_gpu_f0_plan.argtypes = [C.POINTER(F0Options), fp, P_int, P_int, P_int, P_int]
     L.llsm_gpu_batch_estimate_f0.argtypes = [vp, C.POINTER(F0Options)]
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the tracker)
+        L.llsm_gpu_f0_track_default_options.argtypes = [C.POINTER(F0TrackOptions)]
+        L.llsm_gpu_f0_track_default_options.restype = None
+        L.llsm_gpu_f0_track_check.argtypes = [C.POINTER(F0TrackOptions)]
+        L.llsm_gpu_batch_track_f0.argtypes = [vp, C.POINTER(F0Options), C.POINTER(F0TrackOptions)]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
     try:                                                 # (as above: an experiment build of an earlier commit lacks the coder)
         L.llsm_gpu_batch_enable_coder.argtypes = [vp, C.c_int, C.c_int]
         L.llsm_gpu_batch_coder_dimension.argtypes = [vp]
@@ -361,6 +374,17 @@ def make_f0_options(**kw):
     for k, v in kw.items():
         if k not in dict(F0Options._fields_):
             raise TypeError("llsm_gpu_f0_options has no member " + k)
+        setattr(o, k, v)
+    return o
+
+
+def make_f0_track_options(**kw):
+    """llsm_gpu_f0_track_default_options() with overrides"""
+    o = F0TrackOptions()
+    load().llsm_gpu_f0_track_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(F0TrackOptions._fields_):
+            raise TypeError("llsm_gpu_f0_track_options has no member " + k)
         setattr(o, k, v)
     return o
 
@@ -593,9 +617,18 @@ class Batch:
         o = make_f0_options(**options)
         _check(self.L.llsm_gpu_batch_estimate_f0(self.h, C.byref(o)), "estimate_f0")
 
+    def track_f0(self, f0=None, **track_options):
+        """the F0 row from the uploaded waveforms through the path search (llsm_gpu_batch_track_f0); f0: a dict of
+        members of llsm_gpu_f0_options or None; track_options: members of llsm_gpu_f0_track_options; defaults where
+        not given"""
+        o = make_f0_options(**(f0 or {}))
+        t = make_f0_track_options(**track_options)
+        _check(self.L.llsm_gpu_batch_track_f0(self.h, C.byref(o), C.byref(t)), "track_f0")
+
     def debug_plane(self, which):
         """intermediate plane `which` as a flat float32 array (llsm_gpu_batch_debug_plane; 4: the CMNDF rows of the
-        last estimate_f0(keep_cmndf=1), total_frames x (lmax + 1))"""
+        last estimate_f0 / track_f0 with keep_cmndf=1, total_frames x (lmax + 1); 5: the candidate rows of the last
+        track_f0, total_frames x 24)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())

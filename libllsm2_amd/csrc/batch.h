@@ -186,6 +186,9 @@ struct llsm_gpu_batch {
   // F0 estimation (f0.cpp): the utterances' sums of squares, the raw row before the median pass, and the CMNDF plane of
   // the last call that asked for one, [total_frames][f0_cm_cols] (0: none yet) -- all grow-only
   DevBuf<double> f0_uss; DevBuf<float> f0_raw, f0_cmndf; int f0_cm_cols = 0;
+  // F0 tracking (llsm_gpu_batch_track_f0): the candidate plane of the last call, [total_frames][24] (plane 5 of
+  // llsm_gpu_batch_debug_plane once a call has run), and one word of back pointers per frame -- grow-only
+  DevBuf<float> f0_cand; DevBuf<unsigned> f0_bp; bool f0_cand_filled = false;
 };
 
 

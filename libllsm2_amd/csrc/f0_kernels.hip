@@ -1,11 +1,13 @@
-// f0_kernels.hip -- F0 estimation of a batch's waveforms (llsm_gpu_batch_estimate_f0; rules: llsm_gpu.h, DESIGN.md
-// section 21; host side: f0.cpp).  Three kernels:
+// f0_kernels.hip -- F0 of a batch's waveforms: the estimator llsm_gpu_batch_estimate_f0 and the tracker
+// llsm_gpu_batch_track_f0 (rules: llsm_gpu.h, DESIGN.md sections 21 and 22; host side: f0.cpp).  Four kernels:
 //
 //   k_f0_energy      sum of squares of every utterance, float64, in an order fixed by the utterance's length
 //   k_f0_cmndf_wf    one wavefront per frame pair on the register-resident wavefront FFT (wave_fft.h): the YIN difference
-//                    function through a cross-correlation, the cumulative-mean-normalised difference (CMNDF), the lag
-//                    search and the parabolic fit -> one raw F0 per frame
-//   k_f0_median      the median-of-5 pass over the raw row of each utterance
+//                    function through a cross-correlation, the cumulative-mean-normalised difference (CMNDF), then
+//                    either the lag search and the parabolic fit -> one raw F0 per frame (estimator), or <, CAND = true>
+//                    the up to seven lowest dips of the row -> one candidate row per frame (tracker)
+//   k_f0_median      estimator: the median-of-5 pass over the raw row of each utterance
+//   k_f0_viterbi     tracker: one wavefront per utterance, the minimum-cost path through the candidate rows -> F0
 //
 // k_f0_cmndf_wf, per frame with segment s[0, W + lmax) (zero-padded to N = 2^LOGN >= W + lmax):
 //   the complex transform of z = a + j s, a = s[0, W), carries the spectra of both real sequences; they separate by
@@ -64,9 +66,36 @@ DEV double wave_scan_excl_d(double v, int lane) {
   return lane == 0 ? 0.0 : up;
 }
 
-template <int LOGN>
+// Cross-lane reads without the LDS pipe (data-parallel primitives of the vector ALU; every lane must be active): lane l
+// reads lane l ^ 1 or l ^ 2 (quad permutes), or the lane 4, 8 or 12 below it round its row of 16 lanes (row rotations).
+#define DPP_XOR1 0xB1
+#define DPP_XOR2 0x4E
+#define DPP_ROR4 0x124
+#define DPP_ROR8 0x128
+#define DPP_ROR12 0x12C
+template <int CTRL> DEV int dpp_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
+template <int CTRL> DEV float dpp_f(float v) { return __builtin_bit_cast(float, dpp_i<CTRL>(__builtin_bit_cast(int, v))); }
+DEV float lane_f(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+// the least v of the wavefront, on every lane: within the rows of 16 by permutes and rotations (a minimum may meet a
+// lane twice), then over the four rows
+DEV float wave_min_f(float v) {
+  v = fminf(v, dpp_f<DPP_XOR1>(v)); v = fminf(v, dpp_f<DPP_XOR2>(v));
+  v = fminf(v, dpp_f<DPP_ROR4>(v)); v = fminf(v, dpp_f<DPP_ROR8>(v));
+  return fminf(fminf(lane_f(v, 0), lane_f(v, 16)), fminf(lane_f(v, 32), lane_f(v, 48)));
+}
+DEV int wave_min_i(int v) {
+  v = min(v, dpp_i<DPP_XOR1>(v)); v = min(v, dpp_i<DPP_XOR2>(v));
+  v = min(v, dpp_i<DPP_ROR4>(v)); v = min(v, dpp_i<DPP_ROR8>(v));
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+#define F0_CB 4                                    // lags a lane looks at per group in the candidate search
+// CAND: rule T1 of llsm_gpu_batch_track_f0 instead of rules 6 - 7 -- the candidate row of the frame into c.plane, raw
+// not written
+template <int LOGN, bool CAND>
 __global__ __launch_bounds__(WAVE, (LOGN >= 12 ? 1 : 2)) void k_f0_cmndf_wf(F0Dev d, const double* __restrict__ uss,
-  float* __restrict__ raw, float* __restrict__ cmndf) {
+  float* __restrict__ raw, float* __restrict__ cmndf, F0Cand c) {
   constexpr int N = 1 << LOGN, P = N / WAVE, H = P / 2;
   const int lane = threadIdx.x;
   float2* lds = (float2*)g_lds;
@@ -125,6 +154,9 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 12 ? 1 : 2)) void k_f0_cmndf_wf(F0De
       wave_reflect<P>(c1r, xr, lane); wave_reflect<P>(vi, xi, lane);
     }
     wave_fft<LOGN>(xi, xr, tw, lds, lane);                            // inverse (x N): r1 in xr, r2 in xi
+    // CAND: lane 8 e + k keeps candidate k of frame e -- its lag and the three CMNDF values around it -- until both frames
+    // are through: the float64 of rule 7 and of the logarithm then has the registers of the transforms to itself
+    int c_tau = 0; float c_y0 = 0.0f, c_y1 = 0.0f, c_y2 = 0.0f; bool c_have = false;
 
 #pragma unroll
     for(int e = 0; e < 2; e ++) {
@@ -177,33 +209,93 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 12 ? 1 : 2)) void k_f0_cmndf_wf(F0De
           R[t] = cm;
         }
         __syncthreads();
-        // rule 6: the first lag below the threshold, then down the slope to where it stops falling
-        int tau = -1;
-        for(int b0 = lmin; b0 < lmax && tau < 0; b0 += WAVE) {
-          const int t = b0 + lane;
-          const unsigned long long hit = __ballot(t < lmax && (double)R[t < lmax ? t : 0] < d.threshold);
-          if(hit) tau = b0 + __ffsll((long long)hit) - 1;
-        }
-        if(tau >= 0) {
-          for(int b0 = tau; ; b0 += WAVE) {
-            const int t = b0 + lane;
-            const bool falls = t + 1 < lmax && R[t + 1 < lmax ? t + 1 : 0] < R[t + 1 < lmax ? t : 0];
-            const unsigned long long stop = __ballot(! falls);       // (t = lmax - 1 stops: the loop ends)
-            if(stop) { tau = b0 + __ffsll((long long)stop) - 1; break; }
+        if constexpr(CAND) {
+          // rule T1.  Each lane owns the lags lmin + lane + 64 m: the local-minimum test per lag, the candidates' values
+          // (else +inf) over the segment, which nobody reads any more, and the lane's lowest (value, lag)
+          // (an opaque copy of the lane, as above: what is derived from it is formed here, not kept across the transforms)
+          int ln = lane; asm volatile("" : "+v"(ln));
+          float* C = S;
+          // (F0_CB lags at a time, their reads issued together: one LDS latency per group, not per lag; a lag beyond the
+          // row reads the last one again and is not looked at)
+          float bv = INFINITY; int bt = 0x7fffffff;
+          for(int tb = lmin + ln; tb < lmax; tb += F0_CB * WAVE) {
+            float y0[F0_CB], y1[F0_CB], y2[F0_CB];
+#pragma unroll
+            for(int q = 0; q < F0_CB; q ++) {
+              const int t = min(tb + q * WAVE, lmax - 1);
+              y0[q] = R[t - 1]; y1[q] = R[t]; y2[q] = R[t + 1];
+            }
+#pragma unroll
+            for(int q = 0; q < F0_CB; q ++) {
+              const int t = tb + q * WAVE;
+              const bool is = t < lmax && y1[q] < y0[q] && y1[q] <= y2[q] && y1[q] < c.threshold;
+              if(t < lmax) C[t] = is ? y1[q] : INFINITY;
+              if(is && y1[q] < bv) { bv = y1[q]; bt = t; }
+            }
           }
-          // rule 7 (lmin >= 2 and tau < lmax: both neighbours are lags of the row)
-          const double y0 = (double)R[tau - 1], y1 = (double)R[tau], y2 = (double)R[tau + 1];
-          const double den = y0 - 2.0 * y1 + y2;
-          const double off = fabs(den) > 1e-12 ? 0.5 * (y0 - y2) / den : 0.0;
-          f0v = (float)((double)d.fs / ((double)tau + off));
+          // seven rounds of a wave-wide arg-min over (value, lag) -- the least value, then the least lag among the lanes
+          // that hold it; the lane that owned the winner strikes it out and looks through its lags again
+          for(int k = 0; k < 7; k ++) {
+            const float v = wave_min_f(bv);
+            if(!(v < INFINITY)) break;                                // (the same on every lane)
+            const int tv = wave_min_i(bv == v ? bt : 0x7fffffff);
+            if(ln == 8 * e + k) { c_tau = tv; c_y0 = R[tv - 1]; c_y1 = v; c_y2 = R[tv + 1]; c_have = true; }
+            if(((tv - lmin) & (WAVE - 1)) == ln) {
+              C[tv] = INFINITY;
+              bv = INFINITY; bt = 0x7fffffff;
+              for(int tb = lmin + ln; tb < lmax; tb += F0_CB * WAVE) {
+                float y[F0_CB];
+#pragma unroll
+                for(int q = 0; q < F0_CB; q ++) y[q] = C[min(tb + q * WAVE, lmax - 1)];
+#pragma unroll
+                for(int q = 0; q < F0_CB; q ++) { const int t = tb + q * WAVE; if(t < lmax && y[q] < bv) { bv = y[q]; bt = t; } }
+              }
+            }
+          }
+        } else {
+          // rule 6: the first lag below the threshold, then down the slope to where it stops falling
+          int tau = -1;
+          for(int b0 = lmin; b0 < lmax && tau < 0; b0 += WAVE) {
+            const int t = b0 + lane;
+            const unsigned long long hit = __ballot(t < lmax && (double)R[t < lmax ? t : 0] < d.threshold);
+            if(hit) tau = b0 + __ffsll((long long)hit) - 1;
+          }
+          if(tau >= 0) {
+            for(int b0 = tau; ; b0 += WAVE) {
+              const int t = b0 + lane;
+              const bool falls = t + 1 < lmax && R[t + 1 < lmax ? t + 1 : 0] < R[t + 1 < lmax ? t : 0];
+              const unsigned long long stop = __ballot(! falls);       // (t = lmax - 1 stops: the loop ends)
+              if(stop) { tau = b0 + __ffsll((long long)stop) - 1; break; }
+            }
+            // rule 7 (lmin >= 2 and tau < lmax: both neighbours are lags of the row)
+            const double y0 = (double)R[tau - 1], y1 = (double)R[tau], y2 = (double)R[tau + 1];
+            const double den = y0 - 2.0 * y1 + y2;
+            const double off = fabs(den) > 1e-12 ? 0.5 * (y0 - y2) / den : 0.0;
+            f0v = (float)((double)d.fs / ((double)tau + off));
+          }
         }
       }
-      if(lane == 0) raw[g] = f0v;
+      if(! CAND && lane == 0) raw[g] = f0v;
       if(cmndf) {
         float* row = cmndf + (size_t)g * (size_t)(lmax + 1);
         for(int t = lane; t <= lmax; t += WAVE) row[t] = gated ? 1.0f : R[t];
       }
       __syncthreads();                                                 // the next frame, or the next pair's transform, reuses the LDS
+    }
+    if constexpr(CAND) {
+      // slot lane & 7 of the row of frame g0 + (lane >> 3): rule 7 of the lane's lag, and its logarithm
+      float f0v = 0.0f, l2v = (lane & 7) == 7 ? c.L : 0.0f;
+      if(c_have) {
+        const double y0 = (double)c_y0, y1 = (double)c_y1, y2 = (double)c_y2;
+        const double den = y0 - 2.0 * y1 + y2;
+        const double off = fabs(den) > 1e-12 ? 0.5 * (y0 - y2) / den : 0.0;
+        f0v = (float)((double)d.fs / ((double)c_tau + off));
+        l2v = (float)log2((double)f0v);
+      }
+      if(lane < (two ? 16 : 8)) {
+        float* row = c.plane + (size_t)(g0 + (lane >> 3)) * 24 + (lane & 7);
+        row[0] = f0v; row[8] = c_y1; row[16] = l2v;
+      }
     }
   }
 }
@@ -236,6 +328,103 @@ __global__ __launch_bounds__(256) void k_f0_median(int nframes, const int* __res
   f0[g] = out;
 }
 
+// ---------------------------------------------------------------- the path through the candidates
+// Rules T2 - T5 of llsm_gpu_batch_track_f0, one wavefront per utterance.  Eight states (candidate slots 0 ... 6, and 7 =
+// unvoiced) give 64 transitions: lane 8 j + a owns the one from state a of frame i - 1 to state j of frame i.  What does
+// not depend on the running costs -- the local cost of j, the cost of the transition -- is formed for VIT_U frames at a
+// time from rows loaded one such block ahead; the dependent chain of a frame is one addition, the (value, a) minimum over
+// the eight lanes of a group, the local cost, the minimum over the groups, its subtraction, and the transposition that
+// hands acc[a] to the lanes 8 j + a.  The back pointers, 3 bits per state, are one word per frame: lane i % 64 keeps the
+// word of frame i and the wavefront stores 64 of them at a time.  The backtrack loads them 64 at a time as well and
+// walks them with scalar reads of the lanes; lane k notes the state of frame base + k and fetches its F0 afterwards.
+#define VIT_U 8
+struct VitRows { float fj[VIT_U], f00[VIT_U], cj[VIT_U], lj[VIT_U], la[VIT_U]; };
+// the rows of frames [base, base + VIT_U), as lane 8 j + a needs them; beyond the last frame: the last frame again
+DEV void vit_load(VitRows& r, const float* __restrict__ rows, int base, int n, int j, int a) {
+#pragma unroll
+  for(int k = 0; k < VIT_U; k ++) {
+    const float* row = rows + (size_t)min(base + k, n - 1) * 24;
+    r.fj[k] = row[j]; r.f00[k] = row[0]; r.cj[k] = row[8 + j]; r.lj[k] = row[16 + j]; r.la[k] = row[16 + a];
+  }
+}
+
+// the least of v over the eight groups, v being the same on the eight lanes of a group
+DEV float vit_min_groups(float v) {
+  v = fminf(v, dpp_f<DPP_ROR8>(v));
+  return fminf(fminf(lane_f(v, 0), lane_f(v, 16)), fminf(lane_f(v, 32), lane_f(v, 48)));
+}
+
+__global__ __launch_bounds__(WAVE) void k_f0_viterbi(const int* __restrict__ frm_off, const int* __restrict__ nfrm,
+  const float* __restrict__ plane, F0Track o, unsigned* __restrict__ bp, float* __restrict__ f0) {
+  const int u = blockIdx.x, lane = threadIdx.x, j = lane >> 3, a = lane & 7;
+  const int n = nfrm[u];
+  if(n <= 0) return;
+  const float* rows = plane + (size_t)frm_off[u] * 24;
+  unsigned* bpu = bp + frm_off[u];
+  float* out = f0 + frm_off[u];
+  const float L = rows[23];
+  float acc_a = 0.0f, acc_j = 0.0f, la_prev = 0.0f;                    // acc[a] of the frame before, acc[j] of this one
+  unsigned word = 0;                                                    // the back pointers of frame (i & ~63) + lane
+  VitRows cur, nxt;
+  vit_load(cur, rows, 0, n, j, a);
+  for(int b = 0; b < n; b += VIT_U) {
+    vit_load(nxt, rows, b + VIT_U, n, j, a);
+    float loc[VIT_U], tr[VIT_U];
+#pragma unroll
+    for(int k = 0; k < VIT_U; k ++) {
+      // T2 (a slot is taken when its F0 is not zero)
+      const float voiced = cur.fj[k] != 0.0f ? __fadd_rn(cur.cj[k], __fmul_rn(o.octave, __fsub_rn(L, cur.lj[k]))) : INFINITY;
+      loc[k] = j < 7 ? voiced : (cur.f00[k] != 0.0f ? o.unvoiced : 0.0f);
+      // T3
+      const float lp = k == 0 ? la_prev : cur.la[k > 0 ? k - 1 : 0];
+      tr[k] = j < 7 && a < 7 ? __fmul_rn(o.jump, fabsf(__fsub_rn(cur.lj[k], lp))) : (j == 7 && a == 7 ? 0.0f : o.sw);
+      if(b + k == 0) tr[k] = 0.0f;                                     // acc_0 = loc_0
+    }
+    la_prev = cur.la[VIT_U - 1];
+#pragma unroll
+    for(int k = 0; k < VIT_U; k ++) {
+      const int i = b + k;
+      if(i >= n) break;
+      // T4: the smallest a of the least acc[a] + tr(a, j), within the group of eight lanes
+      float v = __fadd_rn(acc_a, tr[k]); int arg = a;
+      auto take = [&](float ov, int oa) { if(ov < v || (ov == v && oa < arg)) { v = ov; arg = oa; } };
+      take(dpp_f<DPP_XOR1>(v), dpp_i<DPP_XOR1>(arg));
+      take(dpp_f<DPP_XOR2>(v), dpp_i<DPP_XOR2>(arg));
+      // lane ^ 4 is 12 or 4 lanes round the row; both reads are made with every lane active, then one is chosen
+      const float v_up = dpp_f<DPP_ROR12>(v), v_dn = dpp_f<DPP_ROR4>(v);
+      const int a_up = dpp_i<DPP_ROR12>(arg), a_dn = dpp_i<DPP_ROR4>(arg);
+      take(a < 4 ? v_up : v_dn, a < 4 ? a_up : a_dn);
+      v = __fadd_rn(v, loc[k]);
+      const float m = vit_min_groups(v);
+      if(i > 0) v = __fsub_rn(v, m);
+      acc_j = v;
+      acc_a = __shfl(v, 8 * a, WAVE);
+      // lane 3 s + t (below 24) contributes bit t of the back pointer of state s
+      const int as = __shfl(arg, 8 * (lane / 3), WAVE);
+      const unsigned w = (unsigned)__ballot(lane < 24 && ((as >> (lane % 3)) & 1));
+      if((i & (WAVE - 1)) == lane) word = w;
+      if(((i & (WAVE - 1)) == WAVE - 1 || i == n - 1) && lane <= (i & (WAVE - 1))) bpu[(i & ~(WAVE - 1)) + lane] = word;
+    }
+    cur = nxt;
+  }
+  // the path ends in the smallest state of least acc on the last frame
+  const float m = vit_min_groups(acc_j);
+  int s = __builtin_amdgcn_readfirstlane((__ffsll((long long)__ballot(acc_j == m)) - 1) >> 3);
+  for(int base = (n - 1) & ~(WAVE - 1); base >= 0; base -= WAVE) {
+    const int cnt = min(WAVE, n - base);
+    const int w = lane < cnt ? (int)bpu[base + lane] : 0;             // (the lane's own stores: the same thread reads them)
+    int st = 7;
+#pragma unroll
+    for(int k = WAVE - 1; k >= 0; k --) {
+      if(k < cnt) {
+        if(lane == k) st = s;
+        s = ((unsigned)__builtin_amdgcn_readlane(w, k) >> (3 * s)) & 7;   // T4: state of frame base + k - 1
+      }
+    }
+    if(lane < cnt) out[base + lane] = st < 7 ? rows[(size_t)(base + lane) * 24 + st] : 0.0f;   // T5
+  }
+}
+
 // ---------------------------------------------------------------- launchers
 int launch_f0_energy(LaunchCtx* P, const F0Dev& d, double* uss) {
   if(d.n_utt == 0) return 0;
@@ -243,17 +432,21 @@ int launch_f0_energy(LaunchCtx* P, const F0Dev& d, double* uss) {
   return 0;
 }
 
-int launch_f0_cmndf(LaunchCtx* P, const F0Dev& d, int logN, const double* uss, float* raw, float* cmndf) {
+int launch_f0_cmndf(LaunchCtx* P, const F0Dev& d, int logN, const double* uss, float* raw, float* cmndf, const F0Cand& c) {
   if(d.npairs == 0) return 0;
-  // one instantiation per transform size wave_fft.h has; -1: none for this size
-  return pick_int<8, 9, 10, 11, 12>(logN, -1, [&](auto ln) {
+  // one instantiation per transform size wave_fft.h has, with and without the candidate search; -1: none for this size
+  auto go = [&](auto ln, auto cand) {
     const size_t lds = sizeof(float2) * wf_lds_elems<ln>();
     // one-wavefront workgroups, each on a run of consecutive pairs: as many as stay resident, and 2048 at the least (a
     // floor, as for the other wavefront-FFT kernels: the runs are independent, so workgroups beyond the resident ones
     // -- LOGN 12 keeps 1024 -- simply follow them)
-    const int grid = std::min(d.npairs, std::max(resident_blocks((const void*)k_f0_cmndf_wf<ln>, WAVE, lds), 2048));
-    LAUNCH("k_f0_cmndf_wf", (k_f0_cmndf_wf<ln>), dim3(grid), dim3(WAVE), lds, d, uss, raw, cmndf);
+    const int grid = std::min(d.npairs, std::max(resident_blocks((const void*)k_f0_cmndf_wf<ln, cand>, WAVE, lds), 2048));
+    LAUNCH(cand ? "k_f0_cmndf_wf_cand" : "k_f0_cmndf_wf", (k_f0_cmndf_wf<ln, cand>), dim3(grid), dim3(WAVE), lds, d, uss, raw,
+      cmndf, c);
     return 0;
+  };
+  return pick_int<8, 9, 10, 11, 12>(logN, -1, [&](auto ln) {
+    return c.plane ? go(ln, std::true_type{}) : go(ln, std::false_type{});
   });
 }
 
@@ -261,5 +454,11 @@ int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0) 
   if(d.nframes == 0) return 0;
   LAUNCH("k_f0_median", k_f0_median, dim3((d.nframes + 255) / 256), dim3(256), 0, d.nframes, d.frm_utt, d.frm_off, d.nfrm,
     raw, f0);
+  return 0;
+}
+
+int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0) {
+  if(d.n_utt == 0 || d.nframes == 0) return 0;
+  LAUNCH("k_f0_viterbi", k_f0_viterbi, dim3(d.n_utt), dim3(WAVE), 0, d.frm_off, d.nfrm, plane, t, bp, f0);
   return 0;
 }

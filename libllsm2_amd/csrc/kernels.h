@@ -320,8 +320,16 @@ struct F0Dev {
   double threshold, gate;
 };
 int launch_f0_energy(LaunchCtx* P, const F0Dev& d, double* uss);            // uss[u] = sum of x^2 over utterance u, float64
-// raw[g]: rules 2 - 7 of frame g; cmndf (or NULL): [nframes][lmax + 1]; logN: log2 of the transform, 8 ... 12
-int launch_f0_cmndf(LaunchCtx* P, const F0Dev& d, int logN, const double* uss, float* raw, float* cmndf);
+// What the candidate search of llsm_gpu_batch_track_f0 adds (rule T1): the plane [nframes][24], cand_threshold, and
+// L = (float)log2(fs / lmin).  plane == NULL: the lag search of estimate_f0 (rules 6 - 7) into raw.
+struct F0Cand { float* plane; float threshold, L; };
+// the four costs of rules T2 - T3
+struct F0Track { float unvoiced, sw, jump, octave; };
+// raw[g]: rules 2 - 7 of frame g, or with c.plane the candidate row of frame g and raw not written; cmndf (or NULL):
+// [nframes][lmax + 1]; logN: log2 of the transform, 8 ... 12
+int launch_f0_cmndf(LaunchCtx* P, const F0Dev& d, int logN, const double* uss, float* raw, float* cmndf, const F0Cand& c);
 int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);   // rule 8
+// rules T2 - T5 over the candidate plane: f0[nframes]; bp: one word per frame of scratch
+int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0);
 
 #endif

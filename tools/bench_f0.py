@@ -1,11 +1,13 @@
 """Times llsm_gpu_batch_estimate_f0 at the bench shape (1 024 utterances x 200 frames, 44.1 kHz, thop = 5 ms, default
 options: 2 048-point transforms) and, beside it on the same box, the frames per second of the Python estimator it replaces
-(yin_track of tests/golden/make_f0_track.py on one CPU core, over a short stretch of one utterance).
+(yin_track of tests/golden/make_f0_track.py on one CPU core, over a short stretch of one utterance).  With --track,
+llsm_gpu_batch_track_f0 is timed the same way on the same batch in the same run, after the estimator.
 
 Prints one JSON object: ms per call (wall, and the sum of the kernels' HIP events), ms per call of each kernel
-(llsm_gpu_get_profile), frames per second of both, and the share of voiced frames found.
+(llsm_gpu_get_profile), frames per second of both, and the share of voiced frames found; with --track the same figures
+of the tracker under "track" (its CMNDF kernel is listed as k_f0_cmndf_wf_cand).
 
-    python tools/bench_f0.py [--utts 1024] [--steps 5] [--warmup 2] [--cpu-frames 40] [--keep-cmndf] [--out FILE]
+    python tools/bench_f0.py [--utts 1024] [--steps 5] [--warmup 2] [--cpu-frames 40] [--keep-cmndf] [--track] [--out FILE]
 """
 import argparse
 import json
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cpu-frames", type=int, default=40)
     ap.add_argument("--keep-cmndf", action="store_true")
+    ap.add_argument("--track", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n_utt = a.utts
@@ -39,26 +42,32 @@ def main():
     b.upload(llsm.A_X, x.ravel())
     opts = dict(keep_cmndf=int(a.keep_cmndf))
     plan = llsm.f0_plan(FS)
-    for _ in range(a.warmup):
-        b.estimate_f0(**opts)
-    ctx.sync()
-    walls = []
-    for _ in range(a.steps):                               # wall time of the call, no events
-        t0 = time.perf_counter(); b.estimate_f0(**opts); ctx.sync(); walls.append((time.perf_counter() - t0) * 1e3)
-    ctx.set_profiling(True); ctx.reset_profile()
-    for _ in range(a.steps):
-        b.estimate_f0(**opts)
-    ctx.sync()
-    prof = ctx.profile()
-    ctx.set_profiling(False)
-    kern = {k: v[0] / v[1] for k, v in prof.items() if v[1] > 0}
-    f0 = b.download(llsm.A_F0)
     F = n_utt * NFRM
-    wall = float(np.median(walls))
+
+    def measure(call):
+        for _ in range(a.warmup):
+            call()
+        ctx.sync()
+        walls = []
+        for _ in range(a.steps):                           # wall time of the call, no events
+            t0 = time.perf_counter(); call(); ctx.sync(); walls.append((time.perf_counter() - t0) * 1e3)
+        ctx.set_profiling(True); ctx.reset_profile()
+        for _ in range(a.steps):
+            call()
+        ctx.sync()
+        prof = ctx.profile()
+        ctx.set_profiling(False)
+        kern = {k: v[0] / v[1] for k, v in prof.items() if v[1] > 0}
+        f0 = b.download(llsm.A_F0)
+        wall = float(np.median(walls))
+        return dict(wall_ms=dict(min=min(walls), median=wall, max=max(walls)), kernels_ms=kern, kernels_ms_sum=sum(kern.values()),
+                    frames_per_s=F / (wall * 1e-3), voiced_share=float(np.count_nonzero(f0)) / F,
+                    f0_median=float(np.median(f0[f0 > 0])) if np.any(f0 > 0) else 0.0)
+
     out = dict(shape=dict(utterances=n_utt, frames=F, fs=FS, thop=THOP, **plan), keep_cmndf=bool(a.keep_cmndf),
-               wall_ms=dict(min=min(walls), median=wall, max=max(walls)), kernels_ms=kern, kernels_ms_sum=sum(kern.values()),
-               frames_per_s=F / (wall * 1e-3), voiced_share=float(np.count_nonzero(f0)) / F,
-               f0_median=float(np.median(f0[f0 > 0])) if np.any(f0 > 0) else 0.0)
+               **measure(lambda: b.estimate_f0(**opts)))
+    if a.track:
+        out["track"] = measure(lambda: b.track_f0(opts))
     b.close(); ctx.close()
     if a.cpu_frames > 0:
         from make_f0_track import yin_track
