@@ -156,6 +156,9 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * is all ones.  Refused until such a call has run; no other call writes it.
  * which = 5: the candidate plane of the last llsm_gpu_batch_track_f0 of this batch (rule T1 below that call),
  * [total_frames][24]: f0[0..7], cost[0..7], l2[0..7] per frame.  Refused until such a call has run; no other call writes it.
+ * which = 6: the distance planes of the last successful llsm_gpu_batch_align with this batch as a (rule D1 below that call):
+ * pair after pair in list order, each [na][nb] row-major, sum of na x nb floats.  Refused until such a call has run; no
+ * other call writes it.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -435,6 +438,53 @@ typedef struct {
 void llsm_gpu_f0_track_default_options(llsm_gpu_f0_track_options* dst);
 int  llsm_gpu_f0_track_check(const llsm_gpu_f0_track_options* topt);
 int  llsm_gpu_batch_track_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt, const llsm_gpu_f0_track_options* topt);
+
+/* ---- alignment: one minimum-cost monotonic path (dynamic time warping, DTW) per pair of utterances through the
+ * frame-distance matrix of their coder vectors (LLSM_GPU_CODE below), on the device.  It gives the list a morph needs --
+ * where, in frames of utterance B, each frame of utterance A belongs -- in the form llsm_gpu_batch_splice takes, and the
+ * accumulated cost of the path, which is what unit selection sorts a bank of candidates by.
+ * Pair p aligns utterance utt_a[p] of batch a (na frames) with utterance utt_b[p] of batch b (nb frames).  pos is a host
+ * array of sum_p na(p) floats, pair after pair in list order; its entries lie in [0, nb - 1], so they go into
+ * llsm_gpu_splice_map.pos_b (with utt_b) or .pos_a unchanged.  cost[p] (cost may be NULL) is the accumulated cost of
+ * the path of pair p.  Synchronous: on return both arrays are filled.  A refused call returns -1, sets
+ * llsm_gpu_last_error() (the message starts with "llsm_gpu_batch_align:"), launches nothing and leaves pos and cost
+ * untouched.  The call reads LLSM_GPU_CODE of both batches and writes no array of either; it writes scratch of its own
+ * on a only (the distance planes, llsm_gpu_batch_debug_plane(a, 6, ...), always kept); the lowest-F0 bound and every row
+ * stay as they were.  a == b is allowed, and an utterance may appear in any number of pairs.
+ *
+ * The rules, per pair.  A is the [na][dim] rows of a's LLSM_GPU_CODE for the utterance, B likewise.  Everything is
+ * float32, one rounding per operation, no contraction.
+ *  D1. d = 0; for k = first ... first + count - 1 ascending: t = A[i][k] - B[j][k]; d = d + t * t.  Then D[i][j] =
+ *      d + voicing_cost if exactly one of A[i][0], B[j][0] is > 0.5f, else d.  (The squared-difference form, not
+ *      |a|^2 + |b|^2 - 2ab: along the path the two frames are close, and the expanded form cancels there.)
+ *  D2. acc[0][0] = D[0][0].  Row 0: acc[0][j] = (acc[0][j-1] + step_cost) + D[0][j], move 2.  Column 0: acc[i][0] =
+ *      (acc[i-1][0] + step_cost) + D[i][0], move 1.  Elsewhere: m = acc[i-1][j-1], move 0; up = acc[i-1][j] + step_cost, if
+ *      up < m: m = up, move 1; lf = acc[i][j-1] + step_cost, if lf < m: m = lf, move 2; acc[i][j] = m + D[i][j].  The moves
+ *      on the two borders are forced and not compared, so a NaN in the features cannot send the path outside the matrix.
+ *  D3. The path runs from (na - 1, nb - 1) back along the moves (0: i - 1, j - 1; 1: i - 1; 2: j - 1) to (0, 0): at most
+ *      na + nb - 2 moves, whatever the bits of LLSM_GPU_CODE.  pos[i] = (float)(lo_i + hi_i) * 0.5f with lo_i and hi_i the
+ *      least and the largest j the path visits in row i; cost = acc[na-1][nb-1].
+ * A pair's result depends on its own two utterances and the options only: not on the other pairs, their order, the
+ * batches around them, or earlier calls.
+ *
+ * Refused: a NULL batch; n_pairs < 0; different contexts; coder not enabled on either batch, or different coder
+ * dimensions; a column range outside [0, dim); a NaN, infinite or negative cost; with n_pairs > 0 a NULL list or pos,
+ * an utterance index outside its batch, a named utterance without frames, and a sum of na x nb above 2^28 cells (the
+ * message names the total).  n_pairs == 0 returns 0.
+ * llsm_gpu_align_check is host only: 0, or -1 with the message llsm_gpu_batch_align would give for these options
+ * (NULL: the defaults) on batches whose coder has these orders.
+ * Known limits: the whole matrix of a pair is searched -- there is no diagonal band, so long material has to be cut
+ * into pairs that fit the 2^28 cells; there are no slope constraints beyond monotonicity. */
+typedef struct {
+  int     first, count;   /* columns [first, first + count) of LLSM_GPU_CODE are compared; defaults 3 and order_spec
+                             (count <= 0: order_spec): the mel-spectrum points */
+  FP_TYPE step_cost;      /* added to a move that is not diagonal; default 0; >= 0, finite */
+  FP_TYPE voicing_cost;   /* added to a cell whose two frames differ in voicing (code[0] > 0.5f); default 0; >= 0, finite */
+} llsm_gpu_align_options;
+void llsm_gpu_align_default_options(llsm_gpu_align_options* dst);
+int  llsm_gpu_align_check(const llsm_gpu_align_options* opt, int order_spec, int order_bap);
+int  llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
 
 /* ---- frame coder of a device-resident layer-1 batch: every frame <-> the vector [voicing, f0, Rd, order_spec mel-spectrum
  * points, order_bap band aperiodicities] of llsm_coder_encode_frames / llsm_coder_decode_frames (llsm.h), without leaving

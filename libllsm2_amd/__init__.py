@@ -84,6 +84,10 @@ class F0TrackOptions(C.Structure):                        # llsm_gpu_f0_track_op
     _fields_ = [("cand_threshold", fp), ("unvoiced_cost", fp), ("switch_cost", fp), ("jump_cost", fp), ("octave_cost", fp)]
 
 
+class AlignOptions(C.Structure):                          # llsm_gpu_align_options
+    _fields_ = [("first", C.c_int), ("count", C.c_int), ("step_cost", fp), ("voicing_cost", fp)]
+
+
 # frame / conf member indices (llsm.h)
 FRAME_F0, FRAME_HM, FRAME_NM, FRAME_PSDRES = 0, 1, 2, 3
 FRAME_PBPEFF, FRAME_PBPSYN, FRAME_RD, FRAME_VTMAGN, FRAME_VSPHSE = 8, 9, 10, 11, 12
@@ -147,6 +151,7 @@ llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode
 llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu_batch_download_blob_block
 llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
 llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f0
+llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
 """.split()
 
 _lib = None
@@ -218,6 +223,14 @@ def load():
         L.llsm_gpu_f0_track_default_options.restype = None
         L.llsm_gpu_f0_track_check.argtypes = [C.POINTER(F0TrackOptions)]
         L.llsm_gpu_batch_track_f0.argtypes = [vp, C.POINTER(F0Options), C.POINTER(F0TrackOptions)]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the alignment)
+        L.llsm_gpu_align_default_options.argtypes = [C.POINTER(AlignOptions)]
+        L.llsm_gpu_align_default_options.restype = None
+        L.llsm_gpu_align_check.argtypes = [C.POINTER(AlignOptions), C.c_int, C.c_int]
+        L.llsm_gpu_batch_align.argtypes = [vp, vp, C.c_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -385,6 +398,17 @@ def make_f0_track_options(**kw):
     for k, v in kw.items():
         if k not in dict(F0TrackOptions._fields_):
             raise TypeError("llsm_gpu_f0_track_options has no member " + k)
+        setattr(o, k, v)
+    return o
+
+
+def make_align_options(**kw):
+    """llsm_gpu_align_default_options() with overrides"""
+    o = AlignOptions()
+    load().llsm_gpu_align_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(AlignOptions._fields_):
+            raise TypeError("llsm_gpu_align_options has no member " + k)
         setattr(o, k, v)
     return o
 
@@ -628,7 +652,8 @@ class Batch:
     def debug_plane(self, which):
         """intermediate plane `which` as a flat float32 array (llsm_gpu_batch_debug_plane; 4: the CMNDF rows of the
         last estimate_f0 / track_f0 with keep_cmndf=1, total_frames x (lmax + 1); 5: the candidate rows of the last
-        track_f0, total_frames x 24)"""
+        track_f0, total_frames x 24; 6: the distance planes of the last align with this batch as a, pair after pair,
+        each na x nb)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -650,6 +675,24 @@ class Batch:
 
     def decode(self, use_layer1):
         _check(self.L.llsm_gpu_batch_decode(self.h, int(use_layer1)), "decode")
+
+    # ---- alignment (llsm_gpu.h): LLSM_GPU_CODE of two batches -> positions for splice and path costs
+    def align(self, other, utt_a, utt_b, **options):
+        """one minimum-cost monotonic path per pair (utterance utt_a[p] of this batch, utterance utt_b[p] of batch
+        `other`) through the distances of their coder vectors (llsm_gpu_batch_align); options: the members of
+        llsm_gpu_align_options, defaults where not given.  Returns (a list with one float32 array per pair: for every
+        frame of the utterance of this batch its position in frames of the other utterance, as splice takes it; the
+        float32 array of the path costs)"""
+        o = make_align_options(**options)
+        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
+        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
+        nfrm = np.diff(self.frm_off)
+        inside = ua[(ua >= 0) & (ua < len(nfrm))]                   # (an index outside is the library's to refuse)
+        na = np.zeros(len(ua), np.int64); na[(ua >= 0) & (ua < len(nfrm))] = nfrm[inside]
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        _check(self.L.llsm_gpu_batch_align(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                                           C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align")
+        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
 
     # ---- export as chunk blobs (llsm_gpu.h): the wire format of csrc/wire.cpp, packed on the device
     def _blob_range(self, utt0, n):

@@ -189,6 +189,12 @@ struct llsm_gpu_batch {
   // F0 tracking (llsm_gpu_batch_track_f0): the candidate plane of the last call, [total_frames][24] (plane 5 of
   // llsm_gpu_batch_debug_plane once a call has run), and one word of back pointers per frame -- grow-only
   DevBuf<float> f0_cand; DevBuf<unsigned> f0_bp; bool f0_cand_filled = false;
+  // alignment (align.cpp), scratch of the batch given as a: the distance planes of the last successful
+  // llsm_gpu_batch_align (plane 6 of llsm_gpu_batch_debug_plane; al_cells floats, 0: no call yet), the moves (2 bits per
+  // lane and step of k_align_dtw), the row one strip of 64 rows hands to the next, the pair and tile tables, and the
+  // device block [pos of every pair | cost of every pair] -- all grow-only
+  DevBuf<float> al_plane, al_row, al_out; DevBuf<uint4> al_moves; DevBuf<AlignPair> al_pairs; DevBuf<int4> al_tiles;
+  long long al_cells = 0;
 };
 
 

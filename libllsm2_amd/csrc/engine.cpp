@@ -603,6 +603,8 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> coder_mel.release();
   b -> blob_widths.release(); b -> blob_tab.release(); b -> blob_dev.release();
   b -> f0_uss.release(); b -> f0_raw.release(); b -> f0_cmndf.release(); b -> f0_cand.release(); b -> f0_bp.release();
+  b -> al_plane.release(); b -> al_row.release(); b -> al_out.release(); b -> al_moves.release(); b -> al_pairs.release();
+  b -> al_tiles.release();
   delete b;
 }
 
@@ -619,19 +621,21 @@ extern "C" int llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq) {
 // synthesize only read ce and colored, and no other call touches them: both hold the band filter's output until the next
 // analyze / synthesize of this batch.  4: the CMNDF plane of the last estimate_f0 / track_f0 with keep_cmndf = 1,
 // [total_frames][lmax + 1]; only such a call writes it.  5: the candidate plane of the last llsm_gpu_batch_track_f0,
-// [total_frames][24]; only such a call writes it.  dst == NULL: only the size.  Returns the number of floats of the
-// plane, -1 without one.
+// [total_frames][24]; only such a call writes it.  6: the distance planes of the last successful llsm_gpu_batch_align
+// with this batch as a, pair after pair, each [na][nb]; only such a call writes it.  dst == NULL: only the size.  Returns
+// the number of floats of the plane, -1 without one.
 extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap) {
-  if(! b || which < 0 || which > 5) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
+  if(! b || which < 0 || which > 6) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
   DevBuf<float>& src = which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : which == 3 ? b -> colored :
-                      which == 4 ? b -> f0_cmndf : b -> f0_cand;
+                      which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : b -> al_plane;
   const long long n = which <= 1 ? (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1) :
                       which == 2 ? (long long)b -> lay.nchannel * b -> lay.total_samples :
                       which == 3 ? (long long)b -> lay.n_utt * b -> lay.nchannel * b -> lay.ntemplate_ext :
                       which == 4 ? (long long)b -> lay.total_frames * b -> f0_cm_cols :
-                                   (long long)b -> lay.total_frames * 24;
+                      which == 5 ? (long long)b -> lay.total_frames * 24 : b -> al_cells;
   if(which == 4 && b -> f0_cm_cols == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_estimate_f0 with keep_cmndf has run on this batch"); return -1; }
   if(which == 5 && ! b -> f0_cand_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_track_f0 has run on this batch"); return -1; }
+  if(which == 6 && b -> al_cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align has run on this batch"); return -1; }
   if(which == 2 && ! b -> ce_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has filtered the bands of this batch"); return -1; }
   if(which == 3 && ! b -> colored_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no synthesis has filtered the templates of this batch"); return -1; }
   if(! src.p || n <= 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has run on this batch"); return -1; }

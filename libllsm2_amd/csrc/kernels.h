@@ -332,4 +332,20 @@ int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);
 // rules T2 - T5 over the candidate plane: f0[nframes]; bp: one word per frame of scratch
 int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0);
 
+// ---- alignment of utterance pairs (align.cpp, align_kernels.hip; rules D1 - D3: llsm_gpu.h)
+// One pair: rows [a0, a0 + na) of code_a against rows [b0, b0 + nb) of code_b (flat frame indices); its distance plane
+// starts at float cell0 of the plane, its moves at entry mv0 (ALIGN_STEPS(nb) entries of 16 bytes per strip of 64 rows),
+// its hand-over row at float row0, its positions at float pos0 of the out block
+struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, pad; long long mv0; };
+#define ALIGN_TILE 64                                  // k_align_dist: cells per side of a workgroup's tile
+#define ALIGN_STEPS(nb) ((long long)(nb) + 63)         // anti-diagonals of a strip of 64 rows
+struct AlignDev {
+  const float* code_a; const float* code_b; int dim, first, count; float step_cost, voicing_cost;
+  const AlignPair* pairs; int n_pairs;
+};
+// D1: tiles[t] = (pair, first row, first column, 0) of tile t; the planes of all pairs in one launch
+int launch_align_dist(LaunchCtx* P, const AlignDev& d, const int4* tiles, int n_tiles, float* plane);
+// D2 - D3 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
+int launch_align_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
+
 #endif
