@@ -159,6 +159,9 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * which = 6: the distance planes of the last successful llsm_gpu_batch_align with this batch as a (rule D1 below that call):
  * pair after pair in list order, each [na][nb] row-major, sum of na x nb floats.  Refused until such a call has run; no
  * other call writes it.
+ * which = 7 and 8: the candidate plane [total_frames][16] (rule S2 below llsm_gpu_batch_select) and the join plane
+ * [total_frames][64] (rule S3) of the last successful llsm_gpu_batch_select with this batch as t.  Refused until such a
+ * call has run; no other call writes them.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -485,6 +488,71 @@ void llsm_gpu_align_default_options(llsm_gpu_align_options* dst);
 int  llsm_gpu_align_check(const llsm_gpu_align_options* opt, int order_spec, int order_bap);
 int  llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+
+/* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
+ * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere
+ * in the bank -- and then one minimum-cost path per target utterance through these candidates, with a join cost between
+ * the choices of neighbouring frames that is zero where the bank simply continues.  It gives the index lists
+ * llsm_gpu_batch_splice renders, so that encode -> select -> splice -> tolayer0 -> synthesize stays on the device.
+ * utt and pos are host arrays of t.total_frames entries in t's flat frame order: utt[g] is the bank utterance and pos[g]
+ * the frame within it, as a float, of the bank frame chosen for target frame g.  They go into llsm_gpu_splice_map.utt_a /
+ * .pos_a unchanged (dst shaped like t, src = bank), or into the _b side.  cost[u] (cost may be NULL; n_utt entries of t)
+ * is the accumulated cost of the path of utterance u, 0 for an utterance without frames.  Synchronous: on return the
+ * arrays are filled.  A refused call returns -1, sets llsm_gpu_last_error() (the message starts with
+ * "llsm_gpu_batch_select:"), launches nothing and leaves the three arrays untouched.  The call reads LLSM_GPU_CODE of both
+ * batches and writes no array of either; it writes scratch of its own on t only (planes 7 and 8 of
+ * llsm_gpu_batch_debug_plane among it); the lowest-F0 bound and every row stay as they were.  t == bank is allowed.
+ *
+ * The rules.  T is the [t.total_frames][dim] rows of t's LLSM_GPU_CODE, B the rows of the bank's, f a flat frame index
+ * of the bank in its frame order.  Everything is float32, one rounding per operation, no contraction.
+ *  S1. d(x, y) is rule D1 above between the rows x and y: d = 0; for k = first ... first + count - 1 ascending:
+ *      t = x[k] - y[k]; d = d + t * t; then d + voicing_cost if exactly one of x[0], y[0] is > 0.5f.  c(x, y) = d if
+ *      d < 1e30f (a float32 comparison), else 1e30f: a NaN or infinite distance becomes 1e30f.  Nothing from here on can
+ *      produce a NaN: every term is >= 0 and finite or +infinity, there is no subtraction, and no product of 0 with an
+ *      infinity (c is finite).  An infinity is possible only where the options are that large: join_weight * c and
+ *      join_cost + ... overflow float32 above about 3.4e38 (join_weight 1e30 on c = 1e30, say), and so may a long sum of
+ *      such terms.  Infinite costs compare and tie like any others under S4, and every index stays in the bank.
+ *  S2. Every bank frame is eligible for target frame g of utterance u; with skip_own_utterance the frames of bank
+ *      utterance u are not.  The K = 8 eligible frames that are lowest under the total order (c(T[g], B[f]), f)
+ *      ascending are kept, in that order; n_u = min(8, eligible frames) is the same for every frame of u.  Plane 7,
+ *      [t.total_frames][16]: row g holds c[0..7] and then the frame indices as floats; slots >= n_u hold 1e30f and -1.
+ *      The order is total, so the result does not depend on how the bank is cut among workgroups.
+ *  S3. For frame i >= 1 of an utterance, slot a of frame i - 1 (bank frame fa) and slot j of frame i (bank frame fb):
+ *      if fb == fa + 1 and both lie in one bank utterance, J = 0 (a natural continuation).  Otherwise s = fa + 1 if that
+ *      frame lies in fa's utterance, else fa, and J = join_cost + join_weight * c(B[s], B[fb]): one multiplication, then
+ *      one addition.  Plane 8, [t.total_frames][64]: entry 8 a + j; the rows of first frames and the entries of absent
+ *      slots are 0.
+ *  S4. States are the slots 0 ... n_u - 1; an absent slot is never a predecessor or an end state.  acc_0[j] = c_0[j].
+ *      For i >= 1: m is found over a ascending, starting with acc_{i-1}[0] + J(0, j) and replaced only by a strictly
+ *      smaller acc_{i-1}[a] + J(a, j); the back pointer is that a; acc_i[j] = m + c_i[j].  No per-frame normalisation.
+ *      The path ends in the smallest state of least acc on the last frame and follows the back pointers; cost[u] is
+ *      that acc.
+ *  S5. utt[g] is the bank utterance of the chosen slot's bank frame and pos[g] = (float)(its frame within that utterance).
+ * A target utterance's result depends on its own rows, the bank and the options only: not on the other target
+ * utterances, its place in t, or earlier calls.
+ *
+ * Refused, before anything is allocated or launched: a NULL batch; different contexts; coder not enabled on either batch,
+ * or different coder dimensions; a column range outside [0, dim); a NaN, infinite or negative cost or weight;
+ * skip_own_utterance not 0 or 1, or 1 with t != bank; with target frames present a NULL utt or pos, a bank without
+ * frames, a bank of more than 2^24 frames (plane 7 keeps indices as floats), and skip_own_utterance leaving a target
+ * utterance that has frames without an eligible bank frame.  A t without frames returns 0.
+ * llsm_gpu_select_check is host only: 0, or -1 with the message llsm_gpu_batch_select would give for these options
+ * (NULL: the defaults) on batches whose coder has these orders.
+ * Known limits: the candidates are the eight nearest frames only -- the successors of the previous frame's candidates are
+ * not added, so a continuation that is not itself among the eight nearest is not considered.  The search is exact and
+ * exhaustive: there is no index, and no matrix-core form, because the squared-difference rule has two roundings per term. */
+typedef struct {
+  int     first, count;        /* columns [first, first + count) of LLSM_GPU_CODE are compared; defaults 3 and order_spec
+                                  (count <= 0: order_spec) */
+  FP_TYPE voicing_cost;        /* as llsm_gpu_align_options; default 0; >= 0, finite */
+  FP_TYPE join_cost;           /* added to every transition that is not a natural continuation; default 0; >= 0, finite */
+  FP_TYPE join_weight;         /* weight of the spectral join distance; default 1; >= 0, finite */
+  int     skip_own_utterance;  /* 1: with t == bank, frames of the target's own utterance are not candidates; default 0 */
+} llsm_gpu_select_options;
+void llsm_gpu_select_default_options(llsm_gpu_select_options* dst);
+int  llsm_gpu_select_check(const llsm_gpu_select_options* opt, int order_spec, int order_bap);
+int  llsm_gpu_batch_select(llsm_gpu_batch* t, const llsm_gpu_batch* bank, const llsm_gpu_select_options* opt /* NULL: defaults */,
+       int* utt, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
 
 /* ---- frame coder of a device-resident layer-1 batch: every frame <-> the vector [voicing, f0, Rd, order_spec mel-spectrum
  * points, order_bap band aperiodicities] of llsm_coder_encode_frames / llsm_coder_decode_frames (llsm.h), without leaving

@@ -88,6 +88,11 @@ class AlignOptions(C.Structure):                          # llsm_gpu_align_optio
     _fields_ = [("first", C.c_int), ("count", C.c_int), ("step_cost", fp), ("voicing_cost", fp)]
 
 
+class SelectOptions(C.Structure):                         # llsm_gpu_select_options
+    _fields_ = [("first", C.c_int), ("count", C.c_int), ("voicing_cost", fp), ("join_cost", fp), ("join_weight", fp),
+                ("skip_own_utterance", C.c_int)]
+
+
 # frame / conf member indices (llsm.h)
 FRAME_F0, FRAME_HM, FRAME_NM, FRAME_PSDRES = 0, 1, 2, 3
 FRAME_PBPEFF, FRAME_PBPSYN, FRAME_RD, FRAME_VTMAGN, FRAME_VSPHSE = 8, 9, 10, 11, 12
@@ -152,6 +157,7 @@ llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu
 llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
 llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f0
 llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
+llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select
 """.split()
 
 _lib = None
@@ -231,6 +237,14 @@ def load():
         L.llsm_gpu_align_default_options.restype = None
         L.llsm_gpu_align_check.argtypes = [C.POINTER(AlignOptions), C.c_int, C.c_int]
         L.llsm_gpu_batch_align.argtypes = [vp, vp, C.c_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the selection)
+        L.llsm_gpu_select_default_options.argtypes = [C.POINTER(SelectOptions)]
+        L.llsm_gpu_select_default_options.restype = None
+        L.llsm_gpu_select_check.argtypes = [C.POINTER(SelectOptions), C.c_int, C.c_int]
+        L.llsm_gpu_batch_select.argtypes = [vp, vp, C.POINTER(SelectOptions), P_int, P_fp, P_fp]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -409,6 +423,17 @@ def make_align_options(**kw):
     for k, v in kw.items():
         if k not in dict(AlignOptions._fields_):
             raise TypeError("llsm_gpu_align_options has no member " + k)
+        setattr(o, k, v)
+    return o
+
+
+def make_select_options(**kw):
+    """llsm_gpu_select_default_options() with overrides"""
+    o = SelectOptions()
+    load().llsm_gpu_select_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(SelectOptions._fields_):
+            raise TypeError("llsm_gpu_select_options has no member " + k)
         setattr(o, k, v)
     return o
 
@@ -653,7 +678,8 @@ class Batch:
         """intermediate plane `which` as a flat float32 array (llsm_gpu_batch_debug_plane; 4: the CMNDF rows of the
         last estimate_f0 / track_f0 with keep_cmndf=1, total_frames x (lmax + 1); 5: the candidate rows of the last
         track_f0, total_frames x 24; 6: the distance planes of the last align with this batch as a, pair after pair,
-        each na x nb)"""
+        each na x nb; 7 and 8: the candidate rows, total_frames x 16, and the join costs, total_frames x 64, of the last select
+        with this batch as the target)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -693,6 +719,20 @@ class Batch:
         _check(self.L.llsm_gpu_batch_align(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
                                            C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align")
         return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+
+    # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders
+    def select(self, bank, opt=None, **options):
+        """for every frame of this batch the frame of `bank` that renders it (llsm_gpu_batch_select): the eight nearest
+        bank frames per frame, then a minimum-cost path per utterance with a join cost.  opt: a SelectOptions (None: the
+        defaults), or its members as keywords.  Returns (utt int32 [total_frames], pos float32 [total_frames], as splice
+        takes them for utt_a / pos_a with src = bank; cost float32 [n_utt])"""
+        assert opt is None or not options
+        o = opt if opt is not None else make_select_options(**options)
+        n = int(self.frm_off[-1])
+        utt = np.zeros(n, np.int32); pos = np.zeros(n, np.float32); cost = np.zeros(self.layout.n_utt, np.float32)
+        _check(self.L.llsm_gpu_batch_select(self.h, bank.h, C.byref(o), utt.ctypes.data_as(P_int), pos.ctypes.data_as(P_fp),
+                                            cost.ctypes.data_as(P_fp)), "select")
+        return utt, pos, cost
 
     # ---- export as chunk blobs (llsm_gpu.h): the wire format of csrc/wire.cpp, packed on the device
     def _blob_range(self, utt0, n):

@@ -26,7 +26,7 @@ SOURCES = ["kernels.hip", "synth_kernels.hip", "l1_kernels.hip", "frame_kernels.
            "engine.cpp", "capi.cpp", "model.cpp", "rt.cpp", "wire.cpp",
            "modify_kernels.hip", "modify.cpp", "coder_kernels.hip", "batch_coder.cpp",
            "blob_kernels.hip", "batch_blob.cpp", "f0_kernels.hip", "f0.cpp",
-           "align_kernels.hip", "align.cpp"]
+           "align_kernels.hip", "align.cpp", "select_kernels.hip", "select.cpp"]
 import glob
 # every header a source may include: csrc/*.h (launch.h was missing from a hand-kept list: ADVICE r4), include/*.h, and the
 # timing experiments' header, which only -DLLSM_KBENCH_EXPERIMENTS builds include

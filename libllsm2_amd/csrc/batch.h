@@ -195,6 +195,12 @@ struct llsm_gpu_batch {
   // device block [pos of every pair | cost of every pair] -- all grow-only
   DevBuf<float> al_plane, al_row, al_out; DevBuf<uint4> al_moves; DevBuf<AlignPair> al_pairs; DevBuf<int4> al_tiles;
   long long al_cells = 0;
+  // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
+  // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful
+  // llsm_gpu_batch_select; sel_frames 0: no call yet), the back pointers (3 bits per state at bit 8 j, one word pair per
+  // frame) and the device block [utt | pos | cost] -- all grow-only
+  DevBuf<float> sel_lists, sel_p7, sel_p8; DevBuf<uint2> sel_bp; DevBuf<int> sel_out;
+  long long sel_frames = 0;
 };
 
 

@@ -348,4 +348,32 @@ int launch_align_dist(LaunchCtx* P, const AlignDev& d, const int4* tiles, int n_
 // D2 - D3 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
 int launch_align_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
 
+// ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5: llsm_gpu.h)
+#define SELECT_K 8                                     // candidates kept per target frame
+#define SELECT_SEG 1024                                // k_select_knn: bank frames per segment at the least ...
+#define SELECT_MAX_SEG 64                              // ... and segments at the most (one lane each in k_select_merge)
+// the segment rule, of the bank's frames n alone: the bank is cut into min(64, ceil(n / 1024)) parts, a part rounded up to
+// a multiple of 64 frames is the segment length, and the segments are as many of that length as cover the bank
+static inline int select_seg_len(int n) {
+  int s = (n + SELECT_SEG - 1) / SELECT_SEG; s = s < 1 ? 1 : s > SELECT_MAX_SEG ? SELECT_MAX_SEG : s;
+  return (int)((((long long)n + s - 1) / s + 63) / 64 * 64);
+}
+static inline int select_segments(int n) { const int l = select_seg_len(n); const int s = (n + l - 1) / l; return s < 1 ? 1 : s; }
+struct SelectDev {
+  const float* code_t; const float* code_b; int dim, first, count;      // rows of t and of the bank
+  float voicing_cost, join_cost, join_weight; int skip_own;
+  int nt, nb, n_utt;                                                      // frames of t, frames of the bank, utterances of t
+  const int* t_frm_off; const int* t_nfrm; const int* t_frm_utt;          // t: per utterance, per utterance, per frame
+  const int* b_frm_off; const int* b_nfrm; const int* b_frm_utt;          // the bank likewise
+  int n_seg, seg_len;
+};
+// S1 - S2 per bank segment: lists[seg][nt][16] (n_seg == 1: plane 7 itself)
+int launch_select_knn(LaunchCtx* P, const SelectDev& d, float* lists);
+// the K lowest of the n_seg lists of every target frame -> plane 7 [nt][16]
+int launch_select_merge(LaunchCtx* P, const SelectDev& d, const float* lists, float* p7);
+// S3: plane 8 [nt][64] from plane 7
+int launch_select_join(LaunchCtx* P, const SelectDev& d, const float* p7, float* p8);
+// S4 - S5, one wavefront per utterance of t: out = [utt of every frame | pos of every frame (float bits) | cost per utterance (float bits)]
+int launch_select_path(LaunchCtx* P, const SelectDev& d, const float* p7, const float* p8, uint2* bp, int* out);
+
 #endif
