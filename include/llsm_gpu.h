@@ -162,6 +162,10 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * which = 7 and 8: the candidate plane [total_frames][16] (rule S2 below llsm_gpu_batch_select) and the join plane
  * [total_frames][64] (rule S3) of the last successful llsm_gpu_batch_select with this batch as t.  Refused until such a
  * call has run; no other call writes them.
+ * which = 9: the band planes of the last successful llsm_gpu_batch_align_band with this batch as a (rules B1 - B2 below that
+ * call): pair after pair in list order, each [na][2 band + 1] row-major; entry q of row i is column c_i - band + q, and the
+ * entries whose column lies outside [lo_i, hi_i] hold +infinity.  Refused until such a call has run; no other call writes
+ * it, and that call does not write plane 6.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -476,8 +480,9 @@ int  llsm_gpu_batch_track_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt, 
  * message names the total).  n_pairs == 0 returns 0.
  * llsm_gpu_align_check is host only: 0, or -1 with the message llsm_gpu_batch_align would give for these options
  * (NULL: the defaults) on batches whose coder has these orders.
- * Known limits: the whole matrix of a pair is searched -- there is no diagonal band, so long material has to be cut
- * into pairs that fit the 2^28 cells; there are no slope constraints beyond monotonicity. */
+ * Known limits: the whole matrix of a pair is searched, so a call holds pairs of 2^28 cells in all -- long material goes
+ * through llsm_gpu_batch_align_band below, which searches a band around the diagonal; there are no slope constraints beyond
+ * monotonicity. */
 typedef struct {
   int     first, count;   /* columns [first, first + count) of LLSM_GPU_CODE are compared; defaults 3 and order_spec
                              (count <= 0: order_spec): the mel-spectrum points */
@@ -488,6 +493,46 @@ void llsm_gpu_align_default_options(llsm_gpu_align_options* dst);
 int  llsm_gpu_align_check(const llsm_gpu_align_options* opt, int order_spec, int order_bap);
 int  llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+
+/* ---- alignment inside a diagonal band: llsm_gpu_batch_align for long utterances.  The path of pair p is searched among
+ * the cells within band[p] columns of the straight diagonal only, so the planes, the moves and the time of a pair are
+ * na x (2 band + 1) instead of na x nb, and two five-minute renditions (60 000 frames each) under a band of 500 frames are
+ * 6e7 cells instead of 3.6e9.  band is a host array of n_pairs half-widths in frames.  The contract is that of
+ * llsm_gpu_batch_align -- the same pos and cost, synchronous, a refused call returns -1 with a message that starts with
+ * "llsm_gpu_batch_align_band:", launches nothing and leaves pos and cost untouched; LLSM_GPU_CODE of both batches is read and
+ * no array of either written; a == b is allowed -- with scratch of its own on a (the band planes,
+ * llsm_gpu_batch_debug_plane(a, 9, ...), always kept): the scratch of llsm_gpu_batch_align, plane 6 among it, stays as the
+ * last such call left it.  A pair's result depends on its own two utterances, its band and the options only.
+ *
+ * The rules, per pair; float32, one rounding per operation, no contraction.
+ *  B1. The band.  na > 1: c_i = (2 i (nb - 1) + (na - 1)) / (2 (na - 1)) in 64-bit integer division, the diagonal rounded
+ *      half up; na == 1: c_0 = 0.  Row i spans the columns lo_i = max(0, c_i - band) ... hi_i = min(nb - 1, c_i + band).
+ *      The band is connected when lo_{i+1} <= hi_i + 1 for every i and hi_{na-1} == nb - 1; a connected band contains
+ *      (0, 0) and (na - 1, nb - 1), and every cell of it other than (0, 0) has at least one predecessor inside it.
+ *      llsm_gpu_align_band_min returns the least connected band (0 for na >= nb with na > 1, nb - 1 for na == 1, 1 for
+ *      63 x 64, 31 for 2 x 63), -1 if na < 1 or nb < 1.  llsm_gpu_align_band_rows fills lo and hi (na entries each) and
+ *      returns 0, or -1 with a message for na < 1, nb < 1, a NULL array, and a band that is negative or not connected.
+ *      Both are host only and need no device.
+ *  B2. D[i][j] is rule D1 unchanged, for the cells inside the band only.
+ *  B3. acc[0][0] = D[0][0].  Elsewhere the candidates are the predecessors that lie inside the band, in this order:
+ *      acc[i-1][j-1], move 0; acc[i-1][j] + step_cost, move 1; acc[i][j-1] + step_cost, move 2.  m starts from the first
+ *      candidate that exists, and a later one replaces it only if it is strictly smaller; acc[i][j] = m + D[i][j].  Whether a
+ *      predecessor is inside the band is decided by integer comparisons with lo and hi, never by the values, so a NaN or an
+ *      infinity in the features cannot send the path outside the band.  Where the band covers the whole matrix this is D2
+ *      bit for bit: on row 0 only the left candidate exists, on column 0 only the upper one, elsewhere all three.
+ *  B4. D3 unchanged, over the moves of B3: at most na + nb - 2 moves, every cell of the path inside the band;
+ *      cost = acc[na-1][nb-1].
+ *
+ * Refused: everything llsm_gpu_batch_align refuses, and with n_pairs > 0 a NULL band, a negative band, a band that is not
+ * connected for its pair (the message names the pair and llsm_gpu_align_band_min of it), and a sum of na x (2 band + 1)
+ * above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
+ * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else, so it has to be as
+ * wide as the renditions drift apart; there are no slope constraints beyond monotonicity. */
+int  llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       const int* band /* n_pairs half-widths, frames */, const llsm_gpu_align_options* opt /* NULL: defaults */,
+       FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+int  llsm_gpu_align_band_min(int na, int nb);                              /* host only */
+int  llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* hi);  /* host only; na entries each */
 
 /* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
  * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere

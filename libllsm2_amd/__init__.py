@@ -157,6 +157,7 @@ llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu
 llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
 llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f0
 llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
+llsm_gpu_batch_align_band llsm_gpu_align_band_min llsm_gpu_align_band_rows
 llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select
 """.split()
 
@@ -237,6 +238,13 @@ def load():
         L.llsm_gpu_align_default_options.restype = None
         L.llsm_gpu_align_check.argtypes = [C.POINTER(AlignOptions), C.c_int, C.c_int]
         L.llsm_gpu_batch_align.argtypes = [vp, vp, C.c_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the banded alignment)
+        L.llsm_gpu_batch_align_band.argtypes = [vp, vp, C.c_int, P_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
+        L.llsm_gpu_align_band_min.argtypes = [C.c_int, C.c_int]
+        L.llsm_gpu_align_band_rows.argtypes = [C.c_int, C.c_int, C.c_int, P_int, P_int]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -425,6 +433,23 @@ def make_align_options(**kw):
             raise TypeError("llsm_gpu_align_options has no member " + k)
         setattr(o, k, v)
     return o
+
+
+def align_band_min(na, nb):
+    """the least connected band of an na x nb pair (llsm_gpu_align_band_min, rule B1 of llsm_gpu_batch_align_band)"""
+    r = load().llsm_gpu_align_band_min(int(na), int(nb))
+    if r < 0:
+        raise LlsmError("align_band_min: " + load().llsm_gpu_last_error().decode())
+    return int(r)
+
+
+def align_band_rows(na, nb, band):
+    """(lo, hi): the first and the last column of every row of an na x nb pair under this band, int32 [na] each
+    (llsm_gpu_align_band_rows); a band that is negative or not connected is refused"""
+    lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
+    _check(load().llsm_gpu_align_band_rows(int(na), int(nb), int(band), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
+           "align_band_rows")
+    return lo, hi
 
 
 def make_select_options(**kw):
@@ -679,7 +704,8 @@ class Batch:
         last estimate_f0 / track_f0 with keep_cmndf=1, total_frames x (lmax + 1); 5: the candidate rows of the last
         track_f0, total_frames x 24; 6: the distance planes of the last align with this batch as a, pair after pair,
         each na x nb; 7 and 8: the candidate rows, total_frames x 16, and the join costs, total_frames x 64, of the last select
-        with this batch as the target)"""
+        with this batch as the target; 9: the band planes of the last align_band with this batch as a, pair after pair,
+        each na x (2 band + 1), +inf outside the rows' ranges)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -718,6 +744,22 @@ class Batch:
         pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
         _check(self.L.llsm_gpu_batch_align(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
                                            C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align")
+        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+
+    def align_band(self, other, utt_a, utt_b, band, **options):
+        """align within `band` columns of the straight diagonal (llsm_gpu_batch_align_band): what long utterances need,
+        whose full matrices align refuses.  band: an int, or one int per pair.  Returns what align returns"""
+        o = make_align_options(**options)
+        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
+        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
+        bd = np.ascontiguousarray(np.broadcast_to(np.asarray(band, np.int32), ua.shape))
+        nfrm = np.diff(self.frm_off)
+        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
+        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        _check(self.L.llsm_gpu_batch_align_band(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                                                bd.ctypes.data_as(P_int), C.byref(o), pos.ctypes.data_as(P_fp),
+                                                cost.ctypes.data_as(P_fp)), "align_band")
         return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders

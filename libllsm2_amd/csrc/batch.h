@@ -195,6 +195,10 @@ struct llsm_gpu_batch {
   // device block [pos of every pair | cost of every pair] -- all grow-only
   DevBuf<float> al_plane, al_row, al_out; DevBuf<uint4> al_moves; DevBuf<AlignPair> al_pairs; DevBuf<int4> al_tiles;
   long long al_cells = 0;
+  // the same set for llsm_gpu_batch_align_band, its own so that plane 6 stays what the last llsm_gpu_batch_align left: the
+  // band planes of the last successful call (plane 9; alb_cells floats, 0: no call yet), moves, hand-over rows, tables, out
+  DevBuf<float> alb_plane, alb_row, alb_out; DevBuf<uint4> alb_moves; DevBuf<AlignBandPair> alb_pairs; DevBuf<int4> alb_tiles;
+  long long alb_cells = 0;
   // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
   // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful
   // llsm_gpu_batch_select; sel_frames 0: no call yet), the back pointers (3 bits per state at bit 8 j, one word pair per

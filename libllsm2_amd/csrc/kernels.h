@@ -348,6 +348,25 @@ int launch_align_dist(LaunchCtx* P, const AlignDev& d, const int4* tiles, int n_
 // D2 - D3 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
 int launch_align_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
 
+// ---- alignment inside a diagonal band (align.cpp, align_kernels.hip; rules B1 - B4: llsm_gpu.h)
+// The centre column of row i of an na x nb pair, rule B1: the diagonal rounded half up.  Row i spans columns
+// max(0, c - band) ... min(nb - 1, c + band); entry q of its row of the band plane is column c - band + q.
+__host__ __device__ static inline int align_band_center(int i, int na, int nb) {
+  return na > 1 ? (int)((2ll * i * (nb - 1) + (na - 1)) / (2ll * (na - 1))) : 0;
+}
+// One pair: as AlignPair, with the band plane [na][2 band + 1] at float cell0 and `steps` entries of moves per strip of
+// 64 rows (the widest column window of a strip + 63 anti-diagonals)
+struct AlignBandPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
+struct AlignBandDev {
+  const float* code_a; const float* code_b; int dim, first, count; float step_cost, voicing_cost;
+  const AlignBandPair* pairs; int n_pairs;
+};
+// D1 in the band layout: tiles[t] = (pair, first row, first column -- which may be negative --, 0); every entry of the
+// band planes is written, +infinity where its column lies outside the matrix
+int launch_align_band_dist(LaunchCtx* P, const AlignBandDev& d, const int4* tiles, int n_tiles, float* plane);
+// B3 - B4 over the band planes, one wavefront per pair; out as launch_align_dtw
+int launch_align_band_dtw(LaunchCtx* P, const AlignBandDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
+
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame
 #define SELECT_SEG 1024                                // k_select_knn: bank frames per segment at the least ...
