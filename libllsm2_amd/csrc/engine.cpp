@@ -603,10 +603,7 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> coder_mel.release();
   b -> blob_widths.release(); b -> blob_tab.release(); b -> blob_dev.release();
   b -> f0_uss.release(); b -> f0_raw.release(); b -> f0_cmndf.release(); b -> f0_cand.release(); b -> f0_bp.release();
-  b -> al_plane.release(); b -> al_row.release(); b -> al_out.release(); b -> al_moves.release(); b -> al_pairs.release();
-  b -> al_tiles.release();
-  b -> alb_plane.release(); b -> alb_row.release(); b -> alb_out.release(); b -> alb_moves.release(); b -> alb_pairs.release();
-  b -> alb_tiles.release();
+  b -> al.release(); b -> alb.release();
   b -> sel_lists.release(); b -> sel_p7.release(); b -> sel_p8.release(); b -> sel_bp.release(); b -> sel_out.release();
   delete b;
 }
@@ -633,18 +630,18 @@ extern "C" int llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq) {
 extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap) {
   if(! b || which < 0 || which > 9) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
   DevBuf<float>& src = which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : which == 3 ? b -> colored :
-                      which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : which == 6 ? b -> al_plane :
-                      which == 7 ? b -> sel_p7 : which == 8 ? b -> sel_p8 : b -> alb_plane;
+                      which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : which == 6 ? b -> al.plane :
+                      which == 7 ? b -> sel_p7 : which == 8 ? b -> sel_p8 : b -> alb.plane;
   const long long n = which <= 1 ? (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1) :
                       which == 2 ? (long long)b -> lay.nchannel * b -> lay.total_samples :
                       which == 3 ? (long long)b -> lay.n_utt * b -> lay.nchannel * b -> lay.ntemplate_ext :
                       which == 4 ? (long long)b -> lay.total_frames * b -> f0_cm_cols :
-                      which == 5 ? (long long)b -> lay.total_frames * 24 : which == 6 ? b -> al_cells :
-                      which == 9 ? b -> alb_cells : b -> sel_frames * (which == 7 ? 16 : 64);
+                      which == 5 ? (long long)b -> lay.total_frames * 24 : which == 6 ? b -> al.cells :
+                      which == 9 ? b -> alb.cells : b -> sel_frames * (which == 7 ? 16 : 64);
   if(which == 4 && b -> f0_cm_cols == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_estimate_f0 with keep_cmndf has run on this batch"); return -1; }
   if(which == 5 && ! b -> f0_cand_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_track_f0 has run on this batch"); return -1; }
-  if(which == 6 && b -> al_cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align has run on this batch"); return -1; }
-  if(which == 9 && b -> alb_cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align_band has run on this batch"); return -1; }
+  if(which == 6 && b -> al.cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align has run on this batch"); return -1; }
+  if(which == 9 && b -> alb.cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align_band has run on this batch"); return -1; }
   if((which == 7 || which == 8) && b -> sel_frames == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_select has run on this batch"); return -1; }
   if(which == 2 && ! b -> ce_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has filtered the bands of this batch"); return -1; }
   if(which == 3 && ! b -> colored_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no synthesis has filtered the templates of this batch"); return -1; }

@@ -332,40 +332,28 @@ int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);
 // rules T2 - T5 over the candidate plane: f0[nframes]; bp: one word per frame of scratch
 int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0);
 
-// ---- alignment of utterance pairs (align.cpp, align_kernels.hip; rules D1 - D3: llsm_gpu.h)
-// One pair: rows [a0, a0 + na) of code_a against rows [b0, b0 + nb) of code_b (flat frame indices); its distance plane
-// starts at float cell0 of the plane, its moves at entry mv0 (ALIGN_STEPS(nb) entries of 16 bytes per strip of 64 rows),
-// its hand-over row at float row0, its positions at float pos0 of the out block
-struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, pad; long long mv0; };
-#define ALIGN_TILE 64                                  // k_align_dist: cells per side of a workgroup's tile
-#define ALIGN_STEPS(nb) ((long long)(nb) + 63)         // anti-diagonals of a strip of 64 rows
-struct AlignDev {
-  const float* code_a; const float* code_b; int dim, first, count; float step_cost, voicing_cost;
-  const AlignPair* pairs; int n_pairs;
-};
-// D1: tiles[t] = (pair, first row, first column, 0) of tile t; the planes of all pairs in one launch
-int launch_align_dist(LaunchCtx* P, const AlignDev& d, const int4* tiles, int n_tiles, float* plane);
-// D2 - D3 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
-int launch_align_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
-
-// ---- alignment inside a diagonal band (align.cpp, align_kernels.hip; rules B1 - B4: llsm_gpu.h)
+// ---- alignment of utterance pairs, whole matrix or inside a diagonal band (align.cpp, align_kernels.hip; rules D1 - D3
+// and B1 - B4: llsm_gpu.h)
 // The centre column of row i of an na x nb pair, rule B1: the diagonal rounded half up.  Row i spans columns
 // max(0, c - band) ... min(nb - 1, c + band); entry q of its row of the band plane is column c - band + q.
 __host__ __device__ static inline int align_band_center(int i, int na, int nb) {
   return na > 1 ? (int)((2ll * i * (nb - 1) + (na - 1)) / (2ll * (na - 1))) : 0;
 }
-// One pair: as AlignPair, with the band plane [na][2 band + 1] at float cell0 and `steps` entries of moves per strip of
-// 64 rows (the widest column window of a strip + 63 anti-diagonals)
-struct AlignBandPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
-struct AlignBandDev {
+// One pair: rows [a0, a0 + na) of code_a against rows [b0, b0 + nb) of code_b (flat frame indices); its plane -- [na][nb],
+// or [na][2 band + 1] of a banded call -- starts at float cell0 of the planes, its moves at entry mv0 (`steps` entries of
+// 16 bytes per strip of 64 rows: the anti-diagonals of the strip whose column window is the widest), its hand-over row
+// at float row0, its positions at float pos0 of the out block.  band is 0 and not read where the whole matrix is searched.
+struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
+#define ALIGN_TILE 64                                  // k_align_dist_t: cells per side of a workgroup's tile
+struct AlignDev {
   const float* code_a; const float* code_b; int dim, first, count; float step_cost, voicing_cost;
-  const AlignBandPair* pairs; int n_pairs;
+  const AlignPair* pairs; int n_pairs;
 };
-// D1 in the band layout: tiles[t] = (pair, first row, first column -- which may be negative --, 0); every entry of the
-// band planes is written, +infinity where its column lies outside the matrix
-int launch_align_band_dist(LaunchCtx* P, const AlignBandDev& d, const int4* tiles, int n_tiles, float* plane);
-// B3 - B4 over the band planes, one wavefront per pair; out as launch_align_dtw
-int launch_align_band_dtw(LaunchCtx* P, const AlignBandDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
+// D1 / B2: tiles[t] = (pair, first row, first column -- which may be negative in a band --, 0) of tile t; the planes of all
+// pairs in one launch, with `band` in the band layout, every entry written, +infinity where its column lies outside the matrix
+int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* tiles, int n_tiles, float* plane);
+// D2 - D3 / B3 - B4 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
+int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
 
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame

@@ -24,7 +24,7 @@
 // LDS of k_select_knn.  Both blocks are stored transposed, k major.  The bank block bk is [32][64 + 4]: a wavefront reads
 // rows r ... r + 3 at one k as one 16-byte read with every lane on the same address (a broadcast); the stride of 68 keeps
 // the reads aligned.  The target block tg is [32][64 + 1]: lane l reads tg[k][l], consecutive words; the staging pass,
-// whose lanes run along k for the sake of coalesced global reads, writes at the odd stride of 65 words (k_align_dist).
+// whose lanes run along k for the sake of coalesced global reads, writes at the odd stride of 65 words (k_align_dist_t).
 // Rows past the end of either side are read as the last row and never listed.
 #include <hip/hip_runtime.h>
 #include <algorithm>
