@@ -166,6 +166,9 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * call): pair after pair in list order, each [na][2 band + 1] row-major; entry q of row i is column c_i - band + q, and the
  * entries whose column lies outside [lo_i, hi_i] hold +infinity.  Refused until such a call has run; no other call writes
  * it, and that call does not write plane 6.
+ * which = 10 and 11: the state plane [total_frames][32] and the join plane [total_frames][256] (below
+ * llsm_gpu_batch_select_chain) of the last successful llsm_gpu_batch_select_chain with this batch as t.  Refused until
+ * such a call has run, and again after an accepted call that failed; no other call writes them.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -583,9 +586,8 @@ int  llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* hi);  /* h
  * utterance that has frames without an eligible bank frame.  A t without frames returns 0.
  * llsm_gpu_select_check is host only: 0, or -1 with the message llsm_gpu_batch_select would give for these options
  * (NULL: the defaults) on batches whose coder has these orders.
- * Known limits: the candidates are the eight nearest frames only -- the successors of the previous frame's candidates are
- * not added, so a continuation that is not itself among the eight nearest is not considered.  The search is exact and
- * exhaustive: there is no index, and no matrix-core form, because the squared-difference rule has two roundings per term. */
+ * Known limits: the candidates are the eight nearest frames only; llsm_gpu_batch_select_chain below adds the successors of
+ * the previous frame's candidates.  The search is exact and exhaustive: there is no index, and no matrix-core form, because the squared-difference rule has two roundings per term. */
 typedef struct {
   int     first, count;        /* columns [first, first + count) of LLSM_GPU_CODE are compared; defaults 3 and order_spec
                                   (count <= 0: order_spec) */
@@ -597,6 +599,56 @@ typedef struct {
 void llsm_gpu_select_default_options(llsm_gpu_select_options* dst);
 int  llsm_gpu_select_check(const llsm_gpu_select_options* opt, int order_spec, int order_bap);
 int  llsm_gpu_batch_select(llsm_gpu_batch* t, const llsm_gpu_batch* bank, const llsm_gpu_select_options* opt /* NULL: defaults */,
+       int* utt, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+
+/* ---- chained unit selection: llsm_gpu_batch_select with the continuations of the previous frame's states added to the
+ * candidates of every frame.  Where the bank holds several similar renditions the frame after the one just chosen is
+ * often ninth or tenth nearest: llsm_gpu_batch_select then has to jump to another utterance and pay a join, and the
+ * rendered note hops between recordings; here the continuation is a candidate because its predecessor was one.
+ * The contract is that of llsm_gpu_batch_select word for word: synchronous; utt, pos and cost have the same form and go
+ * into llsm_gpu_splice_map unchanged; t == bank is allowed and skip_own_utterance works as it does there; only
+ * LLSM_GPU_CODE of both batches is read and no array of either is written; a t without frames returns 0 with every cost 0;
+ * a refused call returns -1, launches nothing, allocates nothing and leaves the three arrays untouched.  The refusals are
+ * those listed above, by the same code; every message starts with "llsm_gpu_batch_select_chain:".  llsm_gpu_select_check,
+ * llsm_gpu_select_default_options and the options struct serve both calls.  The call uses scratch of its own on t only:
+ * planes 7 and 8 of llsm_gpu_batch_debug_plane stay what the last llsm_gpu_batch_select left, and that call does not touch
+ * planes 10 and 11.
+ *
+ * The rules.  T, B, f, d and c are those of S1, which applies unchanged; everything is float32, one rounding per
+ * operation, no contraction, every sum over k ascending.  A frame has up to 16 states: slots 0 ... 7 are near slots,
+ * slots 8 ... 15 follower slots.
+ *  C1. Near slots.  Slots 0 ... 7 of a frame are rule S2 unchanged: the same (c, f) in the same order; n_u as in S2.
+ *  C2. First frame of an utterance.  The states are its near slots; acc_0[j] = c_0[j].  There are no followers.
+ *  C3. Followers of frame i >= 1.  Take each present state a of frame i - 1, near and follower slots alike, with bank
+ *      frame fa.  Its successor is s_a = fa + 1 if that frame lies in fa's bank utterance; otherwise it has none.  The pool
+ *      holds the states a that have a successor and whose s_a is not the bank frame of any near slot of frame i.  The pool
+ *      is ordered by (acc_{i-1}[a], a) ascending, acc_{i-1} being the value rule C5 left: a float32 comparison, ties --
+ *      +infinity included -- to the smaller a.  The first min(8, |pool|) states fill slots 8, 9, ... of frame i in that
+ *      order; a follower slot holds bank frame s_a and cost c(T[g], B[s_a]).  Distinct states have distinct bank frames,
+ *      so a frame never holds one bank frame twice.  A follower is eligible under skip_own_utterance because its parent
+ *      was.
+ *  C4. Joins.  J(a, j) is rule S3 between every present state a of frame i - 1 and every present state j of frame i.  A
+ *      follower reached from its own parent is a natural continuation and costs 0; so does a near slot whose frame is s_a.
+ *  C5. Path.  S4 over up to 16 states: m starts at acc_{i-1}[a] + J(a, j) for the first present a and is replaced only
+ *      by a strictly smaller value, over a ascending; the back pointer is that a; acc_i[j] = m + c_i[j].  No
+ *      normalisation.  Absent slots are never predecessors or end states.  The path ends in the smallest state of least
+ *      acc on the last frame; cost[u] is that acc.
+ *  C6. utt, pos and cost are as in S5.
+ * A target utterance's result depends on its own rows, the bank and the options only.
+ * It follows that slots 0 ... 7 of plane 10 and the a, j < 8 block of plane 11 are planes 7 and 8 of
+ * llsm_gpu_batch_select on the same inputs bit for bit; that cost[u] here is never above cost[u] there as float32 values
+ * (the near states are a subset of the states with the same costs, float32 addition is monotone, so by induction every
+ * near state's acc is no larger here, and a minimum over more states is no larger either); and that on a bank whose
+ * utterances all have one frame nothing has a successor, slots 8 ... 15 are absent everywhere, and utt, pos and cost are
+ * the bits of llsm_gpu_batch_select.
+ *
+ * Planes of llsm_gpu_batch_debug_plane, both always kept: plane 10, [t.total_frames][32]: c[0..15], then the bank frame
+ * indices of slots 0 ... 15 as floats; absent slots hold 1e30f and -1.  Plane 11, [t.total_frames][256]: J at entry
+ * 16 a + j; rows of first frames and entries of absent slots are 0.
+ * Known limits: one wavefront per target utterance walks its frames in order, so few long utterances leave the device idle.
+ * The followers are the eight pool states of lowest accumulated cost: a beam, not an exhaustive search over
+ * continuations.  Plane 11 takes 1 KiB per target frame. */
+int  llsm_gpu_batch_select_chain(llsm_gpu_batch* t, const llsm_gpu_batch* bank, const llsm_gpu_select_options* opt /* NULL: defaults */,
        int* utt, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
 
 /* ---- frame coder of a device-resident layer-1 batch: every frame <-> the vector [voicing, f0, Rd, order_spec mel-spectrum

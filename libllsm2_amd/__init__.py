@@ -158,7 +158,7 @@ llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
 llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f0
 llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
 llsm_gpu_batch_align_band llsm_gpu_align_band_min llsm_gpu_align_band_rows
-llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select
+llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select llsm_gpu_batch_select_chain
 """.split()
 
 _lib = None
@@ -253,6 +253,11 @@ def load():
         L.llsm_gpu_select_default_options.restype = None
         L.llsm_gpu_select_check.argtypes = [C.POINTER(SelectOptions), C.c_int, C.c_int]
         L.llsm_gpu_batch_select.argtypes = [vp, vp, C.POINTER(SelectOptions), P_int, P_fp, P_fp]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the chained selection)
+        L.llsm_gpu_batch_select_chain.argtypes = [vp, vp, C.POINTER(SelectOptions), P_int, P_fp, P_fp]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -705,7 +710,9 @@ class Batch:
         track_f0, total_frames x 24; 6: the distance planes of the last align with this batch as a, pair after pair,
         each na x nb; 7 and 8: the candidate rows, total_frames x 16, and the join costs, total_frames x 64, of the last select
         with this batch as the target; 9: the band planes of the last align_band with this batch as a, pair after pair,
-        each na x (2 band + 1), +inf outside the rows' ranges)"""
+        each na x (2 band + 1), +inf outside the rows' ranges; 10 and 11: the state rows, total_frames x 32 (c of slots
+        0 ... 15, then their bank frames; absent slots 1e30 and -1), and the join costs, total_frames x 256 (entry 16 a + j),
+        of the last select_chain with this batch as the target)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -774,6 +781,18 @@ class Batch:
         utt = np.zeros(n, np.int32); pos = np.zeros(n, np.float32); cost = np.zeros(self.layout.n_utt, np.float32)
         _check(self.L.llsm_gpu_batch_select(self.h, bank.h, C.byref(o), utt.ctypes.data_as(P_int), pos.ctypes.data_as(P_fp),
                                             cost.ctypes.data_as(P_fp)), "select")
+        return utt, pos, cost
+
+    def select_chain(self, bank, opt=None, **options):
+        """select with the continuations of the previous frame's states added to every frame's candidates
+        (llsm_gpu_batch_select_chain): where the bank holds similar renditions the path stays in one recording instead of
+        paying joins.  Arguments and results as select; planes 10 and 11 of debug_plane instead of 7 and 8"""
+        assert opt is None or not options
+        o = opt if opt is not None else make_select_options(**options)
+        n = int(self.frm_off[-1])
+        utt = np.zeros(n, np.int32); pos = np.zeros(n, np.float32); cost = np.zeros(self.layout.n_utt, np.float32)
+        _check(self.L.llsm_gpu_batch_select_chain(self.h, bank.h, C.byref(o), utt.ctypes.data_as(P_int),
+                                                  pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "select_chain")
         return utt, pos, cost
 
     # ---- export as chunk blobs (llsm_gpu.h): the wire format of csrc/wire.cpp, packed on the device

@@ -204,6 +204,12 @@ struct llsm_gpu_batch {
   // frame) and the device block [utt | pos | cost] -- all grow-only
   DevBuf<float> sel_lists, sel_p7, sel_p8; DevBuf<uint2> sel_bp; DevBuf<int> sel_out;
   long long sel_frames = 0;
+  // chained unit selection (llsm_gpu_batch_select_chain), a set of its own so that planes 7 and 8 stay what the last
+  // llsm_gpu_batch_select left: the per-segment lists, the near lists [.][16] in the layout of plane 7, planes 10 and 11
+  // ([selc_frames][32] and [selc_frames][256] of the last successful call; selc_frames 0: no call yet), the back pointers
+  // (4 bits per state at bit 4 j, one word pair per frame) and the device block [utt | pos | cost] -- all grow-only
+  DevBuf<float> selc_lists, selc_near, selc_p10, selc_p11; DevBuf<uint2> selc_bp; DevBuf<int> selc_out;
+  long long selc_frames = 0;
 };
 
 

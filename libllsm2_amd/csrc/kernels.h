@@ -355,7 +355,7 @@ int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* ti
 // D2 - D3 / B3 - B4 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
 int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
 
-// ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5: llsm_gpu.h)
+// ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5 and C1 - C6: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame
 #define SELECT_SEG 1024                                // k_select_knn: bank frames per segment at the least ...
 #define SELECT_MAX_SEG 64                              // ... and segments at the most (one lane each in k_select_merge)
@@ -382,5 +382,9 @@ int launch_select_merge(LaunchCtx* P, const SelectDev& d, const float* lists, fl
 int launch_select_join(LaunchCtx* P, const SelectDev& d, const float* p7, float* p8);
 // S4 - S5, one wavefront per utterance of t: out = [utt of every frame | pos of every frame (float bits) | cost per utterance (float bits)]
 int launch_select_path(LaunchCtx* P, const SelectDev& d, const float* p7, const float* p8, uint2* bp, int* out);
+// C2 - C6 (llsm_gpu_batch_select_chain), one wavefront per utterance of t: near [nt][16] in the layout of plane 7 -> plane 10
+// [nt][32], plane 11 [nt][256], one word of back pointers per frame, and out as launch_select_path gives it
+#define SELECT_STATES 16                               // states per frame: SELECT_K near slots and up to SELECT_K followers
+int launch_select_chain(LaunchCtx* P, const SelectDev& d, const float* near, float* p10, float* p11, uint2* bp, int* out);
 
 #endif

@@ -1,5 +1,5 @@
-// select_kernels.hip -- unit selection, llsm_gpu_batch_select (rules S1 - S5: llsm_gpu.h; host side:
-// select.cpp).  Four kernels:
+// select_kernels.hip -- unit selection, llsm_gpu_batch_select (rules S1 - S5: llsm_gpu.h) and
+// llsm_gpu_batch_select_chain (rules C1 - C6: llsm_gpu.h); host side: select.cpp.  Five kernels:
 //
 //   k_select_knn    S1 - S2, the hot path: nt x nb x count x 3 operations, the nt x nb distances never leave the registers.
 //                   A workgroup of 256 threads takes 64 target frames and one segment of the bank (select_seg_len(nb)
@@ -20,6 +20,8 @@
 //                   slots a, B[fb] of the eight slots j) are staged once in the LDS, 64 columns at a time, and every lane
 //                   walks k ascending over its two.
 //   k_select_path   S4 - S5: one wavefront per target utterance, lane 8 j + a (the layout of k_f0_viterbi).
+//   k_select_chain  C2 - C6: one wavefront per target utterance; followers, joins and the path step of a frame in one
+//                   sequential loop, because the followers of a frame depend on the accumulated costs of the frame before.
 //
 // LDS of k_select_knn.  Both blocks are stored transposed, k major.  The bank block bk is [32][64 + 4]: a wavefront reads
 // rows r ... r + 3 at one k as one 16-byte read with every lane on the same address (a broadcast); the stride of 68 keeps
@@ -345,6 +347,277 @@ __global__ __launch_bounds__(WAVE) void k_select_path(SelectDev d, const float* 
   }
 }
 
+// ---------------------------------------------------------------- C2 - C6: followers, joins and the path, one loop
+// A frame has up to 16 states: slots 0 ... 7 the near list of k_select_knn / k_select_merge, slots 8 ... 15 the followers.
+// Lane s < 16 owns state s between frames: its bank frame (-1: absent), the end of that frame's bank utterance, and acc.
+// Within a frame lane l owns the pairs (a, j) = (4 q + (l >> 4), l & 15), q = 0 ... 3: entry 16 a + j of plane 11 is word
+// 64 q + l of the row, and the minimum over a is four values in the lane and two exchanges across the lanes l ^ 16, l ^ 32.
+//
+// Per frame i >= 1:
+//   1. the rows loaded one frame ahead go into the LDS: rows 0 ... 15 B[s_a] of the states a of frame i - 1 (B[fa] where
+//      there is no successor: rule S3), rows 16 ... 23 the near rows of frame i, row 24 T[g]; 64 columns at a time, and
+//      column 64 of a row, the padding of the odd stride, holds whether the row is voiced
+//   2. C3: pool membership (a successor, and not among the eight near frames), the rank of every pool state under (acc, a)
+//      by 16 scalar lane reads, and the parent of every follower slot by 8 ballots; the new state set is then fixed
+//   3. the loads of frame i + 1 are issued: its S rows follow from the state set alone, not from the path step below
+//   4. k ascending, eight columns at a time, each lane: its four join sums (row a against row j: a near row, or the S row of j's parent, which is
+//      the follower's own row) and one target sum (T[g] against S row l & 15: the cost of the follower it may become)
+//   5. C4 / C5, the rows of planes 10 and 11, and the back pointers: four ballots, bit 4 j + b of the word = bit b of arg_j
+// The near lists are loaded three frames ahead, the bank utterances of their frames two and the ends of those one, each a
+// frame after the value it depends on: no load of a list stands in the chain.
+#define SC_KC 64                                   // columns per LDS stage
+#define SC_S (SC_KC + 1)                           // row stride; column SC_KC: voiced
+#define SC_NS SELECT_STATES
+#define SC_ROW_N SC_NS                             // first near row
+#define SC_ROW_T (SC_NS + SELECT_K)                // the target row
+#define SC_ROW_SPARE (SC_ROW_T + 1)                // never read
+#define SC_ABSENT 99                               // the argument of a predecessor that is absent: above every state
+
+struct ScRows { float s[SC_NS], n[SELECT_K], t, vs, vn, vt; };
+
+// columns [k0, k0 + 64) of the rows of frame g: lane r < 16 holds srow of S row r (-1: none), lane r < 8 near frame nf.
+// Every load is made: a row that is absent reads row 0 and a lane past the last column the last column -- no state
+// that is present reads either -- so that the 28 loads are one straight run
+DEV void sc_load(ScRows& r, const SelectDev& d, int srow, int nf, int g, int k0, int lane) {
+  const int col = d.first + k0 + min(lane, min(SC_KC, d.count - k0) - 1);
+  const float* B = d.code_b + col;
+  const unsigned dim = (unsigned)d.dim;
+#pragma unroll
+  for(int q = 0; q < SC_NS; q ++)                                   // (a vector register each: 24 scalar row bases spill)
+    r.s[q] = B[(size_t)(unsigned)max(__shfl(srow, q, WAVE), 0) * dim];
+#pragma unroll
+  for(int q = 0; q < SELECT_K; q ++)
+    r.n[q] = B[(size_t)(unsigned)max(__shfl(nf, q, WAVE), 0) * dim];
+  r.t = d.code_t[(size_t)g * dim + col];
+  r.vs = d.code_b[(size_t)(unsigned)max(srow, 0) * dim];
+  r.vn = d.code_b[(size_t)(unsigned)max(nf, 0) * dim];
+  r.vt = d.code_t[(size_t)g * dim];
+}
+
+// The voicing words are stored by every lane, the lanes that hold none into a spare row: under a branch the loaded value
+// would stay pending on the path around it, and the wait for it -- for every load, the rows of the next frame among them
+// -- would land at the head of the column loop
+DEV void sc_store(float (*rows)[SC_S], const ScRows& r, int lane) {
+#pragma unroll
+  for(int q = 0; q < SC_NS; q ++) rows[q][lane] = r.s[q];
+#pragma unroll
+  for(int q = 0; q < SELECT_K; q ++) rows[SC_ROW_N + q][lane] = r.n[q];
+  rows[SC_ROW_T][lane] = r.t;
+  float* spare = & rows[SC_ROW_SPARE][lane];
+  *(lane < SC_NS ? & rows[lane][SC_KC] : spare) = r.vs > 0.5f ? 1.0f : 0.0f;
+  *(lane < SELECT_K ? & rows[SC_ROW_N + lane][SC_KC] : spare) = r.vn > 0.5f ? 1.0f : 0.0f;
+  *(lane == 0 ? & rows[SC_ROW_T][SC_KC] : spare) = r.vt > 0.5f ? 1.0f : 0.0f;
+}
+
+// bit i of the low 16 bits -> bit 4 i
+DEV unsigned long long sc_spread(unsigned long long x) {
+  x &= 0xFFFFull;
+  x = (x | (x << 24)) & 0x000000FF000000FFull;
+  x = (x | (x << 12)) & 0x000F000F000F000Full;
+  x = (x | (x << 6)) & 0x0303030303030303ull;
+  x = (x | (x << 3)) & 0x1111111111111111ull;
+  return x;
+}
+
+DEV float sc_readlane_f(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+
+__global__ __launch_bounds__(WAVE) void k_select_chain(SelectDev d, const float* __restrict__ nearg, float* __restrict__ p10g,
+  float* __restrict__ p11g, uint2* __restrict__ bp, int* __restrict__ out) {
+  __shared__ float rows[SC_ROW_SPARE + 1][SC_S];
+  const int u = blockIdx.x, lane = threadIdx.x, jj = lane & (SC_NS - 1), ah = lane >> 4;
+  const int n = d.t_nfrm[u], g0 = d.t_frm_off[u];
+  int* cost = out + 2 * (size_t)d.nt;
+  if(n <= 0) { if(lane == 0) cost[u] = __float_as_int(0.0f); return; }
+  const float* near = nearg + (size_t)g0 * 16;
+  float* p10 = p10g + (size_t)g0 * 32; float* p11 = p11g + (size_t)g0 * 256;
+  uint2* bpu = bp + g0;
+  const int* bu = d.b_frm_utt;
+  // the near list of frame i (clamped to the utterance) in lanes 0 ... 7; the other lanes hold an absent slot
+  auto near_load = [&](int i, float& c, int& f) {
+    const size_t at = (size_t)min(i, n - 1) * 16;
+    c = lane < SELECT_K ? near[at + lane] : SEL_CAP;
+    f = lane < SELECT_K ? (int)near[at + 8 + lane] : -1;
+  };
+  // frames i ... i + 3: f the bank frames, u their bank utterances, e the ends of those; each is asked for one frame after
+  // the value it depends on, so that no load of the lists stands in the chain
+  float c_i, c_1, c_2, c_3; int f_i, f_1, f_2, f_3, e_i, e_1, u_1, u_2;
+  near_load(0, c_i, f_i); near_load(1, c_1, f_1); near_load(2, c_2, f_2); near_load(3, c_3, f_3);
+  { const int ub = bu[max(f_i, 0)]; e_i = d.b_frm_off[ub] + d.b_nfrm[ub]; }
+  { const int ub = bu[max(f_1, 0)]; e_1 = d.b_frm_off[ub] + d.b_nfrm[ub]; }
+  u_2 = bu[max(f_2, 0)];
+  // C2: the states of frame 0 are its near slots
+  int sf = f_i, se = e_i;
+  float sacc = sf >= 0 ? c_i : INFINITY;
+  int srow = sf < 0 ? -1 : sf + 1 < se ? sf + 1 : sf;
+  if(lane < SC_NS) { p10[lane] = c_i; p10[SC_NS + lane] = (float)sf; }
+#pragma unroll
+  for(int q = 0; q < 4; q ++) p11[64 * q + lane] = 0.0f;
+  if(lane == 0) bpu[0] = make_uint2(0, 0);
+  ScRows pre;                                                       // (the frame after the last: the last again, unused)
+  sc_load(pre, d, srow, f_1, g0 + min(1, n - 1), 0, lane);
+
+  for(int i = 1; i < n; i ++) {
+    const int g = g0 + i;
+    c_i = c_1; f_i = f_1; e_i = e_1;
+    c_1 = c_2; f_1 = f_2; u_1 = u_2;
+    c_2 = c_3; f_2 = f_3;
+    near_load(i + 3, c_3, f_3);
+    u_2 = bu[max(f_2, 0)];
+    e_1 = d.b_frm_off[u_1] + d.b_nfrm[u_1];
+    __syncthreads();                                                // the rows of the frame before have been read
+    sc_store(rows, pre, lane);
+    // ---- C3
+    const bool has = sf >= 0 && sf + 1 < se;
+    const int succ = sf + 1;
+    bool isnear = false;
+#pragma unroll
+    for(int k = 0; k < SELECT_K; k ++) isnear |= __builtin_amdgcn_readlane(f_i, k) == succ;
+    const bool inpool = has && ! isnear;
+    const unsigned pm = (unsigned)__ballot(inpool);
+    // the rank of a pool state: the pool states before it under (acc, a).  The comparisons are gathered as bits, one per
+    // state b, and the parents as one byte per follower slot: predicates on the lane number alone, one per b and per
+    // slot, would be kept as lane masks across the frame loop and spill scalar registers
+    unsigned lt = 0, eq = 0;
+#pragma unroll
+    for(int b = 0; b < SC_NS; b ++) {
+      const float ab = sc_readlane_f(sacc, b);
+      lt |= (unsigned)(ab < sacc) << b; eq |= (unsigned)(ab == sacc) << b;
+    }
+    const int rank = __popc(pm & (lt | (eq & ((1u << (lane & 31)) - 1u))));
+    const bool taken = inpool && rank < SELECT_K;
+    unsigned long long pw = 0;                                      // byte r: 1 + the parent of follower slot r, 0: none
+#pragma unroll
+    for(int r = 0; r < SELECT_K; r ++)
+      pw |= (unsigned long long)__ffsll((long long)__ballot(taken && rank == r)) << (8 * r);
+    const int par = (lane >> 3) == 1 ? (int)((pw >> (8 * (lane & 7))) & 0xFF) - 1 : -1;   // lane 8 + r: the parent of slot r
+    const int src = max(par, 0);
+    const int f_par = __shfl(succ, src, WAVE), e_par = __shfl(se, src, WAVE);
+    const int nf = lane < SELECT_K ? f_i : par >= 0 ? f_par : -1;  // the states of frame i (lanes >= 16: absent)
+    const int ne = lane < SELECT_K ? e_i : e_par;
+    const int srow_1 = nf < 0 ? -1 : nf + 1 < ne ? nf + 1 : nf;
+    // ---- the rows of frame i + 1, one frame ahead of the chain
+    ScRows nxt;
+    sc_load(nxt, d, srow_1, f_1, g0 + min(i + 1, n - 1), 0, lane);
+    // ---- the sums, k ascending
+    const int par_j = __shfl(par, jj, WAVE);
+    const int frow = jj < SELECT_K ? SC_ROW_N + jj : max(par_j, 0);
+    float accJ[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accT = 0.0f;
+    for(int k0 = 0; k0 < d.count; k0 += SC_KC) {
+      if(k0 > 0) {                                                  // further columns: loaded here
+        ScRows x;
+        sc_load(x, d, srow, f_i, g, k0, lane);
+        __syncthreads();
+        sc_store(rows, x, lane);
+      }
+      __syncthreads();
+      const int kn = min(SC_KC, d.count - k0);
+      // (eight columns at a time where there are eight: one wavefront per SIMD has nothing else to cover the LDS reads of
+      // a column with, so the 56 reads of eight columns are issued together, ahead of the sums, which stay k ascending)
+      int k = 0;
+      for(; k + 8 <= kn; k += 8) {
+        float y[8], x[4][8], tg[8], sj[8];
+#pragma unroll
+        for(int e = 0; e < 8; e ++) {
+          y[e] = rows[frow][k + e]; tg[e] = rows[SC_ROW_T][k + e]; sj[e] = rows[jj][k + e];
+#pragma unroll
+          for(int q = 0; q < 4; q ++) x[q][e] = rows[4 * q + ah][k + e];
+        }
+#pragma unroll
+        for(int e = 0; e < 8; e ++) {
+#pragma unroll
+          for(int q = 0; q < 4; q ++) {
+            const float t = __fsub_rn(x[q][e], y[e]);
+            accJ[q] = __fadd_rn(accJ[q], __fmul_rn(t, t));
+          }
+          const float tt = __fsub_rn(tg[e], sj[e]);
+          accT = __fadd_rn(accT, __fmul_rn(tt, tt));
+        }
+      }
+      for(; k < kn; k ++) {
+        const float y = rows[frow][k];
+#pragma unroll
+        for(int q = 0; q < 4; q ++) {
+          const float t = __fsub_rn(rows[4 * q + ah][k], y);
+          accJ[q] = __fadd_rn(accJ[q], __fmul_rn(t, t));
+        }
+        const float tt = __fsub_rn(rows[SC_ROW_T][k], rows[jj][k]);
+        accT = __fadd_rn(accT, __fmul_rn(tt, tt));
+      }
+    }
+    // ---- the costs of the followers: lane a < 16 holds c(T[g], B[s_a]), slot 8 + r takes its parent's
+    if(rows[SC_ROW_T][SC_KC] != rows[jj][SC_KC]) accT = __fadd_rn(accT, d.voicing_cost);
+    const float ct = accT < SEL_CAP ? accT : SEL_CAP;
+    const float c_par = __shfl(ct, src, WAVE);
+    const float nc = lane < SELECT_K ? c_i : par >= 0 ? c_par : SEL_CAP;
+    if(lane < SC_NS) { p10[(size_t)i * 32 + lane] = nc; p10[(size_t)i * 32 + SC_NS + lane] = (float)nf; }
+    // ---- C4 and the minimum of C5 over a ascending
+    const int fj = __shfl(nf, jj, WAVE);
+    const float vj = rows[frow][SC_KC];
+    float m = INFINITY; int arg = SC_ABSENT;
+#pragma unroll
+    for(int q = 0; q < 4; q ++) {
+      const int a = 4 * q + ah;
+      const int fa = __shfl(sf, a, WAVE), ea = __shfl(se, a, WAVE);
+      const float acc_a = __shfl(sacc, a, WAVE);
+      const bool absent = fa < 0 || fj < 0;
+      const bool natural = fj == fa + 1 && fj < ea;
+      float J = 0.0f;
+      if(! absent && ! natural) {
+        float dd = accJ[q];
+        if(rows[a][SC_KC] != vj) dd = __fadd_rn(dd, d.voicing_cost);
+        const float c = dd < SEL_CAP ? dd : SEL_CAP;
+        J = __fadd_rn(d.join_cost, __fmul_rn(d.join_weight, c));
+      }
+      p11[(size_t)i * 256 + 64 * q + lane] = J;
+      const float v = fa >= 0 ? __fadd_rn(acc_a, J) : INFINITY;
+      const int va = fa >= 0 ? a : SC_ABSENT;
+      if(v < m || (v == m && va < arg)) { m = v; arg = va; }
+    }
+#pragma unroll
+    for(int o = 16; o <= 32; o <<= 1) {
+      const float ov = __shfl_xor(m, o, WAVE); const int oa = __shfl_xor(arg, o, WAVE);
+      if(ov < m || (ov == m && oa < arg)) { m = ov; arg = oa; }
+    }
+    const bool live = lane < SC_NS && nf >= 0;
+    const float nacc = live ? __fadd_rn(m, nc) : INFINITY;
+    const unsigned long long word = sc_spread(__ballot(live && (arg & 1))) | (sc_spread(__ballot(live && (arg & 2))) << 1) |
+                                    (sc_spread(__ballot(live && (arg & 4))) << 2) | (sc_spread(__ballot(live && (arg & 8))) << 3);
+    if(lane == 0) bpu[i] = make_uint2((unsigned)word, (unsigned)(word >> 32));
+    // ---- frame i is done
+    sf = nf; se = ne; sacc = nacc; srow = srow_1; pre = nxt;
+  }
+
+  // the path ends in the smallest state of least acc on the last frame
+  const bool live = lane < SC_NS && sf >= 0;
+  const float mine = live ? sacc : INFINITY;
+  float m = mine;
+#pragma unroll
+  for(int o = 8; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, WAVE));
+  m = sc_readlane_f(m, 0);
+  int s = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(live && mine == m)) - 1);
+  if(lane == 0) cost[u] = __float_as_int(m);
+  __threadfence();                                                  // plane 10 and the back pointers were written by other lanes
+  __syncthreads();
+  for(int base = (n - 1) & ~(WAVE - 1); base >= 0; base -= WAVE) {
+    const int cnt = min(WAVE, n - base);
+    uint2 w = make_uint2(0, 0);
+    if(lane < cnt) w = bpu[base + lane];
+    int st = 0;
+    for(int k = cnt - 1; k >= 0; k --) {
+      if(lane == k) st = s;
+      const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)w.x, k), hi = (unsigned)__builtin_amdgcn_readlane((int)w.y, k);
+      s = ((s < 8 ? lo : hi) >> (4 * (s & 7))) & 15;                // the state of frame base + k - 1
+    }
+    if(lane < cnt) {                                                // C6
+      const int g = g0 + base + lane;
+      const int f = min(max((int)p10[(size_t)(base + lane) * 32 + SC_NS + st], 0), d.nb - 1);   // (a present state: in the bank)
+      const int ub = bu[f];
+      out[g] = ub;
+      out[(size_t)d.nt + g] = __float_as_int((float)(f - d.b_frm_off[ub]));
+    }
+  }
+}
+
 // ---------------------------------------------------------------- launchers
 int launch_select_knn(LaunchCtx* P, const SelectDev& d, float* lists) {
   if(d.nt == 0) return 0;
@@ -367,5 +640,11 @@ int launch_select_join(LaunchCtx* P, const SelectDev& d, const float* p7, float*
 int launch_select_path(LaunchCtx* P, const SelectDev& d, const float* p7, const float* p8, uint2* bp, int* out) {
   if(d.n_utt == 0) return 0;
   LAUNCH("k_select_path", k_select_path, dim3(d.n_utt), dim3(WAVE), 0, d, p7, p8, bp, out);
+  return 0;
+}
+
+int launch_select_chain(LaunchCtx* P, const SelectDev& d, const float* near, float* p10, float* p11, uint2* bp, int* out) {
+  if(d.n_utt == 0) return 0;
+  LAUNCH("k_select_chain", k_select_chain, dim3(d.n_utt), dim3(WAVE), 0, d, near, p10, p11, bp, out);
   return 0;
 }

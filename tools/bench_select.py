@@ -12,8 +12,12 @@ call of each kernel from HIP events (llsm_gpu_get_profile: min / median / max of
 k_select_knn as operations per second from 3 x count x T x N and as a fraction of the fp32 vector peak; and the host round
 trip with its scaling stated.
 
+With --chain every bank also gets a "chain" entry: llsm_gpu_batch_select_chain on the same batches with the same options,
+timed the same way in the same process (wall and per-kernel spreads; k_select_chain stands where k_select_join and
+k_select_path stand for select), whether every cost is at most select's, and the joins both results pay.
+
     python tools/bench_select.py [--utts 1024] [--frames 200] [--bank-utts 64] [--big-bank-utts 256] [--steps 10]
-                                 [--warmup 2] [--cpu-utts 2] [--out FILE]
+                                 [--warmup 2] [--cpu-utts 2] [--chain] [--out FILE]
 """
 import argparse
 import json
@@ -30,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import libllsm2_amd as llsm  # noqa: E402
 import align_reference as aref  # noqa: E402
 import select_reference as sref  # noqa: E402
+import select_chain_reference as cref  # noqa: E402
 
 FS = 44100.0
 OSP, OBAP = 64, 5
@@ -82,6 +87,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cpu-utts", type=int, default=2)
+    ap.add_argument("--chain", action="store_true", help="time llsm_gpu_batch_select_chain at the same shapes as well")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n, F = a.utts, a.frames
@@ -106,6 +112,14 @@ def main():
             row["knn_fraction_of_fp32_vector_peak"] = ops / PEAK_FP32_VECTOR
             row["knn_note"] = ("3 x count x T x N operations; the peak of %.1f TFLOP/s counts a fused multiply-add as two, and the "
                                "rule forbids the fusion, so one half of it is the ceiling of this kernel" % (PEAK_FP32_VECTOR / 1e12))
+        if a.chain:
+            rc, cwalls, ckern = time_call(ctx, lambda: t.select_chain(bank, join_cost=1.0), steps, a.warmup if nb == a.bank_utts else 1)
+            row["chain"] = dict(wall_ms=spread(cwalls), kernels_ms={k: spread(v) for k, v in ckern.items()},
+                                kernels_ms_sum=float(sum(np.median(v) for v in ckern.values())),
+                                target_frames_per_s=T / (float(np.median(cwalls)) * 1e-3),
+                                every_cost_at_most_selects=bool(np.all(rc[2] <= r[2])),
+                                joins_select=int(cref.joins_of(r[0], r[1], t.frm_off, bank.frm_off).sum()),
+                                joins_chain=int(cref.joins_of(rc[0], rc[1], t.frm_off, bank.frm_off).sum()))
         out["banks"].append(row)
         if nb == a.bank_utts and a.cpu_utts > 0:           # the host round trip the call replaces, on this bank
             m = min(a.cpu_utts, n)
