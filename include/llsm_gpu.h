@@ -169,6 +169,9 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * which = 10 and 11: the state plane [total_frames][32] and the join plane [total_frames][256] (below
  * llsm_gpu_batch_select_chain) of the last successful llsm_gpu_batch_select_chain with this batch as t.  Refused until
  * such a call has run, and again after an accepted call that failed; no other call writes them.
+ * which = 12: the distance planes of the last successful llsm_gpu_batch_align_slope with this batch as a (rule L2 below that
+ * call, which is D1): pair after pair in list order, each [na][nb] row-major, the whole matrix.  Refused until such a call
+ * has run; no other call writes it, and that call writes neither plane 6 nor plane 9.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -485,7 +488,7 @@ int  llsm_gpu_batch_track_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt, 
  * (NULL: the defaults) on batches whose coder has these orders.
  * Known limits: the whole matrix of a pair is searched, so a call holds pairs of 2^28 cells in all -- long material goes
  * through llsm_gpu_batch_align_band below, which searches a band around the diagonal; there are no slope constraints beyond
- * monotonicity. */
+ * monotonicity -- a path may stay on one frame or skip many: llsm_gpu_batch_align_slope below bounds the local slope. */
 typedef struct {
   int     first, count;   /* columns [first, first + count) of LLSM_GPU_CODE are compared; defaults 3 and order_spec
                              (count <= 0: order_spec): the mel-spectrum points */
@@ -530,12 +533,61 @@ int  llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pair
  * connected for its pair (the message names the pair and llsm_gpu_align_band_min of it), and a sum of na x (2 band + 1)
  * above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
  * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else, so it has to be as
- * wide as the renditions drift apart; there are no slope constraints beyond monotonicity. */
+ * wide as the renditions drift apart; there are no slope constraints beyond monotonicity (llsm_gpu_batch_align_slope below
+ * has them, over the whole matrix). */
 int  llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const int* band /* n_pairs half-widths, frames */, const llsm_gpu_align_options* opt /* NULL: defaults */,
        FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
 int  llsm_gpu_align_band_min(int na, int nb);                              /* host only */
 int  llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* hi);  /* host only; na entries each */
+
+/* ---- slope-constrained alignment: llsm_gpu_batch_align with local slopes in [1/2, 2].  Under rules D2 and B3 a path may
+ * stay on one frame of B for any number of frames of A or jump many frames of B inside one row of A -- step_cost only makes
+ * that dearer -- and in a morph a stall is a frozen frame, a jump a skipped stretch.  Here every move advances both
+ * utterances, by one frame each or by two frames of one and one of the other (Sakoe and Chiba's symmetric step pattern with
+ * P = 1).  The contract is that of llsm_gpu_batch_align -- the same pos and cost, the same options and llsm_gpu_align_check,
+ * synchronous, a refused call returns -1 with a message that starts with "llsm_gpu_batch_align_slope:", launches and allocates
+ * nothing and leaves pos and cost untouched; LLSM_GPU_CODE of both batches is read and no array of either written; a == b is
+ * allowed -- with scratch of its own on a (the distance planes, llsm_gpu_batch_debug_plane(a, 12, ...), always kept): planes 6
+ * and 9 and the scratch of the other two calls stay as they were.  A pair's result depends on its own two utterances and the
+ * options only.
+ *
+ * The rules, per pair; float32, one rounding per operation, no contraction.
+ *  L1. The region.  A pair is admissible when nb - 1 <= 2 (na - 1) and na - 1 <= 2 (nb - 1): 1 x 1 is, 1 x 2 is not.  Row i
+ *      holds the columns lo_i = max(ceil(i / 2), (nb - 1) - 2 (na - 1 - i)) ... hi_i = min(2 i, (nb - 1) - ceil((na - 1 - i)
+ *      / 2)), integers taken in 64-bit: the cells from which (0, 0) is reached backwards and (na - 1, nb - 1) forwards under
+ *      the moves of L3.  lo_i > hi_i is possible (3 x 2: row 1 is (1, 0)): no path stops on such a row, it is only passed
+ *      through.  Every cell of the region other than (0, 0) has at least one predecessor of L3 inside the region.
+ *      llsm_gpu_align_slope_rows fills lo and hi (na entries each; either may be NULL, both NULL only asks whether the pair
+ *      is admissible) and returns 0, or -1 with a message that names na, nb and the bound that fails for na < 1, nb < 1 or a
+ *      pair that is not admissible.  Host only, needs no device.
+ *  L2. D[i][j] is rule D1 unchanged, for the whole matrix.
+ *  L3. acc[0][0] = D[0][0].  For every other cell (i, j) of the region the candidates are, in this order, each only if its
+ *      predecessor cell lies in the region (integer comparisons with lo and hi of that row, never of values):
+ *        move 0: acc[i-1][j-1];
+ *        move 1: (acc[i-2][j-1] + D[i-1][j]) + step_cost;
+ *        move 2: (acc[i-1][j-2] + D[i][j-1]) + step_cost.
+ *      m starts from the first candidate that exists, and a later one replaces it only if it is strictly smaller;
+ *      acc[i][j] = m + D[i][j].  The cell between the two ends of move 1 or 2 need not lie in the region; it is always
+ *      inside the matrix.  The additions are in the order of a diagonal move of D2 followed by an upper or a left one, so
+ *      every such path is a path of D2 with the same sequence of operations.
+ *  L4. The path runs from (na - 1, nb - 1) back along the moves to (0, 0) (0: (i - 1, j - 1); 1: (i - 1, j), then
+ *      (i - 2, j - 1); 2: (i, j - 1), then (i - 1, j - 2)): at most min(na, nb) - 1 moves, whatever the bits of
+ *      LLSM_GPU_CODE.  pos[i] = (float)(lo + hi) * 0.5f over the least and the largest column visited in row i, the cells in
+ *      between included; every row is visited.  cost = acc[na-1][nb-1].  A NaN never replaces a candidate and cannot move the
+ *      path out of the region; the cost may then be NaN, as in D2.
+ * It follows that pos does not decrease, pos[i+1] - pos[i] <= 2, pos[i+2] - pos[i] >= 1, a row spans at most two columns,
+ * and, for finite features, cost is never below the cost of llsm_gpu_batch_align on the same pair as float32 values
+ * (rounded addition and minimum are monotone, and the paths are a subset with the same order of operations).
+ *
+ * Refused: everything llsm_gpu_batch_align refuses, by the same code and in the same order, the cap of 2^28 cells on the sum
+ * of na x nb among it; and with n_pairs > 0 a pair that is not admissible (the message names the pair, na and nb), checked
+ * pair by pair before anything is allocated.  n_pairs == 0 returns 0.
+ * Known limits: the whole matrix of D is computed although the region is about a third of a square pair; there is no band
+ * variant, so the cap holds a pair to about 16 400 x 16 400; one wavefront walks a pair; P = 1 is the only pattern. */
+int  llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi);   /* host only; lo, hi: na entries each, both may be NULL */
+int  llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
 
 /* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
  * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere

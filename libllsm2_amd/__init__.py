@@ -158,6 +158,7 @@ llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
 llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f0
 llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
 llsm_gpu_batch_align_band llsm_gpu_align_band_min llsm_gpu_align_band_rows
+llsm_gpu_batch_align_slope llsm_gpu_align_slope_rows
 llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select llsm_gpu_batch_select_chain
 """.split()
 
@@ -245,6 +246,12 @@ def load():
         L.llsm_gpu_batch_align_band.argtypes = [vp, vp, C.c_int, P_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
         L.llsm_gpu_align_band_min.argtypes = [C.c_int, C.c_int]
         L.llsm_gpu_align_band_rows.argtypes = [C.c_int, C.c_int, C.c_int, P_int, P_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the slope pattern)
+        L.llsm_gpu_batch_align_slope.argtypes = [vp, vp, C.c_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
+        L.llsm_gpu_align_slope_rows.argtypes = [C.c_int, C.c_int, P_int, P_int]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -454,6 +461,16 @@ def align_band_rows(na, nb, band):
     lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
     _check(load().llsm_gpu_align_band_rows(int(na), int(nb), int(band), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
            "align_band_rows")
+    return lo, hi
+
+
+def align_slope_rows(na, nb):
+    """(lo, hi): the first and the last column of every row of an na x nb pair under the slope pattern, int32 [na] each,
+    lo > hi where no path stops on the row (llsm_gpu_align_slope_rows, rule L1 of llsm_gpu_batch_align_slope); a pair that
+    is not admissible is refused"""
+    lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
+    _check(load().llsm_gpu_align_slope_rows(int(na), int(nb), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
+           "align_slope_rows")
     return lo, hi
 
 
@@ -712,7 +729,8 @@ class Batch:
         with this batch as the target; 9: the band planes of the last align_band with this batch as a, pair after pair,
         each na x (2 band + 1), +inf outside the rows' ranges; 10 and 11: the state rows, total_frames x 32 (c of slots
         0 ... 15, then their bank frames; absent slots 1e30 and -1), and the join costs, total_frames x 256 (entry 16 a + j),
-        of the last select_chain with this batch as the target)"""
+        of the last select_chain with this batch as the target; 12: the distance planes of the last align_slope with this
+        batch as a, pair after pair, each na x nb)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -767,6 +785,21 @@ class Batch:
         _check(self.L.llsm_gpu_batch_align_band(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
                                                 bd.ctypes.data_as(P_int), C.byref(o), pos.ctypes.data_as(P_fp),
                                                 cost.ctypes.data_as(P_fp)), "align_band")
+        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+
+    def align_slope(self, other, utt_a, utt_b, **options):
+        """align with the local slope of the path held within [1/2, 2] (llsm_gpu_batch_align_slope): no frame of either
+        utterance is held for more than two frames of the other, none is skipped.  Pairs outside nb - 1 <= 2 (na - 1),
+        na - 1 <= 2 (nb - 1) are refused.  Returns what align returns"""
+        o = make_align_options(**options)
+        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
+        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
+        nfrm = np.diff(self.frm_off)
+        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
+        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        _check(self.L.llsm_gpu_batch_align_slope(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                                                 C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align_slope")
         return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders

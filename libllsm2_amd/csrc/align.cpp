@@ -8,8 +8,12 @@
 //   llsm_gpu_align_band_min / _rows  host only: the least connected band of a pair and the column range of every row (rule B1)
 //   llsm_gpu_batch_align_band        the same inside a band around the diagonal (rules B1 - B4), with
 //                                    scratch of its own
+//   llsm_gpu_align_slope_rows        host only: whether a pair is admissible under the slope pattern and the column range of
+//                                    every row (rule L1)
+//   llsm_gpu_batch_align_slope       the whole planes again, and a path whose local slope stays within [1/2, 2] (rules L1 -
+//                                    L4, DESIGN.md section 27: k_align_slope_dtw), with scratch of its own
 //
-// The two calls are one function, align_run.  Every check runs before anything is allocated, copied or launched.  The
+// The three calls are one function, align_run.  Every check runs before anything is allocated, copied or launched.  The
 // scratch lives on batch a, grow-only.
 #include <hip/hip_runtime.h>
 
@@ -23,6 +27,7 @@
 namespace {
 const char* kAlign = "llsm_gpu_batch_align";
 const char* kBand = "llsm_gpu_batch_align_band";
+const char* kSlope = "llsm_gpu_batch_align_slope";
 const long long kMaxCells = 1ll << 28;
 
 int refuse(const std::string& why, const char* who = kAlign) { llsm_set_error(std::string(who) + ": " + why); return -1; }
@@ -38,6 +43,14 @@ int band_min(int na, int nb) {
     gap = std::max(gap, n - c); c = n;
   }
   return gap / 2;                                                   // ceil((gap - 1) / 2) for gap >= 0
+}
+
+// rule L1: empty if an na x nb pair (na, nb >= 1) is admissible under the slope pattern, else the bound that fails
+std::string slope_bound(int na, int nb) {
+  const long long ra = (long long)na - 1, rb = (long long)nb - 1;
+  if(rb > 2 * ra) return "nb - 1 = " + std::to_string(rb) + " exceeds 2 (na - 1) = " + std::to_string(2 * ra);
+  if(ra > 2 * rb) return "na - 1 = " + std::to_string(ra) + " exceeds 2 (nb - 1) = " + std::to_string(2 * rb);
+  return "";
 }
 
 // the options checked against a coder of these orders, count resolved; -1 with the error set in the name of `who`
@@ -70,11 +83,12 @@ extern "C" int llsm_gpu_align_check(const llsm_gpu_align_options* opt, int order
 namespace {
 static_assert(ALIGN_TILE == 64, "a row of tiles of the distance kernel is a strip of 64 rows of the path kernel");
 
-// Both calls: llsm_gpu_batch_align_band with `banded`, else llsm_gpu_batch_align (band is not read: the whole matrix of every
-// pair).  The checks run in the order in which either call has always made them.
-int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, bool banded,
+// The three calls: llsm_gpu_batch_align_band with kBand, else band is not read and the planes hold the whole matrix of every
+// pair: llsm_gpu_batch_align with kAlign, llsm_gpu_batch_align_slope with kSlope.  The checks run in the order in which the
+// calls have always made them.
+int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, const char* who,
   const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  const char* who = banded ? kBand : kAlign;
+  const bool banded = who == kBand, slope = who == kSlope;
   if(! a || ! b) return refuse("NULL batch", who);
   if(n_pairs < 0) return refuse("n_pairs < 0", who);
   if(a -> ctx != b -> ctx) return refuse("the batches belong to different contexts", who);
@@ -99,12 +113,21 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     return ub < 0 || ub >= b -> lay.n_utt ? 0 : na * std::max(b -> nfrm[ub], 0);
   };
   // rows [i0, i0 + 63] of a pair, a strip of the path kernel and a row of tiles of the distance kernel: the first column
-  // of its first row and the last of its last as the plane stores them (under a band they may lie outside the matrix)
+  // of its first row and the last of its last as the plane stores them (under a band they may lie outside the matrix; the
+  // slope pattern stores whole rows and walks the window of slope_window below)
   auto span = [&](const AlignPair& q, int i0, int& jlo, int& jhi) {
     const int i1 = std::min(i0 + 63, q.na - 1);
     jlo = banded ? align_band_center(i0, q.na, q.nb) - q.band : 0;
     jhi = banded ? align_band_center(i1, q.na, q.nb) + q.band : q.nb - 1;
     return i1;
+  };
+  // rule L1 for the same rows: lo of the first and hi of the last (neither decreases with the row), and the steps
+  // k_align_slope_dtw takes over them: one more where a strip follows, whose first row may be entered past column jhi
+  auto slope_window = [&](const AlignPair& q, int i0, int& jlo, int& jhi) {
+    const int i1 = std::min(i0 + 63, q.na - 1);
+    int unused;
+    align_slope_row(i0, q.na, q.nb, jlo, unused); align_slope_row(i1, q.na, q.nb, unused, jhi);
+    return jhi - jlo + 1 + i1 - i0 + (i1 + 1 < q.na ? 1 : 0);
   };
   auto tile_floor = [](int j) { return j >= 0 ? j / ALIGN_TILE * ALIGN_TILE : -((-j + ALIGN_TILE - 1) / ALIGN_TILE * ALIGN_TILE); };
   std::vector<AlignPair> pairs((size_t)n_pairs);
@@ -121,6 +144,10 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     if(bd < least)
       return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
         std::to_string(nb) + " frames: llsm_gpu_align_band_min is " + std::to_string(least), who);
+    if(slope) {
+      const std::string bound = slope_bound(na, nb);
+      if(! bound.empty()) return refuse(pair() + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound, who);
+    }
     AlignPair& q = pairs[p];
     q.a0 = a -> frm_off[ua]; q.na = na; q.b0 = b -> frm_off[ub]; q.nb = nb;
     q.cell0 = (int)cells; q.row0 = (int)rows; q.pos0 = (int)frames; q.band = bd; q.mv0 = steps; q.pad = 0;
@@ -134,14 +161,14 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     q.steps = 0;
     for(int i0 = 0, jlo, jhi; i0 < na; i0 += 64) {
       const int i1 = span(q, i0, jlo, jhi);
-      q.steps = std::max(q.steps, std::min(jhi, nb - 1) - std::max(jlo, 0) + 1 + i1 - i0);
       n_tiles += (jhi - tile_floor(jlo)) / ALIGN_TILE + 1;
+      q.steps = std::max(q.steps, slope ? slope_window(q, i0, jlo, jhi) : std::min(jhi, nb - 1) - std::max(jlo, 0) + 1 + i1 - i0);
     }
-    rows += nb; frames += na;
+    rows += slope ? 2ll * nb : nb; frames += na;
     steps += (long long)((na + 63) / 64) * q.steps;
   }
   // accepted: from here on this call's scratch on a changes (and the other call's, its plane among it, does not)
-  llsm_gpu_batch::AlignScratch& sc = banded ? a -> alb : a -> al;
+  llsm_gpu_batch::AlignScratch& sc = banded ? a -> alb : slope ? a -> als : a -> al;
   std::vector<int4> tiles; tiles.reserve((size_t)n_tiles);
   for(int p = 0; p < n_pairs; p ++)                                 // the tiles of the matrix that meet the rows' columns, overhang included
     for(int i0 = 0, jlo, jhi; i0 < pairs[p].na; i0 += ALIGN_TILE) {
@@ -163,7 +190,8 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   d.step_cost = o.step_cost; d.voicing_cost = o.voicing_cost;
   d.pairs = sc.pairs.p; d.n_pairs = n_pairs;
   int rc = launch_align_dist(P, banded, d, sc.tiles.p, (int)tiles.size(), sc.plane.p);
-  if(! rc) rc = launch_align_dtw(P, banded, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames);
+  if(! rc) rc = slope ? launch_align_slope_dtw(P, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
+                      : launch_align_dtw(P, banded, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames);
   if(rc) return refuse(std::string("launch failed: ") + hipGetErrorString((hipError_t)rc), who);
   // into memory of our own first: a failed copy leaves pos and cost untouched
   std::vector<float> host(n_out);
@@ -178,7 +206,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
 
 extern "C" int llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, false, nullptr, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, kAlign, nullptr, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- inside a diagonal band (rules B1 - B4)
@@ -205,5 +233,24 @@ extern "C" int llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* 
 
 extern "C" int llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, true, band, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, kBand, band, opt, pos, cost);
+}
+
+// ---------------------------------------------------------------- local slopes within [1/2, 2] (rules L1 - L4)
+extern "C" int llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi) {
+  const char* who = "llsm_gpu_align_slope_rows";
+  if(na < 1 || nb < 1) return refuse("na < 1 or nb < 1 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ")", who);
+  const std::string bound = slope_bound(na, nb);
+  if(! bound.empty()) return refuse(std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound, who);
+  for(int i = 0, l, h; i < na && (lo || hi); i ++) {
+    align_slope_row(i, na, nb, l, h);
+    if(lo) lo[i] = l;
+    if(hi) hi[i] = h;
+  }
+  return 0;
+}
+
+extern "C" int llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
+  const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
+  return align_run(a, b, n_pairs, utt_a, utt_b, kSlope, nullptr, opt, pos, cost);
 }

@@ -1,6 +1,7 @@
-// align_kernels.hip -- alignment of utterance pairs: llsm_gpu_batch_align (rules D1 - D3: llsm_gpu.h)
-// and llsm_gpu_batch_align_band (rules B1 - B4, section 25); host side: align.cpp.  Two kernel templates, each instantiated
-// for the two geometries:
+// align_kernels.hip -- alignment of utterance pairs: llsm_gpu_batch_align (rules D1 - D3: llsm_gpu.h),
+// llsm_gpu_batch_align_band (rules B1 - B4, section 25) and llsm_gpu_batch_align_slope (rules L1 - L4, section 27; its path
+// kernel k_align_slope_dtw is described above it, its planes are k_align_dist_t's full ones); host side: align.cpp.  Two
+// kernel templates, each instantiated for the two geometries:
 //   full    row i spans columns 0 ... nb - 1 and is stored as it is: off = 0, width = nb, all of it known when compiling
 //   band    row i spans lo_i = max(off_i, 0) ... hi_i = min(off_i + 2 band, nb - 1), off_i = align_band_center(i) - band, and
 //           entry q of its row of the plane [na][width = 2 band + 1] is column off_i + q
@@ -279,6 +280,141 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
   if(lane == 0) pos[0] = __fmul_rn((float)(0 + hi), 0.5f);
 }
 
+// ---------------------------------------------------------------- L3 - L4: the path under the slope pattern
+// The layout of k_align_dtw_t over whole-matrix planes: lane l on row i = 64 s + l, on column j = wlo + t - l at step t, the
+// strip's window [wlo, whi] = [lo of its first row, hi of its last] (rule L1; lo and hi do not decrease with i, so the
+// window holds every row's range).  What a lane holds when it reaches (i, j):
+//   diag   acc[i-1][j-1], the `up` it received one step ago: move 0
+//   qi     (acc[i-2][j-1] + D[i-1][j]) + step_cost, which the lane above formed one step ago on (i - 1, j): move 1.  It comes
+//          with a second wavefront shift; lane 0 takes it from the second hand-over row
+//   qo     (acc[i-1][j-2] + D[i][j-1]) + step_cost, which the lane formed itself one step ago on (i, j - 1): move 2
+// and one sum serves the last two: through (i, j) from (i - 1, j - 1) the path goes on to (i, j + 1) by move 2 or to
+// (i + 1, j) by move 1, and either candidate is (diag + D[i][j]) + step_cost.  A lane forms it on every cell it passes,
+// inside its row's range or not: the cell between the two ends of a move need not lie in the region, and whether a
+// candidate exists is decided where it is used, by integer comparisons of j with the ranges of rows i - 1 and i - 2, so what
+// a lane outside its range, an earlier strip or unwritten memory left behind is never used.
+// Hand-over: lane 63 leaves acc[i][j] in the first row and that sum in the second, both indexed by the column, for lane 0 of
+// the next strip.  The sum is needed one column past whi, where a move 1 into row i + 1 passes (i, hi_i + 1), so a strip
+// that has a successor takes one step more.  Lane 0 starts a strip on column wlo with diag = acc[i-1][wlo-1] and, for a move
+// 2 from (i - 1, wlo - 2), qo = (acc[i-1][wlo-2] + D[i][wlo-1]) + step_cost, both from the first row before the loop.  All
+// lanes count their steps from the same wlo: lane 0 loads column x of either row at step x - wlo at the latest and lane 63
+// stores column x at step x - wlo + 63, so the reads stay ahead of the writes by 63 steps however narrow the window is;
+// the loads past the window's end are clamped to column nb - 1 and not used.
+// The walk back reads the masks as k_align_dtw_t does.  Every move leaves its row, so pos[i] follows from the cell and the
+// move: columns j - 1 and j under move 2, else j alone; move 1 passes (i - 1, j) and nothing else of row i - 1.  Each move
+// lowers i and j by one at the least: at most min(na, nb) - 1 moves.
+struct SlopeBlock { float d[DTW_U], p[DTW_U], q[DTW_U]; };
+// as dtw_load<false>, with the second hand-over row beside the first
+DEV void slope_load(SlopeBlock& b, const float* __restrict__ drow, const float* hand, const float* handq, int j0, int lane, int nb) {
+#pragma unroll
+  for(int k = 0; k < DTW_U; k ++) {
+    const int x = min(max(j0 + lane + k, 0), nb - 1);
+    b.d[k] = drow[min(max(j0 + k, 0), nb - 1)];
+    b.p[k] = hand[x]; b.q[k] = handq[x];
+  }
+}
+
+__global__ __launch_bounds__(WAVE) void k_align_slope_dtw(AlignDev d, const float* __restrict__ plane, uint4* __restrict__ moves,
+  float* hand_rows, float* __restrict__ out, int cost0) {
+  const int lane = threadIdx.x;
+  const AlignPair p = d.pairs[blockIdx.x];
+  const int na = p.na, nb = p.nb;
+  const float* D = plane + (size_t)p.cell0;
+  float* hand = hand_rows + (size_t)p.row0;
+  float* handq = hand + nb;
+  uint4* mv = moves + p.mv0;
+  const long long per_strip = p.steps;
+  const float step = d.step_cost;
+  const int nstrips = (na + WAVE - 1) / WAVE;
+  float v = 0.0f;                                                     // acc of this lane's last cell
+  for(int s = 0; s < nstrips; s ++) {
+    const int i = s * WAVE + lane, rows = min(WAVE, na - s * WAVE);
+    const bool more = s + 1 < nstrips;
+    // the range of this lane's row; the columns j for which (i - 1, j - 1) and (i - 2, j - 1) lie in the region; empty
+    // ranges (1, 0) where there is no such row
+    int lo = 1, hi = 0, a0 = 1, b0 = 0, a1 = 1, b1 = 0;
+    if(i < na) {
+      align_slope_row(i, na, nb, lo, hi);
+      if(i >= 1) { align_slope_row(i - 1, na, nb, a0, b0); a0 ++; b0 ++; }
+      if(i >= 2) { align_slope_row(i - 2, na, nb, a1, b1); a1 ++; b1 ++; }
+    }
+    const int wlo = __shfl(lo, 0), whi = __shfl(hi, rows - 1), nsteps = whi - wlo + rows + (more ? 1 : 0);
+    const float* drow = D + (size_t)min(i, na - 1) * nb;
+    uint4* mvs = mv + (long long)s * per_strip;
+    // lane 0's first cell (file head; in strip 0 nothing of it is used)
+    float diag = hand[max(wlo - 1, 0)];
+    float qo = __fadd_rn(__fadd_rn(hand[max(wlo - 2, 0)], drow[max(wlo - 1, 0)]), step);
+    unsigned long long w0 = 0, w1 = 0;                                // the masks of step (t & ~63) + lane
+    SlopeBlock cur, nxt;
+    slope_load(cur, drow, hand, handq, wlo - lane, lane, nb);
+    for(int t0 = 0; t0 < nsteps; t0 += DTW_U) {
+      slope_load(nxt, drow, hand, handq, wlo + t0 + DTW_U - lane, lane, nb);
+#pragma unroll
+      for(int k = 0; k < DTW_U; k ++) {
+        const int t = t0 + k;
+        if(t >= nsteps) break;
+        const int j = wlo + t - lane;
+        const bool on = j >= lo && j <= hi;
+        const bool has0 = j >= a0 && j <= b0, has1 = j >= a1 && j <= b1, has2 = j - 1 >= a0 && j - 1 <= b0;
+        const float up_raw = wave_shr1(cur.p[k], v);                  // acc[i-1][j]
+        const float qi = wave_shr1(cur.q[k], qo);
+        float m = diag; int move = 0;                                 // L3: the first candidate that exists ...
+        if(! has0) { m = qi; move = 1; }
+        if(! has0 && ! has1) { m = qo; move = 2; }
+        if(has0 && has1 && qi < m) { m = qi; move = 1; }              // ... and a later one only if strictly smaller
+        if((has0 || has1) && has2 && qo < m) { m = qo; move = 2; }
+        float acc = __fadd_rn(m, cur.d[k]);
+        if(i == 0 && j == 0) { acc = cur.d[k]; move = 0; }
+        qo = __fadd_rn(__fadd_rn(diag, cur.d[k]), step);              // through (i, j) from (i - 1, j - 1)
+        diag = up_raw;
+        if(on) v = acc;
+        const unsigned long long m0 = __ballot(on && (move & 1)), m1 = __ballot(on && (move & 2));
+        if((t & (WAVE - 1)) == lane) { w0 = m0; w1 = m1; }
+        if(((t & (WAVE - 1)) == WAVE - 1 || t == nsteps - 1) && lane <= (t & (WAVE - 1)))
+          mvs[(t & ~(WAVE - 1)) + lane] = make_uint4((unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32));
+        if(lane == WAVE - 1 && more && j >= 0 && j < nb) {            // for lane 0 of the next strip
+          handq[j] = qo;
+          if(on) hand[j] = acc;
+        }
+      }
+      cur = nxt;
+    }
+    __threadfence();                                                  // the hand-over rows and the masks, before other lanes read them
+  }
+  const int last = (na - 1) & (WAVE - 1);
+  if(lane == last) out[cost0 + blockIdx.x] = v;                       // acc[na-1][nb-1]: the last cell of the last row's range
+
+  // L4: back along the moves
+  float* pos = out + (size_t)p.pos0;
+  int i = na - 1, j = nb - 1;
+  int cur_s = -1, cur_b = -1, wlo = 0;
+  uint4 w = make_uint4(0, 0, 0, 0);
+  for(int guard = min(na, nb); guard > 0; guard --) {
+    if(i == 0 && j == 0) break;
+    const int s = i >> 6, l = i & (WAVE - 1);
+    if(s != cur_s) { int h; align_slope_row((long long)s * WAVE, na, nb, wlo, h); }
+    const int t = j - wlo + l, blk = t & ~(WAVE - 1);
+    if(t < 0 || t >= per_strip) break;                                // (a cell outside the region: no stored move leads there)
+    if(s != cur_s || blk != cur_b) {
+      w = make_uint4(0, 0, 0, 0);
+      if((long long)blk + lane < per_strip) w = mv[(long long)s * per_strip + blk + lane];
+      cur_s = s; cur_b = blk;
+    }
+    const int k = t & (WAVE - 1);
+    const unsigned m0 = (unsigned)__builtin_amdgcn_readlane((int)(l < 32 ? w.x : w.y), k);
+    const unsigned m1 = (unsigned)__builtin_amdgcn_readlane((int)(l < 32 ? w.z : w.w), k);
+    const int move = (int)((m0 >> (l & 31)) & 1u) | (int)(((m1 >> (l & 31)) & 1u) << 1);
+    if(i < 1 || j < 1 || move == 3 || (move == 1 && i < 2) || (move == 2 && j < 2)) break;   // (likewise: it would leave the matrix)
+    if(lane == 0) pos[i] = __fmul_rn((float)(2 * j - (move == 2)), 0.5f);
+    if(move == 1) {
+      if(lane == 0) pos[i - 1] = __fmul_rn((float)(2 * j), 0.5f);     // (i - 1, j) on the way to (i - 2, j - 1)
+      i -= 2; j --;
+    } else if(move == 2) { i --; j -= 2; }
+    else { i --; j --; }
+  }
+  if(lane == 0) pos[0] = 0.0f;                                        // row 0 is (0, 0) alone
+}
+
 // ---------------------------------------------------------------- launchers
 int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* tiles, int n_tiles, float* plane) {
   if(n_tiles == 0) return 0;
@@ -291,5 +427,11 @@ int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* pl
   if(d.n_pairs == 0) return 0;
   if(band) LAUNCH("k_align_band_dtw", k_align_dtw_t<true>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0);
   else LAUNCH("k_align_dtw", k_align_dtw_t<false>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0);
+  return 0;
+}
+
+int launch_align_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0) {
+  if(d.n_pairs == 0) return 0;
+  LAUNCH("k_align_slope_dtw", k_align_slope_dtw, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0);
   return 0;
 }

@@ -332,17 +332,25 @@ int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);
 // rules T2 - T5 over the candidate plane: f0[nframes]; bp: one word per frame of scratch
 int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0);
 
-// ---- alignment of utterance pairs, whole matrix or inside a diagonal band (align.cpp, align_kernels.hip; rules D1 - D3
-// and B1 - B4: llsm_gpu.h)
+// ---- alignment of utterance pairs: whole matrix, inside a diagonal band, or whole matrix under the slope pattern (align.cpp,
+// align_kernels.hip; rules D1 - D3, B1 - B4 and L1 - L4: llsm_gpu.h)
 // The centre column of row i of an na x nb pair, rule B1: the diagonal rounded half up.  Row i spans columns
 // max(0, c - band) ... min(nb - 1, c + band); entry q of its row of the band plane is column c - band + q.
 __host__ __device__ static inline int align_band_center(int i, int na, int nb) {
   return na > 1 ? (int)((2ll * i * (nb - 1) + (na - 1)) / (2ll * (na - 1))) : 0;
 }
+// The columns lo ... hi of row i of an admissible na x nb pair under the slope pattern, rule L1 (llsm_gpu_batch_align_slope):
+// the cells from which (0, 0) is reached backwards and (na - 1, nb - 1) forwards.  lo > hi: no path stops on the row.
+__host__ __device__ static inline void align_slope_row(long long i, int na, int nb, int& lo, int& hi) {
+  const long long r = (long long)na - 1 - i, l0 = (i + 1) / 2, l1 = (long long)nb - 1 - 2 * r, h0 = 2 * i,
+                  h1 = (long long)nb - 1 - (r + 1) / 2;
+  lo = (int)(l0 > l1 ? l0 : l1); hi = (int)(h0 < h1 ? h0 : h1);
+}
 // One pair: rows [a0, a0 + na) of code_a against rows [b0, b0 + nb) of code_b (flat frame indices); its plane -- [na][nb],
 // or [na][2 band + 1] of a banded call -- starts at float cell0 of the planes, its moves at entry mv0 (`steps` entries of
 // 16 bytes per strip of 64 rows: the anti-diagonals of the strip whose column window is the widest), its hand-over row
-// at float row0, its positions at float pos0 of the out block.  band is 0 and not read where the whole matrix is searched.
+// (two rows of nb floats under the slope pattern) at float row0, its positions at float pos0 of the out block.  band is 0
+// and not read where the whole matrix is searched.
 struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
 #define ALIGN_TILE 64                                  // k_align_dist_t: cells per side of a workgroup's tile
 struct AlignDev {
@@ -354,6 +362,8 @@ struct AlignDev {
 int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* tiles, int n_tiles, float* plane);
 // D2 - D3 / B3 - B4 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
 int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
+// L3 - L4 over whole-matrix planes, one wavefront per pair; row: two hand-over rows of nb floats per pair, out as above
+int launch_align_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
 
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5 and C1 - C6: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame
