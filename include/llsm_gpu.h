@@ -172,6 +172,10 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * which = 12: the distance planes of the last successful llsm_gpu_batch_align_slope with this batch as a (rule L2 below that
  * call, which is D1): pair after pair in list order, each [na][nb] row-major, the whole matrix.  Refused until such a call
  * has run; no other call writes it, and that call writes neither plane 6 nor plane 9.
+ * which = 13: the band planes of the last successful llsm_gpu_batch_align_band_slope with this batch as a (rules K1 - K2 below
+ * that call), laid out as plane 9: pair after pair in list order, each [na][2 band + 1] row-major, entry q of row i column
+ * c_i - band + q, +infinity where that column lies outside the band's row [p_i, q_i] (the whole band, not only the region of
+ * K1).  Refused until such a call has run; no other call writes it, and that call writes none of planes 6, 9 and 12.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -534,7 +538,7 @@ int  llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pair
  * above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
  * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else, so it has to be as
  * wide as the renditions drift apart; there are no slope constraints beyond monotonicity (llsm_gpu_batch_align_slope below
- * has them, over the whole matrix). */
+ * has them over the whole matrix, llsm_gpu_batch_align_band_slope inside this band). */
 int  llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const int* band /* n_pairs half-widths, frames */, const llsm_gpu_align_options* opt /* NULL: defaults */,
        FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
@@ -583,11 +587,78 @@ int  llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* hi);  /* h
  * Refused: everything llsm_gpu_batch_align refuses, by the same code and in the same order, the cap of 2^28 cells on the sum
  * of na x nb among it; and with n_pairs > 0 a pair that is not admissible (the message names the pair, na and nb), checked
  * pair by pair before anything is allocated.  n_pairs == 0 returns 0.
- * Known limits: the whole matrix of D is computed although the region is about a third of a square pair; there is no band
- * variant, so the cap holds a pair to about 16 400 x 16 400; one wavefront walks a pair; P = 1 is the only pattern. */
+ * Known limits: the whole matrix of D is computed although the region is about a third of a square pair, so the cap holds a
+ * pair to about 16 400 x 16 400 -- longer material goes through llsm_gpu_batch_align_band_slope below, the same pattern inside
+ * a band; one wavefront walks a pair; P = 1 is the only pattern. */
 int  llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi);   /* host only; lo, hi: na entries each, both may be NULL */
 int  llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+
+/* ---- slope-constrained alignment inside a diagonal band: the moves of llsm_gpu_batch_align_slope searched among the cells
+ * of the band of llsm_gpu_batch_align_band, so that long material -- two five-minute renditions of 60 000 frames under a band of
+ * 500 -- gets a path without stalls and jumps: the planes, the moves and the time of a pair are na x (2 band + 1).  The contract
+ * is that of llsm_gpu_batch_align_band -- the same band array, the same pos and cost, the same options and
+ * llsm_gpu_align_check, synchronous, a refused call returns -1 with a message that starts with
+ * "llsm_gpu_batch_align_band_slope:", launches and allocates nothing and leaves pos and cost untouched; LLSM_GPU_CODE of both
+ * batches is read and no array of either written; a == b is allowed -- with scratch of its own on a (the band planes,
+ * llsm_gpu_batch_debug_plane(a, 13, ...), always kept): planes 6, 9 and 12 and the scratch of the other three calls stay as they
+ * were.  A pair's result depends on its own two utterances, its band and the options only.
+ *
+ * The rules, per pair; float32, one rounding per operation, no contraction; integers taken in 64 bits.
+ *  K1. The region.  A pair must be admissible under L1.  p_i ... q_i is the column range of row i of the band of rule B1
+ *      (lo_i and hi_i there, c_i unchanged).  A move of L3 is allowed when both of its ends lie in the band and the cell it
+ *      passes lies in the band: move 1 passes (i - 1, j), move 2 passes (i, j - 1).  The region is the set of cells that lie on
+ *      some path of allowed moves from (0, 0) to (na - 1, nb - 1).  It is computed by two integer sweeps over intervals; an
+ *      interval with lower end > upper end is empty, and empty intervals contribute nothing.
+ *        Forward.  F_0 = [0, 0].  For i >= 1, with F_{i-1} = [a, b] and F_{i-2} = [c, d], the pieces are
+ *          [max(a + 1, p_i), min(b + 1, q_i)] for move 0, [max(a + 2, p_i + 1), min(b + 2, q_i)] for move 2 and, for i >= 2,
+ *          [max(c + 1, p_i, p_{i-1}), min(d + 1, q_i, q_{i-1})] for move 1; F_i runs from the least lower end to the largest
+ *          upper end of the non-empty pieces.
+ *        Backward.  G_{na-1} = [nb - 1, nb - 1] if q_{na-1} >= nb - 1, else empty.  For i < na - 1, with G_{i+1} = [a, b] and
+ *          G_{i+2} = [c, d], the pieces are [max(a - 1, p_i), min(b - 1, q_i)], [max(a - 2, p_i, p_{i+1} - 1), min(b - 2, q_i)]
+ *          and, for i + 2 < na, [max(c - 1, p_i, p_{i+1} - 1), min(d - 1, q_i, q_{i+1} - 1)].
+ *      Row i of the region is the intersection of F_i and G_i; an empty row is reported as lo = 1, hi = 0: no path stops on
+ *      it, it is only passed through, as in L1.  The band is connected for the slope pattern when row na - 1 is non-empty; it
+ *      is then [nb - 1, nb - 1], and row 0 is [0, 0].  Connectedness is monotone in band.
+ *      That the pieces always join into one interval -- so that the sweeps give exactly the reachable sets --, that lo and
+ *      hi of a connected band do not decrease over the non-empty rows and that no two consecutive rows are empty is MEASURED,
+ *      not proven: the rule rests on tests/test_align_band_slope_host.py, which compares the sweeps with reachability cell
+ *      by cell for every admissible na, nb <= 40 at every band.  With band >= nb - 1 the non-empty rows are those of L1; the
+ *      least connected band is 0 or 1 for every admissible pair up to 70 x 70 (64 x 64: 0; 63 x 64: 1).
+ *      llsm_gpu_align_band_slope_min returns the least connected band, or -1 with a message for na < 1, nb < 1, a pair that
+ *      is not admissible or na above 2^28 (the sweeps hold a few words per row, and no call takes such a pair).
+ *      llsm_gpu_align_band_slope_rows fills lo and hi (na entries each; either may be NULL, both NULL only asks whether the
+ *      band is connected) and returns 0, or -1 with a message that names na, nb and the band -- and
+ *      llsm_gpu_align_band_slope_min of the pair where the band is not connected -- for na < 1, nb < 1, a pair that is not
+ *      admissible, na above 2^28, and a band that is negative or not connected for the pattern.  Both are host only and
+ *      need no device.
+ *  K2. D[i][j] is rule D1 unchanged, for the cells of the band only (rule B2 unchanged).
+ *  K3. acc[0][0] = D[0][0].  For every other cell (i, j) of the region the candidates are, in this order:
+ *        move 0: acc[i-1][j-1], if (i - 1, j - 1) is in the region;
+ *        move 1: (acc[i-2][j-1] + D[i-1][j]) + step_cost, if (i - 2, j - 1) is in the region and p_{i-1} <= j <= q_{i-1};
+ *        move 2: (acc[i-1][j-2] + D[i][j-1]) + step_cost, if (i - 1, j - 2) is in the region and j - 1 >= p_i.
+ *      m starts from the first candidate that exists, and a later one replaces it only if it is strictly smaller;
+ *      acc[i][j] = m + D[i][j].  Which candidates exist is decided by integer comparisons with the rows of the region and of
+ *      the band, never by values.  Every cell of the region other than (0, 0) has a candidate.
+ *  K4. L4 unchanged, over the moves of K3: at most min(na, nb) - 1 moves; pos[i] from the least and the largest column visited
+ *      in row i, the passed cells included; every row is visited; cost = acc[na-1][nb-1].  A NaN never replaces a candidate
+ *      and cannot move the path out of the region.
+ * It follows that the properties of pos listed under L4 hold, and every pos[i] lies in [p_i, q_i]; that where the band covers
+ * the matrix (band >= nb - 1) pos and cost are the bits of llsm_gpu_batch_align_slope; and that, for finite features, cost is
+ * never below the cost of llsm_gpu_batch_align_slope on the pair, nor below that of llsm_gpu_batch_align_band with the same
+ * band: each path here is a path of those rules with the same sequence of operations.
+ *
+ * Refused: everything llsm_gpu_batch_align refuses, by the same code and in the same order; and with n_pairs > 0 a NULL band,
+ * a negative band, a pair that is not admissible under L1 (in the words of llsm_gpu_batch_align_slope), a band that is not
+ * connected for the slope pattern on its pair (the message names the pair and llsm_gpu_align_band_slope_min of it), and a sum
+ * of na x (2 band + 1) above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
+ * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else; P = 1 is the only
+ * pattern; the rows of the region are computed on the host, na steps per pair and call. */
+int  llsm_gpu_batch_align_band_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       const int* band /* n_pairs half-widths, frames */, const llsm_gpu_align_options* opt /* NULL: defaults */,
+       FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+int  llsm_gpu_align_band_slope_min(int na, int nb);                                  /* host only */
+int  llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo, int* hi);     /* host only; na entries each, both may be NULL */
 
 /* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
  * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere

@@ -159,6 +159,7 @@ llsm_gpu_f0_track_default_options llsm_gpu_f0_track_check llsm_gpu_batch_track_f
 llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
 llsm_gpu_batch_align_band llsm_gpu_align_band_min llsm_gpu_align_band_rows
 llsm_gpu_batch_align_slope llsm_gpu_align_slope_rows
+llsm_gpu_batch_align_band_slope llsm_gpu_align_band_slope_min llsm_gpu_align_band_slope_rows
 llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select llsm_gpu_batch_select_chain
 """.split()
 
@@ -252,6 +253,13 @@ def load():
     try:                                                 # (as above: an experiment build of an earlier commit lacks the slope pattern)
         L.llsm_gpu_batch_align_slope.argtypes = [vp, vp, C.c_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
         L.llsm_gpu_align_slope_rows.argtypes = [C.c_int, C.c_int, P_int, P_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the banded slope pattern)
+        L.llsm_gpu_batch_align_band_slope.argtypes = [vp, vp, C.c_int, P_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
+        L.llsm_gpu_align_band_slope_min.argtypes = [C.c_int, C.c_int]
+        L.llsm_gpu_align_band_slope_rows.argtypes = [C.c_int, C.c_int, C.c_int, P_int, P_int]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -471,6 +479,25 @@ def align_slope_rows(na, nb):
     lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
     _check(load().llsm_gpu_align_slope_rows(int(na), int(nb), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
            "align_slope_rows")
+    return lo, hi
+
+
+def align_band_slope_min(na, nb):
+    """the least band that is connected for the slope pattern on an na x nb pair (llsm_gpu_align_band_slope_min, rule K1 of
+    llsm_gpu_batch_align_band_slope); a pair that is not admissible is refused"""
+    r = load().llsm_gpu_align_band_slope_min(int(na), int(nb))
+    if r < 0:
+        raise LlsmError("align_band_slope_min: " + load().llsm_gpu_last_error().decode())
+    return int(r)
+
+
+def align_band_slope_rows(na, nb, band):
+    """(lo, hi): the first and the last column of every row of the region of the slope pattern inside `band` columns of the
+    diagonal, int32 [na] each, lo > hi (1, 0) where no path stops on the row (llsm_gpu_align_band_slope_rows, rule K1); a
+    pair that is not admissible and a band that is negative or not connected for the pattern are refused"""
+    lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
+    _check(load().llsm_gpu_align_band_slope_rows(int(na), int(nb), int(band), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
+           "align_band_slope_rows")
     return lo, hi
 
 
@@ -730,7 +757,8 @@ class Batch:
         each na x (2 band + 1), +inf outside the rows' ranges; 10 and 11: the state rows, total_frames x 32 (c of slots
         0 ... 15, then their bank frames; absent slots 1e30 and -1), and the join costs, total_frames x 256 (entry 16 a + j),
         of the last select_chain with this batch as the target; 12: the distance planes of the last align_slope with this
-        batch as a, pair after pair, each na x nb)"""
+        batch as a, pair after pair, each na x nb; 13: the band planes of the last align_band_slope with this batch as a,
+        laid out as plane 9)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -800,6 +828,23 @@ class Batch:
         pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
         _check(self.L.llsm_gpu_batch_align_slope(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
                                                  C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align_slope")
+        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+
+    def align_band_slope(self, other, utt_a, utt_b, band, **options):
+        """align_slope within `band` columns of the straight diagonal (llsm_gpu_batch_align_band_slope): slopes within
+        [1/2, 2] for utterances whose full matrices align_slope refuses.  band: an int, or one int per pair; a pair that
+        align_slope refuses and a band below align_band_slope_min of the pair are refused.  Returns what align_band returns"""
+        o = make_align_options(**options)
+        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
+        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
+        bd = np.ascontiguousarray(np.broadcast_to(np.asarray(band, np.int32), ua.shape))
+        nfrm = np.diff(self.frm_off)
+        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
+        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        _check(self.L.llsm_gpu_batch_align_band_slope(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                                                      bd.ctypes.data_as(P_int), C.byref(o), pos.ctypes.data_as(P_fp),
+                                                      cost.ctypes.data_as(P_fp)), "align_band_slope")
         return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders

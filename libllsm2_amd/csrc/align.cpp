@@ -12,13 +12,19 @@
 //                                    every row (rule L1)
 //   llsm_gpu_batch_align_slope       the whole planes again, and a path whose local slope stays within [1/2, 2] (rules L1 -
 //                                    L4, DESIGN.md section 27: k_align_slope_dtw), with scratch of its own
+//   llsm_gpu_align_band_slope_min / _rows   host only: the least band that is connected for the slope pattern, and the
+//                                    column range of every row of the region (rule K1: two integer sweeps over intervals)
+//   llsm_gpu_batch_align_band_slope  the slope pattern inside the band (rules K1 - K4, DESIGN.md section 28: the band planes
+//                                    of k_align_band_dist, the region's rows as a table, k_align_band_slope_dtw), with
+//                                    scratch of its own
 //
-// The three calls are one function, align_run.  Every check runs before anything is allocated, copied or launched.  The
+// The four calls are one function, align_run.  Every check runs before anything is allocated, copied or launched.  The
 // scratch lives on batch a, grow-only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -28,6 +34,7 @@ namespace {
 const char* kAlign = "llsm_gpu_batch_align";
 const char* kBand = "llsm_gpu_batch_align_band";
 const char* kSlope = "llsm_gpu_batch_align_slope";
+const char* kBandSlope = "llsm_gpu_batch_align_band_slope";
 const long long kMaxCells = 1ll << 28;
 
 int refuse(const std::string& why, const char* who = kAlign) { llsm_set_error(std::string(who) + ": " + why); return -1; }
@@ -51,6 +58,63 @@ std::string slope_bound(int na, int nb) {
   if(rb > 2 * ra) return "nb - 1 = " + std::to_string(rb) + " exceeds 2 (na - 1) = " + std::to_string(2 * ra);
   if(ra > 2 * rb) return "na - 1 = " + std::to_string(ra) + " exceeds 2 (nb - 1) = " + std::to_string(2 * rb);
   return "";
+}
+
+// rule K1: the rows of the region of an admissible na x nb pair (na, nb >= 1) under the slope pattern inside a band >= 0, by
+// the two sweeps over intervals; an empty row is (1, 0).  Returns whether the band is connected for the pattern, i.e. whether
+// the last row is non-empty.  A piece with lower end > upper end is empty and contributes nothing.
+struct Interval {
+  long long a = 1, b = 0;
+  bool empty() const { return a > b; }
+  void join(long long lo, long long hi) {                           // from the least lower end to the largest upper end
+    if(lo > hi) return;
+    if(empty()) { a = lo; b = hi; } else { a = std::min(a, lo); b = std::max(b, hi); }
+  }
+};
+bool band_slope_rows(int na, int nb, int band, std::vector<int2>& rows) {
+  using std::max; using std::min;
+  std::vector<long long> p((size_t)na), q((size_t)na);
+  for(int i = 0; i < na; i ++) {
+    const long long c = align_band_center(i, na, nb);
+    p[i] = max(c - band, 0ll); q[i] = min(c + band, (long long)nb - 1);
+  }
+  std::vector<Interval> F((size_t)na);
+  F[0].a = 0; F[0].b = 0;
+  for(int i = 1; i < na; i ++) {
+    const Interval& u = F[i - 1];
+    if(! u.empty()) {
+      F[i].join(max(u.a + 1, p[i]), min(u.b + 1, q[i]));                                      // move 0
+      F[i].join(max(u.a + 2, p[i] + 1), min(u.b + 2, q[i]));                                  // move 2, past (i, j - 1)
+    }
+    if(i >= 2 && ! F[i - 2].empty())                                                           // move 1, past (i - 1, j)
+      F[i].join(max(max(F[i - 2].a + 1, p[i]), p[i - 1]), min(min(F[i - 2].b + 1, q[i]), q[i - 1]));
+  }
+  rows.assign((size_t)na, make_int2(1, 0));
+  Interval g1, g2;                                                  // G of rows i + 1 and i + 2
+  for(int i = na - 1; i >= 0; i --) {
+    Interval g;
+    if(i == na - 1) { if(q[i] >= nb - 1) { g.a = nb - 1; g.b = nb - 1; } }
+    else {
+      if(! g1.empty()) {
+        g.join(max(g1.a - 1, p[i]), min(g1.b - 1, q[i]));
+        g.join(max(max(g1.a - 2, p[i]), p[i + 1] - 1), min(g1.b - 2, q[i]));
+      }
+      if(i + 2 < na && ! g2.empty())
+        g.join(max(max(g2.a - 1, p[i]), p[i + 1] - 1), min(min(g2.b - 1, q[i]), q[i + 1] - 1));
+    }
+    if(! g.empty() && ! F[i].empty() && max(g.a, F[i].a) <= min(g.b, F[i].b))
+      rows[i] = make_int2((int)max(g.a, F[i].a), (int)min(g.b, F[i].b));
+    g2 = g1; g1 = g;
+  }
+  return rows[na - 1].x <= rows[na - 1].y;
+}
+// the least band that is connected for the slope pattern (connectedness is monotone in the band, and the band that covers
+// the matrix is connected: its region is that of L1)
+int band_slope_min(int na, int nb) {
+  std::vector<int2> rows;
+  int band = 0;
+  while(band < nb - 1 && ! band_slope_rows(na, nb, band, rows)) band ++;
+  return band;
 }
 
 // the options checked against a coder of these orders, count resolved; -1 with the error set in the name of `who`
@@ -83,12 +147,12 @@ extern "C" int llsm_gpu_align_check(const llsm_gpu_align_options* opt, int order
 namespace {
 static_assert(ALIGN_TILE == 64, "a row of tiles of the distance kernel is a strip of 64 rows of the path kernel");
 
-// The three calls: llsm_gpu_batch_align_band with kBand, else band is not read and the planes hold the whole matrix of every
-// pair: llsm_gpu_batch_align with kAlign, llsm_gpu_batch_align_slope with kSlope.  The checks run in the order in which the
-// calls have always made them.
+// The four calls: llsm_gpu_batch_align_band with kBand and llsm_gpu_batch_align_band_slope with kBandSlope hold band planes,
+// else band is not read and the planes hold the whole matrix of every pair: llsm_gpu_batch_align with kAlign,
+// llsm_gpu_batch_align_slope with kSlope.  The checks run in the order in which the calls have always made them.
 int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, const char* who,
   const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  const bool banded = who == kBand, slope = who == kSlope;
+  const bool bslope = who == kBandSlope, banded = who == kBand || bslope, slope = who == kSlope;
   if(! a || ! b) return refuse("NULL batch", who);
   if(n_pairs < 0) return refuse("n_pairs < 0", who);
   if(a -> ctx != b -> ctx) return refuse("the batches belong to different contexts", who);
@@ -129,6 +193,18 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     align_slope_row(i0, q.na, q.nb, jlo, unused); align_slope_row(i1, q.na, q.nb, unused, jhi);
     return jhi - jlo + 1 + i1 - i0 + (i1 + 1 < q.na ? 1 : 0);
   };
+  // rule K1 for the same rows, from the pair's rows of the region: the least lo and the largest hi of the non-empty ones
+  // (k_align_band_slope_dtw takes them the same way), and the steps over them as above
+  std::vector<int2> table, region;                                  // the rows of the region of all pairs, and of one
+  auto band_slope_window = [&](const AlignPair& q, int i0) {
+    const int i1 = std::min(i0 + 63, q.na - 1);
+    int jlo = q.nb - 1, jhi = 0;
+    for(int i = i0; i <= i1; i ++) {
+      const int2 r = table[(size_t)q.pad + i];
+      if(r.x <= r.y) { jlo = std::min(jlo, r.x); jhi = std::max(jhi, r.y); }
+    }
+    return std::max(jhi - jlo, 0) + 1 + i1 - i0 + (i1 + 1 < q.na ? 1 : 0);
+  };
   auto tile_floor = [](int j) { return j >= 0 ? j / ALIGN_TILE * ALIGN_TILE : -((-j + ALIGN_TILE - 1) / ALIGN_TILE * ALIGN_TILE); };
   std::vector<AlignPair> pairs((size_t)n_pairs);
   long long cells = 0, rows = 0, frames = 0, steps = 0, n_tiles = 0;
@@ -140,17 +216,24 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     const int na = a -> nfrm[ua], nb = b -> nfrm[ub];
     if(na <= 0 || nb <= 0) return refuse(pair() + "an utterance without frames", who);
     if(bd < 0) return refuse(pair() + "band < 0", who);
-    const int least = banded ? band_min(na, nb) : 0;
+    const int least = banded && ! bslope ? band_min(na, nb) : 0;
     if(bd < least)
       return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
         std::to_string(nb) + " frames: llsm_gpu_align_band_min is " + std::to_string(least), who);
-    if(slope) {
+    if(slope || bslope) {
       const std::string bound = slope_bound(na, nb);
       if(! bound.empty()) return refuse(pair() + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound, who);
     }
+    // (a pair of the shape and band of the pair before it shares that pair's rows of the table: equal takes are common)
+    const bool as_before = bslope && p > 0 && na == pairs[p - 1].na && nb == pairs[p - 1].nb && bd == pairs[p - 1].band;
+    if(bslope && ! as_before && ! band_slope_rows(na, nb, bd, region))
+      return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for the slope pattern on " + std::to_string(na) +
+        " x " + std::to_string(nb) + " frames: llsm_gpu_align_band_slope_min is " + std::to_string(band_slope_min(na, nb)), who);
     AlignPair& q = pairs[p];
     q.a0 = a -> frm_off[ua]; q.na = na; q.b0 = b -> frm_off[ub]; q.nb = nb;
-    q.cell0 = (int)cells; q.row0 = (int)rows; q.pos0 = (int)frames; q.band = bd; q.mv0 = steps; q.pad = 0;
+    q.cell0 = (int)cells; q.row0 = (int)rows; q.pos0 = (int)frames; q.band = bd; q.mv0 = steps;
+    q.pad = as_before ? pairs[p - 1].pad : (int)table.size();       // where the pair's rows of the region start
+    if(bslope && ! as_before) table.insert(table.end(), region.begin(), region.end());
     cells += plane_cells(p);                                        // (checked below: the offsets above are only used if it fits)
     if(cells > kMaxCells) {                                         // the total of the whole list, for the message
       for(int r = p + 1; r < n_pairs && (! banded || cells < (1ll << 61)); r ++) cells += plane_cells(r);
@@ -162,13 +245,14 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     for(int i0 = 0, jlo, jhi; i0 < na; i0 += 64) {
       const int i1 = span(q, i0, jlo, jhi);
       n_tiles += (jhi - tile_floor(jlo)) / ALIGN_TILE + 1;
-      q.steps = std::max(q.steps, slope ? slope_window(q, i0, jlo, jhi) : std::min(jhi, nb - 1) - std::max(jlo, 0) + 1 + i1 - i0);
+      q.steps = std::max(q.steps, slope ? slope_window(q, i0, jlo, jhi) : bslope ? band_slope_window(q, i0) :
+                                  std::min(jhi, nb - 1) - std::max(jlo, 0) + 1 + i1 - i0);
     }
-    rows += slope ? 2ll * nb : nb; frames += na;
+    rows += slope || bslope ? 2ll * nb : nb; frames += na;
     steps += (long long)((na + 63) / 64) * q.steps;
   }
   // accepted: from here on this call's scratch on a changes (and the other call's, its plane among it, does not)
-  llsm_gpu_batch::AlignScratch& sc = banded ? a -> alb : slope ? a -> als : a -> al;
+  llsm_gpu_batch::AlignScratch& sc = bslope ? a -> albs : banded ? a -> alb : slope ? a -> als : a -> al;
   std::vector<int4> tiles; tiles.reserve((size_t)n_tiles);
   for(int p = 0; p < n_pairs; p ++)                                 // the tiles of the matrix that meet the rows' columns, overhang included
     for(int i0 = 0, jlo, jhi; i0 < pairs[p].na; i0 += ALIGN_TILE) {
@@ -178,12 +262,13 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   hipSetDevice(a -> ctx -> device);
   const size_t n_out = (size_t)frames + (size_t)n_pairs;
   if(sc.plane.alloc((size_t)cells) || sc.row.alloc((size_t)rows) || sc.out.alloc(n_out) || sc.moves.alloc((size_t)steps) ||
-     sc.pairs.alloc(pairs.size()) || sc.tiles.alloc(tiles.size())) return -1;
+     sc.pairs.alloc(pairs.size()) || sc.tiles.alloc(tiles.size()) || sc.region.alloc(table.size())) return -1;
   sc.cells = 0;                                                     // the planes are being rewritten
   LaunchCtx* P = & a -> ctx -> lc;
   // (pageable sources: the copies have left the vectors when the calls return, and run in stream order)
   HIP_OK(hipMemcpyAsync(sc.pairs.p, pairs.data(), pairs.size() * sizeof(AlignPair), hipMemcpyHostToDevice, P -> stream));
   HIP_OK(hipMemcpyAsync(sc.tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, P -> stream));
+  if(bslope) HIP_OK(hipMemcpyAsync(sc.region.p, table.data(), table.size() * sizeof(int2), hipMemcpyHostToDevice, P -> stream));
   AlignDev d;
   d.code_a = (const float*)a -> arr[LLSM_GPU_CODE]; d.code_b = (const float*)b -> arr[LLSM_GPU_CODE];
   d.dim = a -> coder_os + a -> coder_ob + 3; d.first = o.first; d.count = o.count;
@@ -191,6 +276,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   d.pairs = sc.pairs.p; d.n_pairs = n_pairs;
   int rc = launch_align_dist(P, banded, d, sc.tiles.p, (int)tiles.size(), sc.plane.p);
   if(! rc) rc = slope ? launch_align_slope_dtw(P, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
+             : bslope ? launch_align_band_slope_dtw(P, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
                       : launch_align_dtw(P, banded, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames);
   if(rc) return refuse(std::string("launch failed: ") + hipGetErrorString((hipError_t)rc), who);
   // into memory of our own first: a failed copy leaves pos and cost untouched
@@ -253,4 +339,46 @@ extern "C" int llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi) {
 extern "C" int llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
   return align_run(a, b, n_pairs, utt_a, utt_b, kSlope, nullptr, opt, pos, cost);
+}
+
+// ---------------------------------------------------------------- the slope pattern inside the band (rules K1 - K4)
+namespace {
+// empty, or why a pair is refused by the two host calls below
+std::string band_slope_pair(int na, int nb) {
+  if(na < 1 || nb < 1) return "na < 1 or nb < 1 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ")";
+  const std::string bound = slope_bound(na, nb);
+  if(! bound.empty()) return std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound;
+  // (the sweeps hold a few words per row; a pair of more rows than a call has cells fits no call)
+  return na > kMaxCells ? "na = " + std::to_string(na) + " exceeds 2^28, the cells of a call" : "";
+}
+}  // namespace
+
+extern "C" int llsm_gpu_align_band_slope_min(int na, int nb) {
+  const std::string why = band_slope_pair(na, nb);
+  if(! why.empty()) return refuse(why, "llsm_gpu_align_band_slope_min");
+  try { return band_slope_min(na, nb); }                            // (the sweeps hold a few words per row)
+  catch(const std::bad_alloc&) { return refuse("out of memory for " + std::to_string(na) + " rows", "llsm_gpu_align_band_slope_min"); }
+}
+
+extern "C" int llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo, int* hi) {
+  const char* who = "llsm_gpu_align_band_slope_rows";
+  const std::string why = band_slope_pair(na, nb);
+  if(! why.empty()) return refuse(why, who);
+  if(band < 0) return refuse("band < 0 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ", band = " + std::to_string(band) + ")", who);
+  std::vector<int2> rows;
+  try {
+    if(! band_slope_rows(na, nb, band, rows))
+      return refuse("a band of " + std::to_string(band) + " is not connected for the slope pattern on " + std::to_string(na) + " x " +
+        std::to_string(nb) + " frames: llsm_gpu_align_band_slope_min is " + std::to_string(band_slope_min(na, nb)), who);
+  } catch(const std::bad_alloc&) { return refuse("out of memory for " + std::to_string(na) + " rows", who); }
+  for(int i = 0; i < na && (lo || hi); i ++) {
+    if(lo) lo[i] = rows[i].x;
+    if(hi) hi[i] = rows[i].y;
+  }
+  return 0;
+}
+
+extern "C" int llsm_gpu_batch_align_band_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
+  const int* utt_b, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
+  return align_run(a, b, n_pairs, utt_a, utt_b, kBandSlope, band, opt, pos, cost);
 }

@@ -332,8 +332,8 @@ int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);
 // rules T2 - T5 over the candidate plane: f0[nframes]; bp: one word per frame of scratch
 int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0);
 
-// ---- alignment of utterance pairs: whole matrix, inside a diagonal band, or whole matrix under the slope pattern (align.cpp,
-// align_kernels.hip; rules D1 - D3, B1 - B4 and L1 - L4: llsm_gpu.h)
+// ---- alignment of utterance pairs: whole matrix, inside a diagonal band, whole matrix under the slope pattern, or the slope
+// pattern inside the band (align.cpp, align_kernels.hip; rules D1 - D3, B1 - B4, L1 - L4 and K1 - K4: llsm_gpu.h)
 // The centre column of row i of an na x nb pair, rule B1: the diagonal rounded half up.  Row i spans columns
 // max(0, c - band) ... min(nb - 1, c + band); entry q of its row of the band plane is column c - band + q.
 __host__ __device__ static inline int align_band_center(int i, int na, int nb) {
@@ -350,7 +350,8 @@ __host__ __device__ static inline void align_slope_row(long long i, int na, int 
 // or [na][2 band + 1] of a banded call -- starts at float cell0 of the planes, its moves at entry mv0 (`steps` entries of
 // 16 bytes per strip of 64 rows: the anti-diagonals of the strip whose column window is the widest), its hand-over row
 // (two rows of nb floats under the slope pattern) at float row0, its positions at float pos0 of the out block.  band is 0
-// and not read where the whole matrix is searched.
+// and not read where the whole matrix is searched.  pad is 0 except for llsm_gpu_batch_align_band_slope, where the pair's rows
+// of the region (rule K1) start at entry pad of the table.
 struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
 #define ALIGN_TILE 64                                  // k_align_dist_t: cells per side of a workgroup's tile
 struct AlignDev {
@@ -364,6 +365,10 @@ int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* ti
 int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
 // L3 - L4 over whole-matrix planes, one wavefront per pair; row: two hand-over rows of nb floats per pair, out as above
 int launch_align_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
+// K3 - K4 over band planes, one wavefront per pair; region: {lo, hi} of every row of every pair (an empty row: lo > hi), pair p's
+// from entry pairs[p].pad; row: two hand-over rows of nb floats per pair, out as above
+int launch_align_band_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, const int2* region, uint4* moves, float* row,
+  float* out, int cost0);
 
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5 and C1 - C6: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame
