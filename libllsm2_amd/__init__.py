@@ -782,70 +782,45 @@ class Batch:
         _check(self.L.llsm_gpu_batch_decode(self.h, int(use_layer1)), "decode")
 
     # ---- alignment (llsm_gpu.h): LLSM_GPU_CODE of two batches -> positions for splice and path costs
+    def _align(self, call, name, other, utt_a, utt_b, band, options):
+        """the four alignment calls: `call` of the library under `name`, with one band per pair unless band is None"""
+        o = make_align_options(**options)
+        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
+        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
+        bands = () if band is None else (np.ascontiguousarray(np.broadcast_to(np.asarray(band, np.int32), ua.shape)),)
+        nfrm = np.diff(self.frm_off)
+        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
+        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        _check(call(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                    *(bd.ctypes.data_as(P_int) for bd in bands), C.byref(o), pos.ctypes.data_as(P_fp),
+                    cost.ctypes.data_as(P_fp)), name)
+        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+
     def align(self, other, utt_a, utt_b, **options):
         """one minimum-cost monotonic path per pair (utterance utt_a[p] of this batch, utterance utt_b[p] of batch
         `other`) through the distances of their coder vectors (llsm_gpu_batch_align); options: the members of
         llsm_gpu_align_options, defaults where not given.  Returns (a list with one float32 array per pair: for every
         frame of the utterance of this batch its position in frames of the other utterance, as splice takes it; the
         float32 array of the path costs)"""
-        o = make_align_options(**options)
-        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
-        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
-        nfrm = np.diff(self.frm_off)
-        inside = ua[(ua >= 0) & (ua < len(nfrm))]                   # (an index outside is the library's to refuse)
-        na = np.zeros(len(ua), np.int64); na[(ua >= 0) & (ua < len(nfrm))] = nfrm[inside]
-        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
-        _check(self.L.llsm_gpu_batch_align(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
-                                           C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align")
-        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+        return self._align(self.L.llsm_gpu_batch_align, "align", other, utt_a, utt_b, None, options)
 
     def align_band(self, other, utt_a, utt_b, band, **options):
         """align within `band` columns of the straight diagonal (llsm_gpu_batch_align_band): what long utterances need,
         whose full matrices align refuses.  band: an int, or one int per pair.  Returns what align returns"""
-        o = make_align_options(**options)
-        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
-        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
-        bd = np.ascontiguousarray(np.broadcast_to(np.asarray(band, np.int32), ua.shape))
-        nfrm = np.diff(self.frm_off)
-        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
-        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
-        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
-        _check(self.L.llsm_gpu_batch_align_band(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
-                                                bd.ctypes.data_as(P_int), C.byref(o), pos.ctypes.data_as(P_fp),
-                                                cost.ctypes.data_as(P_fp)), "align_band")
-        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+        return self._align(self.L.llsm_gpu_batch_align_band, "align_band", other, utt_a, utt_b, band, options)
 
     def align_slope(self, other, utt_a, utt_b, **options):
         """align with the local slope of the path held within [1/2, 2] (llsm_gpu_batch_align_slope): no frame of either
         utterance is held for more than two frames of the other, none is skipped.  Pairs outside nb - 1 <= 2 (na - 1),
         na - 1 <= 2 (nb - 1) are refused.  Returns what align returns"""
-        o = make_align_options(**options)
-        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
-        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
-        nfrm = np.diff(self.frm_off)
-        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
-        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
-        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
-        _check(self.L.llsm_gpu_batch_align_slope(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
-                                                 C.byref(o), pos.ctypes.data_as(P_fp), cost.ctypes.data_as(P_fp)), "align_slope")
-        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+        return self._align(self.L.llsm_gpu_batch_align_slope, "align_slope", other, utt_a, utt_b, None, options)
 
     def align_band_slope(self, other, utt_a, utt_b, band, **options):
         """align_slope within `band` columns of the straight diagonal (llsm_gpu_batch_align_band_slope): slopes within
         [1/2, 2] for utterances whose full matrices align_slope refuses.  band: an int, or one int per pair; a pair that
         align_slope refuses and a band below align_band_slope_min of the pair are refused.  Returns what align_band returns"""
-        o = make_align_options(**options)
-        ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
-        assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
-        bd = np.ascontiguousarray(np.broadcast_to(np.asarray(band, np.int32), ua.shape))
-        nfrm = np.diff(self.frm_off)
-        inside = (ua >= 0) & (ua < len(nfrm))                       # (an index outside is the library's to refuse)
-        na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
-        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
-        _check(self.L.llsm_gpu_batch_align_band_slope(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
-                                                      bd.ctypes.data_as(P_int), C.byref(o), pos.ctypes.data_as(P_fp),
-                                                      cost.ctypes.data_as(P_fp)), "align_band_slope")
-        return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
+        return self._align(self.L.llsm_gpu_batch_align_band_slope, "align_band_slope", other, utt_a, utt_b, band, options)
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders
     def select(self, bank, opt=None, **options):

@@ -11,15 +11,16 @@
 //   llsm_gpu_align_slope_rows        host only: whether a pair is admissible under the slope pattern and the column range of
 //                                    every row (rule L1)
 //   llsm_gpu_batch_align_slope       the whole planes again, and a path whose local slope stays within [1/2, 2] (rules L1 -
-//                                    L4, DESIGN.md section 27: k_align_slope_dtw), with scratch of its own
+//                                    L4, DESIGN.md section 27: k_align_slope_dtw_t<false>), with scratch of its own
 //   llsm_gpu_align_band_slope_min / _rows   host only: the least band that is connected for the slope pattern, and the
 //                                    column range of every row of the region (rule K1: two integer sweeps over intervals)
 //   llsm_gpu_batch_align_band_slope  the slope pattern inside the band (rules K1 - K4, DESIGN.md section 28: the band planes
-//                                    of k_align_band_dist, the region's rows as a table, k_align_band_slope_dtw), with
+//                                    of k_align_band_dist, the region's rows as a table, k_align_slope_dtw_t<true>), with
 //                                    scratch of its own
 //
-// The four calls are one function, align_run.  Every check runs before anything is allocated, copied or launched.  The
-// scratch lives on batch a, grow-only.
+// The four calls are one function, align_run, told apart by an AlignMode of two bits (band, slope: batch.h): the name in the
+// messages, the scratch set, the steps of a strip (strip_steps) and the kernel instantiations follow from it.  Every check
+// runs before anything is allocated, copied or launched.  The scratch lives on batch a, grow-only, one set per mode.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,10 +32,7 @@
 #include "batch.h"
 
 namespace {
-const char* kAlign = "llsm_gpu_batch_align";
-const char* kBand = "llsm_gpu_batch_align_band";
-const char* kSlope = "llsm_gpu_batch_align_slope";
-const char* kBandSlope = "llsm_gpu_batch_align_band_slope";
+const char* const kAlign = kAlignCalls[ALIGN_FULL].name;            // in whose name llsm_gpu_align_check refuses
 const long long kMaxCells = 1ll << 28;
 
 int refuse(const std::string& why, const char* who = kAlign) { llsm_set_error(std::string(who) + ": " + why); return -1; }
@@ -147,12 +145,43 @@ extern "C" int llsm_gpu_align_check(const llsm_gpu_align_options* opt, int order
 namespace {
 static_assert(ALIGN_TILE == 64, "a row of tiles of the distance kernel is a strip of 64 rows of the path kernel");
 
-// The four calls: llsm_gpu_batch_align_band with kBand and llsm_gpu_batch_align_band_slope with kBandSlope hold band planes,
-// else band is not read and the planes hold the whole matrix of every pair: llsm_gpu_batch_align with kAlign,
-// llsm_gpu_batch_align_slope with kSlope.  The checks run in the order in which the calls have always made them.
-int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, const char* who,
+int tile_floor(int j) { return j >= 0 ? j / ALIGN_TILE * ALIGN_TILE : -((-j + ALIGN_TILE - 1) / ALIGN_TILE * ALIGN_TILE); }
+
+// rows [i0, i0 + 63] of a pair, a strip of the path kernels and a row of tiles of the distance kernel: the first column of
+// its first row and the last of its last as the plane stores them (under a band they may lie outside the matrix).  Returns
+// the last row.
+int strip_span(bool banded, const AlignPair& q, int i0, int& jlo, int& jhi) {
+  const int i1 = std::min(i0 + 63, q.na - 1);
+  jlo = banded ? align_band_center(i0, q.na, q.nb) - q.band : 0;
+  jhi = banded ? align_band_center(i1, q.na, q.nb) + q.band : q.nb - 1;
+  return i1;
+}
+
+// The steps the path kernel of `mode` takes over the same rows: the anti-diagonals of the strip's column window [jlo, jhi],
+// which each kernel finds the same way.  Without the slope pattern the window is the span within the matrix.  Under it a
+// strip that has a successor takes one step more, as the first row of the successor may be entered past column jhi, and
+// the window is, by rule L1, lo of the first row and hi of the last (neither decreases with the row), or inside a band, by
+// rule K1, the least lo and the largest hi of the non-empty rows among the pair's rows of the region, `region`.
+int strip_steps(int mode, const AlignPair& q, int i0, const int2* region) {
+  int jlo, jhi, unused;
+  const int i1 = strip_span(mode & ALIGN_BAND, q, i0, jlo, jhi);
+  if(! (mode & ALIGN_SLOPE)) { jlo = std::max(jlo, 0); jhi = std::min(jhi, q.nb - 1); }
+  else if(mode & ALIGN_BAND) {
+    jlo = q.nb - 1; jhi = 0;
+    for(int i = i0; i <= i1; i ++)
+      if(region[i].x <= region[i].y) { jlo = std::min(jlo, region[i].x); jhi = std::max(jhi, region[i].y); }
+  } else { align_slope_row(i0, q.na, q.nb, jlo, unused); align_slope_row(i1, q.na, q.nb, unused, jhi); }
+  // (jhi < jlo takes a strip whose rows are all empty, which a connected band does not have)
+  return std::max(jhi - jlo, 0) + 1 + i1 - i0 + ((mode & ALIGN_SLOPE) && i1 + 1 < q.na ? 1 : 0);
+}
+
+// The four calls, told apart by `mode` (AlignMode: batch.h): the name the messages carry and the scratch set on a follow
+// from it.  With ALIGN_BAND the planes are band planes, else band is not read and the planes hold the whole matrix of every
+// pair.  The checks run in the order in which the calls have always made them.
+int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, int mode,
   const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  const bool bslope = who == kBandSlope, banded = who == kBand || bslope, slope = who == kSlope;
+  const bool banded = mode & ALIGN_BAND, slope = mode & ALIGN_SLOPE, bslope = banded && slope;
+  const char* who = kAlignCalls[mode].name;
   if(! a || ! b) return refuse("NULL batch", who);
   if(n_pairs < 0) return refuse("n_pairs < 0", who);
   if(a -> ctx != b -> ctx) return refuse("the batches belong to different contexts", who);
@@ -176,36 +205,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     if(banded) return std::min(na * (2ll * std::max(band[r], 0) + 1), 1ll << 61);
     return ub < 0 || ub >= b -> lay.n_utt ? 0 : na * std::max(b -> nfrm[ub], 0);
   };
-  // rows [i0, i0 + 63] of a pair, a strip of the path kernel and a row of tiles of the distance kernel: the first column
-  // of its first row and the last of its last as the plane stores them (under a band they may lie outside the matrix; the
-  // slope pattern stores whole rows and walks the window of slope_window below)
-  auto span = [&](const AlignPair& q, int i0, int& jlo, int& jhi) {
-    const int i1 = std::min(i0 + 63, q.na - 1);
-    jlo = banded ? align_band_center(i0, q.na, q.nb) - q.band : 0;
-    jhi = banded ? align_band_center(i1, q.na, q.nb) + q.band : q.nb - 1;
-    return i1;
-  };
-  // rule L1 for the same rows: lo of the first and hi of the last (neither decreases with the row), and the steps
-  // k_align_slope_dtw takes over them: one more where a strip follows, whose first row may be entered past column jhi
-  auto slope_window = [&](const AlignPair& q, int i0, int& jlo, int& jhi) {
-    const int i1 = std::min(i0 + 63, q.na - 1);
-    int unused;
-    align_slope_row(i0, q.na, q.nb, jlo, unused); align_slope_row(i1, q.na, q.nb, unused, jhi);
-    return jhi - jlo + 1 + i1 - i0 + (i1 + 1 < q.na ? 1 : 0);
-  };
-  // rule K1 for the same rows, from the pair's rows of the region: the least lo and the largest hi of the non-empty ones
-  // (k_align_band_slope_dtw takes them the same way), and the steps over them as above
-  std::vector<int2> table, region;                                  // the rows of the region of all pairs, and of one
-  auto band_slope_window = [&](const AlignPair& q, int i0) {
-    const int i1 = std::min(i0 + 63, q.na - 1);
-    int jlo = q.nb - 1, jhi = 0;
-    for(int i = i0; i <= i1; i ++) {
-      const int2 r = table[(size_t)q.pad + i];
-      if(r.x <= r.y) { jlo = std::min(jlo, r.x); jhi = std::max(jhi, r.y); }
-    }
-    return std::max(jhi - jlo, 0) + 1 + i1 - i0 + (i1 + 1 < q.na ? 1 : 0);
-  };
-  auto tile_floor = [](int j) { return j >= 0 ? j / ALIGN_TILE * ALIGN_TILE : -((-j + ALIGN_TILE - 1) / ALIGN_TILE * ALIGN_TILE); };
+  std::vector<int2> table, region;                                  // rule K1: the rows of the region of all pairs, and of one
   std::vector<AlignPair> pairs((size_t)n_pairs);
   long long cells = 0, rows = 0, frames = 0, steps = 0, n_tiles = 0;
   for(int p = 0; p < n_pairs; p ++) {
@@ -216,11 +216,11 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     const int na = a -> nfrm[ua], nb = b -> nfrm[ub];
     if(na <= 0 || nb <= 0) return refuse(pair() + "an utterance without frames", who);
     if(bd < 0) return refuse(pair() + "band < 0", who);
-    const int least = banded && ! bslope ? band_min(na, nb) : 0;
+    const int least = banded && ! slope ? band_min(na, nb) : 0;
     if(bd < least)
       return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
         std::to_string(nb) + " frames: llsm_gpu_align_band_min is " + std::to_string(least), who);
-    if(slope || bslope) {
+    if(slope) {
       const std::string bound = slope_bound(na, nb);
       if(! bound.empty()) return refuse(pair() + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound, who);
     }
@@ -243,20 +243,19 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     // the moves of a strip: one entry per anti-diagonal of its column window, as many as the widest strip of the pair has
     q.steps = 0;
     for(int i0 = 0, jlo, jhi; i0 < na; i0 += 64) {
-      const int i1 = span(q, i0, jlo, jhi);
+      strip_span(banded, q, i0, jlo, jhi);
       n_tiles += (jhi - tile_floor(jlo)) / ALIGN_TILE + 1;
-      q.steps = std::max(q.steps, slope ? slope_window(q, i0, jlo, jhi) : bslope ? band_slope_window(q, i0) :
-                                  std::min(jhi, nb - 1) - std::max(jlo, 0) + 1 + i1 - i0);
+      q.steps = std::max(q.steps, strip_steps(mode, q, i0, table.data() + q.pad));
     }
-    rows += slope || bslope ? 2ll * nb : nb; frames += na;
+    rows += slope ? 2ll * nb : nb; frames += na;
     steps += (long long)((na + 63) / 64) * q.steps;
   }
   // accepted: from here on this call's scratch on a changes (and the other call's, its plane among it, does not)
-  llsm_gpu_batch::AlignScratch& sc = bslope ? a -> albs : banded ? a -> alb : slope ? a -> als : a -> al;
+  llsm_gpu_batch::AlignScratch& sc = a -> align[mode];
   std::vector<int4> tiles; tiles.reserve((size_t)n_tiles);
   for(int p = 0; p < n_pairs; p ++)                                 // the tiles of the matrix that meet the rows' columns, overhang included
     for(int i0 = 0, jlo, jhi; i0 < pairs[p].na; i0 += ALIGN_TILE) {
-      span(pairs[p], i0, jlo, jhi);
+      strip_span(banded, pairs[p], i0, jlo, jhi);
       for(int j0 = tile_floor(jlo); j0 <= jhi; j0 += ALIGN_TILE) tiles.push_back(make_int4(p, i0, j0, 0));
     }
   hipSetDevice(a -> ctx -> device);
@@ -275,8 +274,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   d.step_cost = o.step_cost; d.voicing_cost = o.voicing_cost;
   d.pairs = sc.pairs.p; d.n_pairs = n_pairs;
   int rc = launch_align_dist(P, banded, d, sc.tiles.p, (int)tiles.size(), sc.plane.p);
-  if(! rc) rc = slope ? launch_align_slope_dtw(P, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
-             : bslope ? launch_align_band_slope_dtw(P, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
+  if(! rc) rc = slope ? launch_align_slope_dtw(P, banded, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
                       : launch_align_dtw(P, banded, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames);
   if(rc) return refuse(std::string("launch failed: ") + hipGetErrorString((hipError_t)rc), who);
   // into memory of our own first: a failed copy leaves pos and cost untouched
@@ -292,7 +290,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
 
 extern "C" int llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, kAlign, nullptr, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_FULL, nullptr, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- inside a diagonal band (rules B1 - B4)
@@ -319,7 +317,7 @@ extern "C" int llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* 
 
 extern "C" int llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, kBand, band, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_BAND, band, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- local slopes within [1/2, 2] (rules L1 - L4)
@@ -338,7 +336,7 @@ extern "C" int llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi) {
 
 extern "C" int llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, kSlope, nullptr, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_SLOPE, nullptr, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- the slope pattern inside the band (rules K1 - K4)
@@ -380,5 +378,5 @@ extern "C" int llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo,
 
 extern "C" int llsm_gpu_batch_align_band_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, kBandSlope, band, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_BAND | ALIGN_SLOPE, band, opt, pos, cost);
 }

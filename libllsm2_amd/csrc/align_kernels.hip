@@ -1,8 +1,8 @@
 // align_kernels.hip -- alignment of utterance pairs: llsm_gpu_batch_align (rules D1 - D3: llsm_gpu.h),
-// llsm_gpu_batch_align_band (rules B1 - B4, section 25) and llsm_gpu_batch_align_slope (rules L1 - L4, section 27; its path
-// kernel k_align_slope_dtw is described above it, its planes are k_align_dist_t's full ones) and
-// llsm_gpu_batch_align_band_slope (rules K1 - K4, section 28; its path kernel k_align_band_slope_dtw is described above it, its
-// planes are k_align_dist_t's band ones); host side: align.cpp.  Two kernel templates, each instantiated for the two geometries:
+// llsm_gpu_batch_align_band (rules B1 - B4, section 25), llsm_gpu_batch_align_slope (rules L1 - L4, section 27; its planes are
+// k_align_dist_t's full ones) and llsm_gpu_batch_align_band_slope (rules K1 - K4, section 28; its planes are k_align_dist_t's
+// band ones); the path kernel of the last two, k_align_slope_dtw_t, is described above it; host side: align.cpp.  Three kernel
+// templates, each instantiated for the two geometries:
 //   full    row i spans columns 0 ... nb - 1 and is stored as it is: off = 0, width = nb, all of it known when compiling
 //   band    row i spans lo_i = max(off_i, 0) ... hi_i = min(off_i + 2 band, nb - 1), off_i = align_band_center(i) - band, and
 //           entry q of its row of the plane [na][width = 2 band + 1] is column off_i + q
@@ -281,46 +281,81 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
   if(lane == 0) pos[0] = __fmul_rn((float)(0 + hi), 0.5f);
 }
 
-// ---------------------------------------------------------------- L3 - L4: the path under the slope pattern
-// The layout of k_align_dtw_t over whole-matrix planes: lane l on row i = 64 s + l, on column j = wlo + t - l at step t, the
-// strip's window [wlo, whi] = [lo of its first row, hi of its last] (rule L1; lo and hi do not decrease with i, so the
-// window holds every row's range).  What a lane holds when it reaches (i, j):
+// ---------------------------------------------------------------- L3 - L4 / K3 - K4: the path under the slope pattern
+// k_align_slope_dtw_t<BAND>: <false> over whole-matrix planes (rules L1 - L4), <true> over band planes (rules K1 - K4).  The
+// layout of k_align_dtw_t: lane l on row i = 64 s + l, on column j = wlo + t - l at step t of the strip's window [wlo, whi],
+// which holds the range [lo_i, hi_i] of every row of the strip.  What a lane holds when it reaches (i, j):
 //   diag   acc[i-1][j-1], the `up` it received one step ago: move 0
 //   qi     (acc[i-2][j-1] + D[i-1][j]) + step_cost, which the lane above formed one step ago on (i - 1, j): move 1.  It comes
-//          with a second wavefront shift; lane 0 takes it from the second hand-over row
+//          with a second wavefront shift (DPP); lane 0 takes it from the second hand-over row
 //   qo     (acc[i-1][j-2] + D[i][j-1]) + step_cost, which the lane formed itself one step ago on (i, j - 1): move 2
 // and one sum serves the last two: through (i, j) from (i - 1, j - 1) the path goes on to (i, j + 1) by move 2 or to
 // (i + 1, j) by move 1, and either candidate is (diag + D[i][j]) + step_cost.  A lane forms it on every cell it passes,
-// inside its row's range or not: the cell between the two ends of a move need not lie in the region, and whether a
-// candidate exists is decided where it is used, by integer comparisons of j with the ranges of rows i - 1 and i - 2, so what
-// a lane outside its range, an earlier strip or unwritten memory left behind is never used.
+// inside its row's range or not, because the cell between the two ends of an allowed move need not lie in the region.
+// Whether a candidate exists is decided where it is used, by integer comparisons of j with three ranges a lane sets up once
+// per strip ([a0, b0] for move 0, [a1, b1] for move 1, j - 1 in [c0, b0] for move 2), never by the values: so what a lane
+// outside its range, an earlier strip or unwritten memory left in a register or in the hand-over rows is never used.  The
+// moves of a step are two ballots, stored as k_align_dtw_t stores them.
 // Hand-over: lane 63 leaves acc[i][j] in the first row and that sum in the second, both indexed by the column, for lane 0 of
-// the next strip.  The sum is needed one column past whi, where a move 1 into row i + 1 passes (i, hi_i + 1), so a strip
-// that has a successor takes one step more.  Lane 0 starts a strip on column wlo with diag = acc[i-1][wlo-1] and, for a move
-// 2 from (i - 1, wlo - 2), qo = (acc[i-1][wlo-2] + D[i][wlo-1]) + step_cost, both from the first row before the loop.  All
-// lanes count their steps from the same wlo: lane 0 loads column x of either row at step x - wlo at the latest and lane 63
-// stores column x at step x - wlo + 63, so the reads stay ahead of the writes by 63 steps however narrow the window is;
-// the loads past the window's end are clamped to column nb - 1 and not used.
-// The walk back reads the masks as k_align_dtw_t does.  Every move leaves its row, so pos[i] follows from the cell and the
-// move: columns j - 1 and j under move 2, else j alone; move 1 passes (i - 1, j) and nothing else of row i - 1.  Each move
-// lowers i and j by one at the least: at most min(na, nb) - 1 moves.
+// the next strip.  The sum is needed one column past whi, where a move 1 into row i + 1 at column j passes (i, j) with
+// j <= whi + 1 (its other end (i - 1, j - 1) is in the region), so a strip that has a successor takes one step more.  Lane 0
+// starts a strip on column wlo with diag = acc[i-1][wlo-1] and, for a move 2 from (i - 1, wlo - 2), qo = (acc[i-1][wlo-2] +
+// D[i][wlo-1]) + step_cost, both from the first row before the loop; it meets no cell of the region left of wlo.
+// Reads stay 63 steps ahead of the writes, whatever the window.  Every lane of a strip counts its steps from the strip's own
+// wlo.  Lane 0 is on column x at step x - wlo and loads entry x of either row then at the latest (DTW_U to 2 DTW_U - 1 steps
+// earlier in fact, and entries wlo - 1 and wlo - 2 before the first step); lane 63 is on column x at step x - wlo + 63 and
+// stores entry x then.  So whatever whi - wlo is -- 0 under band 0, where lane 0 has left the window before lane 63 stores
+// anything, or 140 and more under band 70, where lane 0 is still reading column wlo + 100 while lane 63 stores column wlo +
+// 37 -- entry x is read at least 63 steps before it is overwritten, and one wavefront runs its steps in program order.
+// Loads of columns past nb - 1 are clamped to nb - 1; they may see the new value, and are not used.
+// The walk back reads the masks as k_align_dtw_t does, finding a strip's wlo again as the forward pass found it.  Every move
+// leaves its row, so pos[i] follows from the cell and the move: columns j - 1 and j under move 2, else j alone; move 1 passes
+// (i - 1, j) and nothing else of row i - 1.  Each move lowers i and j by one at the least: at most min(na, nb) - 1 moves.
+// What BAND changes, each under `if constexpr`:
+//   rows     <false> rule L1 from align_slope_row for rows i, i - 1 and i - 2; the ranges of rows i - 1 and i - 2 moved one
+//            column right are [a0, b0] and [a1, b1], and c0 is a0.  <true> the region's rows (rule K1) from the host's table,
+//            one {lo, hi} per row, an empty row lo > hi, loaded for the same three rows once per strip, and the band's rows
+//            p ... q from align_band_center; K3's comparisons fold into the three ranges: move 0 needs j - 1 in row i - 1 of
+//            the region; move 1 needs j - 1 in row i - 2 of the region and j in row i - 1 of the band; move 2 needs j - 2 in
+//            row i - 1 of the region and j - 1 >= p_i (j - 1 <= q_i follows from j being in the region).  On a cell outside
+//            the band the sum above holds +infinity or a clamped read, and no candidate uses it: those comparisons ask for
+//            the passed cell to be in the band.
+//   window   <false> [lo of the strip's first row, hi of its last]: lo and hi do not decrease with i, two __shfl.  <true> the
+//            least lo and the largest hi of the strip's non-empty rows (band_slope_window, a wavefront reduction), and no
+//            steps if every row is empty.  Over the non-empty rows of a connected band lo and hi do not decrease and no two
+//            consecutive rows are empty (rule K1, measured), so a strip has a non-empty row.
+//   D        <false> entry j of a row of nb, all known when compiling.  <true> entry j - (c_i - band) of a row of 2 band + 1,
+//            clamped to the row.
+// <false> does not read `region`.
 struct SlopeBlock { float d[DTW_U], p[DTW_U], q[DTW_U]; };
-// as dtw_load<false>, with the second hand-over row beside the first
-DEV void slope_load(SlopeBlock& b, const float* __restrict__ drow, const float* hand, const float* handq, int j0, int lane, int nb) {
+// as dtw_load<false>, with the second hand-over row beside the first; D is entry q = column - off of a row of `width` (full:
+// off is 0 and not subtracted -- with `- off` in the text the compiler orders the 16 add / max pairs of the D index otherwise)
+template <bool BAND>
+DEV void slope_load(SlopeBlock& b, const float* __restrict__ drow, const float* hand, const float* handq, int j0, int lane,
+  int off, int width, int nb) {
 #pragma unroll
   for(int k = 0; k < DTW_U; k ++) {
     const int x = min(max(j0 + lane + k, 0), nb - 1);
-    b.d[k] = drow[min(max(j0 + k, 0), nb - 1)];
+    b.d[k] = drow[min(max(BAND ? j0 + k - off : j0 + k, 0), width - 1)];
     b.p[k] = hand[x]; b.q[k] = handq[x];
   }
 }
 
-__global__ __launch_bounds__(WAVE) void k_align_slope_dtw(AlignDev d, const float* __restrict__ plane, uint4* __restrict__ moves,
-  float* hand_rows, float* __restrict__ out, int cost0) {
+// [wlo, whi] of a strip from the range of each lane's row ((1, 0): empty or no row); whi < wlo if every row is empty
+DEV void band_slope_window(int lo, int hi, int nb, int& wlo, int& whi) {
+  wlo = lo <= hi ? lo : nb - 1; whi = lo <= hi ? hi : 0;
+#pragma unroll
+  for(int o = WAVE / 2; o > 0; o >>= 1) { wlo = min(wlo, __shfl_xor(wlo, o)); whi = max(whi, __shfl_xor(whi, o)); }
+}
+
+template <bool BAND>
+__global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const float* __restrict__ plane,
+  const int2* __restrict__ region, uint4* __restrict__ moves, float* hand_rows, float* __restrict__ out, int cost0) {
   const int lane = threadIdx.x;
   const AlignPair p = d.pairs[blockIdx.x];
-  const int na = p.na, nb = p.nb;
+  const int na = p.na, nb = p.nb, band = p.band, width = BAND ? 2 * band + 1 : nb;
   const float* D = plane + (size_t)p.cell0;
+  const int2* tab = BAND ? region + p.pad : nullptr;
   float* hand = hand_rows + (size_t)p.row0;
   float* handq = hand + nb;
   uint4* mv = moves + p.mv0;
@@ -331,35 +366,60 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw(AlignDev d, const floa
   for(int s = 0; s < nstrips; s ++) {
     const int i = s * WAVE + lane, rows = min(WAVE, na - s * WAVE);
     const bool more = s + 1 < nstrips;
-    // the range of this lane's row; the columns j for which (i - 1, j - 1) and (i - 2, j - 1) lie in the region; empty
-    // ranges (1, 0) where there is no such row
-    int lo = 1, hi = 0, a0 = 1, b0 = 0, a1 = 1, b1 = 0;
-    if(i < na) {
-      align_slope_row(i, na, nb, lo, hi);
-      if(i >= 1) { align_slope_row(i - 1, na, nb, a0, b0); a0 ++; b0 ++; }
-      if(i >= 2) { align_slope_row(i - 2, na, nb, a1, b1); a1 ++; b1 ++; }
+    // the range of this lane's row of the region, and the columns j for which move 0, 1 and 2 have a candidate: [a0, b0],
+    // [a1, b1], and j - 1 in [c0, b0]; empty ranges (1, 0) where there is no such row
+    int off = 0, lo = 1, hi = 0, a0 = 1, b0 = 0, a1 = 1, b1 = 0, c0 = 1;
+    if constexpr(BAND) {
+      if(i < na) {
+        const int2 r = tab[i];
+        const int c = align_band_center(i, na, nb);
+        lo = r.x; hi = r.y; off = c - band;
+        if(i >= 1) {
+          const int2 r1 = tab[i - 1];
+          a0 = r1.x + 1; b0 = r1.y + 1; c0 = max(a0, max(off, 0));
+        }
+        if(i >= 2) {
+          const int2 r2 = tab[i - 2];
+          const int cp = align_band_center(i - 1, na, nb);
+          a1 = max(r2.x + 1, max(cp - band, 0)); b1 = min(r2.y + 1, min(cp + band, nb - 1));
+        }
+      }
+    } else {
+      if(i < na) {
+        align_slope_row(i, na, nb, lo, hi);
+        if(i >= 1) { align_slope_row(i - 1, na, nb, a0, b0); a0 ++; b0 ++; }
+        if(i >= 2) { align_slope_row(i - 2, na, nb, a1, b1); a1 ++; b1 ++; }
+      }
+      c0 = a0;
     }
-    const int wlo = __shfl(lo, 0), whi = __shfl(hi, rows - 1), nsteps = whi - wlo + rows + (more ? 1 : 0);
-    const float* drow = D + (size_t)min(i, na - 1) * nb;
+    int wlo, whi, nsteps;
+    if constexpr(BAND) {
+      band_slope_window(lo, hi, nb, wlo, whi);
+      nsteps = whi >= wlo ? whi - wlo + rows + (more ? 1 : 0) : 0;
+    } else {
+      wlo = __shfl(lo, 0); whi = __shfl(hi, rows - 1);
+      nsteps = whi - wlo + rows + (more ? 1 : 0);
+    }
+    const float* drow = D + (size_t)min(i, na - 1) * width;
     uint4* mvs = mv + (long long)s * per_strip;
-    // lane 0's first cell (file head; in strip 0 nothing of it is used)
+    // lane 0's first cell (in strip 0 nothing of it is used)
     float diag = hand[max(wlo - 1, 0)];
-    float qo = __fadd_rn(__fadd_rn(hand[max(wlo - 2, 0)], drow[max(wlo - 1, 0)]), step);
+    float qo = __fadd_rn(__fadd_rn(hand[max(wlo - 2, 0)], drow[BAND ? min(max(wlo - 1 - off, 0), width - 1) : max(wlo - 1, 0)]), step);
     unsigned long long w0 = 0, w1 = 0;                                // the masks of step (t & ~63) + lane
     SlopeBlock cur, nxt;
-    slope_load(cur, drow, hand, handq, wlo - lane, lane, nb);
+    slope_load<BAND>(cur, drow, hand, handq, wlo - lane, lane, off, width, nb);
     for(int t0 = 0; t0 < nsteps; t0 += DTW_U) {
-      slope_load(nxt, drow, hand, handq, wlo + t0 + DTW_U - lane, lane, nb);
+      slope_load<BAND>(nxt, drow, hand, handq, wlo + t0 + DTW_U - lane, lane, off, width, nb);
 #pragma unroll
       for(int k = 0; k < DTW_U; k ++) {
         const int t = t0 + k;
         if(t >= nsteps) break;
         const int j = wlo + t - lane;
         const bool on = j >= lo && j <= hi;
-        const bool has0 = j >= a0 && j <= b0, has1 = j >= a1 && j <= b1, has2 = j - 1 >= a0 && j - 1 <= b0;
+        const bool has0 = j >= a0 && j <= b0, has1 = j >= a1 && j <= b1, has2 = j - 1 >= c0 && j - 1 <= b0;
         const float up_raw = wave_shr1(cur.p[k], v);                  // acc[i-1][j]
         const float qi = wave_shr1(cur.q[k], qo);
-        float m = diag; int move = 0;                                 // L3: the first candidate that exists ...
+        float m = diag; int move = 0;                                 // L3 / K3: the first candidate that exists ...
         if(! has0) { m = qi; move = 1; }
         if(! has0 && ! has1) { m = qo; move = 2; }
         if(has0 && has1 && qi < m) { m = qi; move = 1; }              // ... and a later one only if strictly smaller
@@ -385,164 +445,7 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw(AlignDev d, const floa
   const int last = (na - 1) & (WAVE - 1);
   if(lane == last) out[cost0 + blockIdx.x] = v;                       // acc[na-1][nb-1]: the last cell of the last row's range
 
-  // L4: back along the moves
-  float* pos = out + (size_t)p.pos0;
-  int i = na - 1, j = nb - 1;
-  int cur_s = -1, cur_b = -1, wlo = 0;
-  uint4 w = make_uint4(0, 0, 0, 0);
-  for(int guard = min(na, nb); guard > 0; guard --) {
-    if(i == 0 && j == 0) break;
-    const int s = i >> 6, l = i & (WAVE - 1);
-    if(s != cur_s) { int h; align_slope_row((long long)s * WAVE, na, nb, wlo, h); }
-    const int t = j - wlo + l, blk = t & ~(WAVE - 1);
-    if(t < 0 || t >= per_strip) break;                                // (a cell outside the region: no stored move leads there)
-    if(s != cur_s || blk != cur_b) {
-      w = make_uint4(0, 0, 0, 0);
-      if((long long)blk + lane < per_strip) w = mv[(long long)s * per_strip + blk + lane];
-      cur_s = s; cur_b = blk;
-    }
-    const int k = t & (WAVE - 1);
-    const unsigned m0 = (unsigned)__builtin_amdgcn_readlane((int)(l < 32 ? w.x : w.y), k);
-    const unsigned m1 = (unsigned)__builtin_amdgcn_readlane((int)(l < 32 ? w.z : w.w), k);
-    const int move = (int)((m0 >> (l & 31)) & 1u) | (int)(((m1 >> (l & 31)) & 1u) << 1);
-    if(i < 1 || j < 1 || move == 3 || (move == 1 && i < 2) || (move == 2 && j < 2)) break;   // (likewise: it would leave the matrix)
-    if(lane == 0) pos[i] = __fmul_rn((float)(2 * j - (move == 2)), 0.5f);
-    if(move == 1) {
-      if(lane == 0) pos[i - 1] = __fmul_rn((float)(2 * j), 0.5f);     // (i - 1, j) on the way to (i - 2, j - 1)
-      i -= 2; j --;
-    } else if(move == 2) { i --; j -= 2; }
-    else { i --; j --; }
-  }
-  if(lane == 0) pos[0] = 0.0f;                                        // row 0 is (0, 0) alone
-}
-
-// ---------------------------------------------------------------- K3 - K4: the slope pattern inside the band
-// k_align_slope_dtw's scheme over band planes: lane l on row i = 64 s + l, on column j = wlo + t - l at step t; diag, qi and qo as
-// above it, one DPP shift for acc[i-1][j] and one for the two-step candidate, two hand-over rows indexed by the column, two
-// ballots per step.  What differs:
-//   rows     the region's rows (rule K1) come from the host's table, one {lo, hi} per row, an empty row lo > hi: a lane loads
-//            rows i, i - 1 and i - 2 once per strip.  The band's rows p ... q come from align_band_center.  Which candidates
-//            exist is K3's integer comparisons, folded into three ranges per strip: move 0 needs j - 1 in row i - 1 of the
-//            region; move 1 needs j - 1 in row i - 2 of the region and j in row i - 1 of the band; move 2 needs j - 2 in row
-//            i - 1 of the region and j - 1 >= p_i (j - 1 <= q_i follows from j being in the region).
-//   D        entry j - (c_i - band) of a row of 2 band + 1, clamped to the row.  A lane forms (diag + D[i][j]) + step_cost on
-//            every cell it passes, region or not, because an allowed move passes cells of the band outside the region.  On a
-//            cell outside the band that sum holds +infinity or a clamped read, and no candidate uses it: the comparisons
-//            above ask for the passed cell to be in the band, by integers.  The same holds for what unwritten memory, an
-//            earlier strip or a lane outside its range left in a register or in the hand-over rows.
-//   window   [wlo, whi] = the least lo and the largest hi of the strip's non-empty rows (a wavefront reduction).  Over the
-//            non-empty rows of a connected band lo and hi do not decrease and no two consecutive rows are empty (rule K1,
-//            measured): so a strip has a non-empty row, a move 1 into the first row of the next strip at column j passes
-//            the strip's last row at j <= whi + 1 (its other end (i - 1, j - 1) is in the region) -- one step more where a
-//            strip follows, as above -- and lane 0 meets no cell of the region left of wlo.
-// Hand-over, windows wider or narrower than 64 columns.  Every lane of a strip counts its steps from the strip's own wlo.  Lane
-// 0 is on column x at step x - wlo and loads entry x of either row then at the latest (DTW_U to 2 DTW_U - 1 steps earlier in
-// fact, and entries wlo - 1 and wlo - 2 before the first step); lane 63 is on column x at step x - wlo + 63 and stores entry x
-// then.  So whatever whi - wlo is -- 0 under band 0, where lane 0 has left the window before lane 63 stores anything, or 140
-// and more under band 70, where lane 0 is still reading column wlo + 100 while lane 63 stores column wlo + 37 -- entry x is
-// read at least 63 steps before it is overwritten, and one wavefront runs its steps in program order.  Loads of columns
-// past nb - 1 are clamped to nb - 1; they may see the new value, and are not used.
-// The walk back is k_align_slope_dtw's; the window of a strip is found again from the table.
-DEV void band_slope_load(SlopeBlock& b, const float* __restrict__ drow, const float* hand, const float* handq, int j0, int lane,
-  int off, int width, int nb) {
-#pragma unroll
-  for(int k = 0; k < DTW_U; k ++) {
-    const int x = min(max(j0 + lane + k, 0), nb - 1);
-    b.d[k] = drow[min(max(j0 + k - off, 0), width - 1)];
-    b.p[k] = hand[x]; b.q[k] = handq[x];
-  }
-}
-
-// [wlo, whi] of a strip from the range of each lane's row ((1, 0): empty or no row); whi < wlo if every row is empty
-DEV void band_slope_window(int lo, int hi, int nb, int& wlo, int& whi) {
-  wlo = lo <= hi ? lo : nb - 1; whi = lo <= hi ? hi : 0;
-#pragma unroll
-  for(int o = WAVE / 2; o > 0; o >>= 1) { wlo = min(wlo, __shfl_xor(wlo, o)); whi = max(whi, __shfl_xor(whi, o)); }
-}
-
-__global__ __launch_bounds__(WAVE) void k_align_band_slope_dtw(AlignDev d, const float* __restrict__ plane,
-  const int2* __restrict__ region, uint4* __restrict__ moves, float* hand_rows, float* __restrict__ out, int cost0) {
-  const int lane = threadIdx.x;
-  const AlignPair p = d.pairs[blockIdx.x];
-  const int na = p.na, nb = p.nb, band = p.band, width = 2 * band + 1;
-  const float* D = plane + (size_t)p.cell0;
-  const int2* tab = region + p.pad;
-  float* hand = hand_rows + (size_t)p.row0;
-  float* handq = hand + nb;
-  uint4* mv = moves + p.mv0;
-  const long long per_strip = p.steps;
-  const float step = d.step_cost;
-  const int nstrips = (na + WAVE - 1) / WAVE;
-  float v = 0.0f;                                                     // acc of this lane's last cell
-  for(int s = 0; s < nstrips; s ++) {
-    const int i = s * WAVE + lane, rows = min(WAVE, na - s * WAVE);
-    const bool more = s + 1 < nstrips;
-    // the range of this lane's row of the region, and the columns j for which move 0, 1 and 2 have a candidate: [a0, b0],
-    // [a1, b1], and j - 1 in [c0, b0]; empty ranges (1, 0) where there is no such row
-    int off = 0, lo = 1, hi = 0, a0 = 1, b0 = 0, a1 = 1, b1 = 0, c0 = 1;
-    if(i < na) {
-      const int2 r = tab[i];
-      const int c = align_band_center(i, na, nb);
-      lo = r.x; hi = r.y; off = c - band;
-      if(i >= 1) {
-        const int2 r1 = tab[i - 1];
-        a0 = r1.x + 1; b0 = r1.y + 1; c0 = max(a0, max(off, 0));
-      }
-      if(i >= 2) {
-        const int2 r2 = tab[i - 2];
-        const int cp = align_band_center(i - 1, na, nb);
-        a1 = max(r2.x + 1, max(cp - band, 0)); b1 = min(r2.y + 1, min(cp + band, nb - 1));
-      }
-    }
-    int wlo, whi;
-    band_slope_window(lo, hi, nb, wlo, whi);
-    const int nsteps = whi >= wlo ? whi - wlo + rows + (more ? 1 : 0) : 0;
-    const float* drow = D + (size_t)min(i, na - 1) * width;
-    uint4* mvs = mv + (long long)s * per_strip;
-    // lane 0's first cell (in strip 0 nothing of it is used)
-    float diag = hand[max(wlo - 1, 0)];
-    float qo = __fadd_rn(__fadd_rn(hand[max(wlo - 2, 0)], drow[min(max(wlo - 1 - off, 0), width - 1)]), step);
-    unsigned long long w0 = 0, w1 = 0;                                // the masks of step (t & ~63) + lane
-    SlopeBlock cur, nxt;
-    band_slope_load(cur, drow, hand, handq, wlo - lane, lane, off, width, nb);
-    for(int t0 = 0; t0 < nsteps; t0 += DTW_U) {
-      band_slope_load(nxt, drow, hand, handq, wlo + t0 + DTW_U - lane, lane, off, width, nb);
-#pragma unroll
-      for(int k = 0; k < DTW_U; k ++) {
-        const int t = t0 + k;
-        if(t >= nsteps) break;
-        const int j = wlo + t - lane;
-        const bool on = j >= lo && j <= hi;
-        const bool has0 = j >= a0 && j <= b0, has1 = j >= a1 && j <= b1, has2 = j - 1 >= c0 && j - 1 <= b0;
-        const float up_raw = wave_shr1(cur.p[k], v);                  // acc[i-1][j]
-        const float qi = wave_shr1(cur.q[k], qo);
-        float m = diag; int move = 0;                                 // K3: the first candidate that exists ...
-        if(! has0) { m = qi; move = 1; }
-        if(! has0 && ! has1) { m = qo; move = 2; }
-        if(has0 && has1 && qi < m) { m = qi; move = 1; }              // ... and a later one only if strictly smaller
-        if((has0 || has1) && has2 && qo < m) { m = qo; move = 2; }
-        float acc = __fadd_rn(m, cur.d[k]);
-        if(i == 0 && j == 0) { acc = cur.d[k]; move = 0; }
-        qo = __fadd_rn(__fadd_rn(diag, cur.d[k]), step);              // through (i, j) from (i - 1, j - 1)
-        diag = up_raw;
-        if(on) v = acc;
-        const unsigned long long m0 = __ballot(on && (move & 1)), m1 = __ballot(on && (move & 2));
-        if((t & (WAVE - 1)) == lane) { w0 = m0; w1 = m1; }
-        if(((t & (WAVE - 1)) == WAVE - 1 || t == nsteps - 1) && lane <= (t & (WAVE - 1)))
-          mvs[(t & ~(WAVE - 1)) + lane] = make_uint4((unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32));
-        if(lane == WAVE - 1 && more && j >= 0 && j < nb) {            // for lane 0 of the next strip
-          handq[j] = qo;
-          if(on) hand[j] = acc;
-        }
-      }
-      cur = nxt;
-    }
-    __threadfence();                                                  // the hand-over rows and the masks, before other lanes read them
-  }
-  const int last = (na - 1) & (WAVE - 1);
-  if(lane == last) out[cost0 + blockIdx.x] = v;                       // acc[na-1][nb-1]: the last row of the region is that cell
-
-  // K4: back along the moves
+  // L4 / K4: back along the moves
   float* pos = out + (size_t)p.pos0;
   int i = na - 1, j = nb - 1;
   int cur_s = -1, cur_b = -1, wlo = 0;
@@ -551,9 +454,11 @@ __global__ __launch_bounds__(WAVE) void k_align_band_slope_dtw(AlignDev d, const
     if(i == 0 && j == 0) break;
     const int s = i >> 6, l = i & (WAVE - 1);
     if(s != cur_s) {
-      const int2 r = tab[min(s * WAVE + lane, na - 1)];
-      int whi;
-      band_slope_window(s * WAVE + lane < na ? r.x : 1, s * WAVE + lane < na ? r.y : 0, nb, wlo, whi);
+      if constexpr(BAND) {
+        const int2 r = tab[min(s * WAVE + lane, na - 1)];
+        int whi;
+        band_slope_window(s * WAVE + lane < na ? r.x : 1, s * WAVE + lane < na ? r.y : 0, nb, wlo, whi);
+      } else { int h; align_slope_row((long long)s * WAVE, na, nb, wlo, h); }
     }
     const int t = j - wlo + l, blk = t & ~(WAVE - 1);
     if(t < 0 || t >= per_strip) break;                                // (a cell outside the region: no stored move leads there)
@@ -592,15 +497,10 @@ int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* pl
   return 0;
 }
 
-int launch_align_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0) {
+int launch_align_slope_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
+  float* row, float* out, int cost0) {
   if(d.n_pairs == 0) return 0;
-  LAUNCH("k_align_slope_dtw", k_align_slope_dtw, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0);
-  return 0;
-}
-
-int launch_align_band_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, const int2* region, uint4* moves, float* row,
-  float* out, int cost0) {
-  if(d.n_pairs == 0) return 0;
-  LAUNCH("k_align_band_slope_dtw", k_align_band_slope_dtw, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0);
+  if(band) LAUNCH("k_align_band_slope_dtw", k_align_slope_dtw_t<true>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0);
+  else LAUNCH("k_align_slope_dtw", k_align_slope_dtw_t<false>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0);
   return 0;
 }

@@ -100,6 +100,13 @@ template <class T> struct DevBuf {
   void release() { llsm_dev_free(p); p = nullptr; n = 0; }        // callers synchronise the stream first
 };
 
+// The four alignment calls (align.cpp): two bits, inside a diagonal band and under the slope pattern.  A mode indexes the
+// batch's scratch sets and this table of the call's name and of its plane of llsm_gpu_batch_debug_plane.
+enum AlignMode { ALIGN_FULL = 0, ALIGN_BAND = 1, ALIGN_SLOPE = 2 };
+struct AlignCall { const char* name; int plane; };
+static const AlignCall kAlignCalls[4] = {{"llsm_gpu_batch_align", 6}, {"llsm_gpu_batch_align_band", 9},
+  {"llsm_gpu_batch_align_slope", 12}, {"llsm_gpu_batch_align_band_slope", 13}};
+
 struct llsm_gpu_batch {
   llsm_gpu_context* ctx;
   llsm_gpu_layout lay;
@@ -189,18 +196,17 @@ struct llsm_gpu_batch {
   // F0 tracking (llsm_gpu_batch_track_f0): the candidate plane of the last call, [total_frames][24] (plane 5 of
   // llsm_gpu_batch_debug_plane once a call has run), and one word of back pointers per frame -- grow-only
   DevBuf<float> f0_cand; DevBuf<unsigned> f0_bp; bool f0_cand_filled = false;
-  // alignment (align.cpp), scratch of the batch given as a, one set per call so that plane 6 stays what the last
-  // llsm_gpu_batch_align left, plane 9 what the last llsm_gpu_batch_align_band left, plane 12 what the last
-  // llsm_gpu_batch_align_slope left (als) and plane 13 what the last llsm_gpu_batch_align_band_slope left (albs): the planes
-  // of the last successful call (`cells` floats, 0: no call yet), the row one strip of 64 rows hands to the next (two rows
-  // under the slope pattern), the device block [pos of every pair | cost of every pair], the moves (2 bits per lane and
-  // step of k_align_dtw_t), the pair and tile tables and, in albs alone, the rows of the region (rule K1: one {lo, hi} per
-  // row of every pair) -- all grow-only
+  // alignment (align.cpp), scratch of the batch given as a, one set per call, indexed by the call's AlignMode, so that each
+  // of planes 6, 9, 12 and 13 (kAlignCalls) stays what the last call of its own kind left: the planes of the last
+  // successful call (`cells` floats, 0: no call yet), the row one strip of 64 rows hands to the next (two rows under the
+  // slope pattern), the device block [pos of every pair | cost of every pair], the moves (2 bits per lane and step of the
+  // path kernel), the pair and tile tables and, under ALIGN_BAND | ALIGN_SLOPE alone, the rows of the region (rule K1: one
+  // {lo, hi} per row of every pair) -- all grow-only
   struct AlignScratch {
     DevBuf<float> plane, row, out; DevBuf<uint4> moves; DevBuf<AlignPair> pairs; DevBuf<int4> tiles; DevBuf<int2> region;
     long long cells = 0;
     void release() { plane.release(); row.release(); out.release(); moves.release(); pairs.release(); tiles.release(); region.release(); }
-  } al, alb, als, albs;
+  } align[4];
   // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
   // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful
   // llsm_gpu_batch_select; sel_frames 0: no call yet), the back pointers (3 bits per state at bit 8 j, one word pair per

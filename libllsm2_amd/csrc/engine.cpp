@@ -603,7 +603,7 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   b -> coder_mel.release();
   b -> blob_widths.release(); b -> blob_tab.release(); b -> blob_dev.release();
   b -> f0_uss.release(); b -> f0_raw.release(); b -> f0_cmndf.release(); b -> f0_cand.release(); b -> f0_bp.release();
-  b -> al.release(); b -> alb.release(); b -> als.release(); b -> albs.release();
+  for(auto& sc : b -> align) sc.release();
   b -> sel_lists.release(); b -> sel_p7.release(); b -> sel_p8.release(); b -> sel_bp.release(); b -> sel_out.release();
   b -> selc_lists.release(); b -> selc_near.release(); b -> selc_p10.release(); b -> selc_p11.release(); b -> selc_bp.release();
   b -> selc_out.release();
@@ -636,23 +636,22 @@ extern "C" int llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq) {
 // dst == NULL: only the size.  Returns the number of floats of the plane, -1 without one.
 extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap) {
   if(! b || which < 0 || which > 13) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
-  DevBuf<float>& src = which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : which == 3 ? b -> colored :
-                      which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : which == 6 ? b -> al.plane :
-                      which == 7 ? b -> sel_p7 : which == 8 ? b -> sel_p8 : which == 9 ? b -> alb.plane :
-                      which == 10 ? b -> selc_p10 : which == 11 ? b -> selc_p11 : which == 12 ? b -> als.plane : b -> albs.plane;
-  const long long n = which <= 1 ? (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1) :
+  int mode = -1;                                                      // of the alignment call whose plane `which` is
+  for(int m = 0; m < 4; m ++) if(kAlignCalls[m].plane == which) mode = m;
+  DevBuf<float>& src = mode >= 0 ? b -> align[mode].plane :
+                      which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : which == 3 ? b -> colored :
+                      which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : which == 7 ? b -> sel_p7 : which == 8 ? b -> sel_p8 :
+                      which == 10 ? b -> selc_p10 : b -> selc_p11;
+  const long long n = mode >= 0 ? b -> align[mode].cells :
+                      which <= 1 ? (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1) :
                       which == 2 ? (long long)b -> lay.nchannel * b -> lay.total_samples :
                       which == 3 ? (long long)b -> lay.n_utt * b -> lay.nchannel * b -> lay.ntemplate_ext :
                       which == 4 ? (long long)b -> lay.total_frames * b -> f0_cm_cols :
-                      which == 5 ? (long long)b -> lay.total_frames * 24 : which == 6 ? b -> al.cells :
-                      which == 9 ? b -> alb.cells : which == 12 ? b -> als.cells : which == 13 ? b -> albs.cells : which >= 10 ? b -> selc_frames * (which == 10 ? 32 : 256) :
+                      which == 5 ? (long long)b -> lay.total_frames * 24 : which >= 10 ? b -> selc_frames * (which == 10 ? 32 : 256) :
                       b -> sel_frames * (which == 7 ? 16 : 64);
   if(which == 4 && b -> f0_cm_cols == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_estimate_f0 with keep_cmndf has run on this batch"); return -1; }
   if(which == 5 && ! b -> f0_cand_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_track_f0 has run on this batch"); return -1; }
-  if(which == 6 && b -> al.cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align has run on this batch"); return -1; }
-  if(which == 9 && b -> alb.cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align_band has run on this batch"); return -1; }
-  if(which == 12 && b -> als.cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align_slope has run on this batch"); return -1; }
-  if(which == 13 && b -> albs.cells == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_align_band_slope has run on this batch"); return -1; }
+  if(mode >= 0 && n == 0) { llsm_set_error(std::string("llsm_gpu_batch_debug_plane: no ") + kAlignCalls[mode].name + " has run on this batch"); return -1; }
   if((which == 7 || which == 8) && b -> sel_frames == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_select has run on this batch"); return -1; }
   if((which == 10 || which == 11) && b -> selc_frames == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_select_chain has run on this batch"); return -1; }
   if(which == 2 && ! b -> ce_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has filtered the bands of this batch"); return -1; }

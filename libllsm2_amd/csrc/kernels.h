@@ -363,12 +363,11 @@ struct AlignDev {
 int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* tiles, int n_tiles, float* plane);
 // D2 - D3 / B3 - B4 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
 int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
-// L3 - L4 over whole-matrix planes, one wavefront per pair; row: two hand-over rows of nb floats per pair, out as above
-int launch_align_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
-// K3 - K4 over band planes, one wavefront per pair; region: {lo, hi} of every row of every pair (an empty row: lo > hi), pair p's
-// from entry pairs[p].pad; row: two hand-over rows of nb floats per pair, out as above
-int launch_align_band_slope_dtw(LaunchCtx* P, const AlignDev& d, const float* plane, const int2* region, uint4* moves, float* row,
-  float* out, int cost0);
+// L3 - L4 over whole-matrix planes or, with `band`, K3 - K4 over band planes, one wavefront per pair; region (read with
+// `band` alone): {lo, hi} of every row of every pair (an empty row: lo > hi), pair p's from entry pairs[p].pad; row: two
+// hand-over rows of nb floats per pair, out as above
+int launch_align_slope_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
+  float* row, float* out, int cost0);
 
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5 and C1 - C6: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame

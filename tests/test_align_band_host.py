@@ -12,11 +12,10 @@ import pytest
 import libllsm2_amd as llsm
 import align_reference as aref
 import align_band_reference as bref
+from align_common import BAND_SIZES as SIZES, SEEDS
 
 SHAPES = [(na, nb) for na in range(1, 71) for nb in range(1, 71)] + [(129, 200), (200, 129), (10, 1000), (2, 63), (60000, 59000)]
 SMALL = [(1, 1), (1, 7), (7, 1), (2, 63), (63, 64), (64, 65), (65, 129), (5, 5)]
-SIZES = [(120, 150), (200, 200), (150, 97), (257, 300)]
-SEEDS = range(12)
 
 
 def bits(a):

@@ -16,7 +16,7 @@ import align_reference as aref
 import align_band_reference as bref
 import align_slope_reference as sref
 import align_band_slope_reference as kref
-from test_align_host import COST_REL, DIFFER_CAP
+from align_common import COST_REL, DIFFER_CAP, band_slope_properties as check_properties
 
 SIZES = [(200, 170), (64, 65), (129, 90), (300, 410)]
 SEEDS = range(12)
@@ -241,17 +241,6 @@ def test_a_move_is_refused_where_only_the_passed_cell_is_outside_the_band():
     # one column more of band and the cell is back
     pos, cost = kref.dtw(bref.to_band(D, 1), 3, 0.3)
     assert cost == sref.dtw(D, 0.3)[1] and list(pos) == [0.0, 1.0, 2.0, 2.0]
-
-
-def check_properties(pos, na, nb, band):
-    """what follows from K4 as from L4, and the band"""
-    assert not np.any(np.isnan(pos)) and pos[0] == 0 and pos[-1] >= nb - 1.5 and pos[-1] <= nb - 1
-    d1 = np.diff(pos)
-    assert np.all(d1 >= 0) and np.all(d1 <= 2), (na, nb, pos)
-    assert np.all(pos[2:] - pos[:-2] >= 1), (na, nb, pos)
-    assert np.all((pos * 2) % 1 == 0)                               # a row spans one column or two
-    p, q = kref.band_rows(na, nb, band)
-    assert np.all(pos >= np.array(p)) and np.all(pos <= np.array(q))
 
 
 def test_nan_and_infinite_planes_keep_the_walk_inside():

@@ -13,11 +13,7 @@ import pytest
 
 import libllsm2_amd as llsm
 import align_reference as aref
-
-SIZES = [(200, 170), (64, 65), (129, 63), (300, 410)]
-SEEDS = range(12)
-DIFFER_CAP = 0.005              # share of all frames on which float32 may leave the float64 chain
-COST_REL = 1e-5
+from align_common import COST_REL, DIFFER_CAP, FULL_SIZES as SIZES, SEEDS, full_case as case
 
 
 def test_default_options():
@@ -143,19 +139,6 @@ def test_dist_by_hand():
 
 
 # ---------------------------------------------------------------- float32 against float64, and against the truth
-_cases = {}
-
-
-def case(size, seed):
-    """(float32 chain, float64 chain, truth) of one generated pair, each (pos, cost); computed once"""
-    key = (size, seed)
-    if key not in _cases:
-        A, B, truth = aref.make(seed, size[0], size[1], 24, 0.3)
-        A = A.astype(np.float32); B = B.astype(np.float32)
-        _cases[key] = (aref.align(A, B, 0, 24, step_cost=1.0), aref.align(A, B, 0, 24, step_cost=1.0, dtype=np.float64), truth)
-    return _cases[key]
-
-
 def test_float32_against_float64():
     differ = total = 0
     worst = 0.0

@@ -13,11 +13,9 @@ import pytest
 import libllsm2_amd as llsm
 import align_reference as aref
 import align_slope_reference as sref
-from test_align_host import COST_REL, DIFFER_CAP
+from align_common import COST_REL, DIFFER_CAP, SEEDS, SLOPE_SIZES as SIZES, slope_case as case, slope_properties as check_properties
 
-SIZES = [(200, 170), (64, 65), (129, 90), (300, 410)]
 QUALITY_SIZES = [(200, 170), (64, 65), (129, 90), (300, 360)]      # the warp of (300, 410) exceeds slope 2 in places
-SEEDS = range(12)
 LARGER = [(64, 127), (129, 65), (127, 64), (65, 129), (1000, 1999), (1999, 1000), (1000, 2000), (2001, 1000), (5000, 4001),
           (16400, 16400)]
 
@@ -195,16 +193,6 @@ def test_three_by_two_and_one_by_one():
         sref.dtw(np.zeros((1, 2), np.float32), 0.0)
 
 
-def check_properties(pos, na, nb):
-    lo, hi = sref.rows(na, nb)
-    assert not np.any(np.isnan(pos)) and pos[0] == 0 and pos[-1] >= nb - 1.5 and pos[-1] <= nb - 1
-    d1 = np.diff(pos)
-    assert np.all(d1 >= 0) and np.all(d1 <= 2), (na, nb, pos)
-    assert np.all(pos[2:] - pos[:-2] >= 1), (na, nb, pos)
-    assert np.all((pos * 2) % 1 == 0)                               # a row spans one column or two
-    assert np.all(pos >= lo - 1) and np.all(pos <= hi + 1)            # (a cell between the ends of a move may lie one outside)
-
-
 def test_a_nan_row_keeps_the_walk_inside():
     rng = np.random.default_rng(5)
     for na, nb, nan_rows in ((9, 7, [4]), (7, 9, [0]), (6, 6, [5]), (5, 8, [0, 1, 2, 3, 4]), (64, 127, [10, 11]), (9, 5, [3, 4])):
@@ -239,20 +227,6 @@ def test_properties_of_pos_on_random_planes():
 
 
 # ---------------------------------------------------------------- float32 against float64, the truth, the full rule
-_cases = {}
-
-
-def case(size, seed):
-    """(float32 chain, float64 chain, truth, float32 chain of rules D1 - D3) of one generated pair, each (pos, cost)"""
-    key = (size, seed)
-    if key not in _cases:
-        A, B, truth = aref.make(seed, size[0], size[1], 24, 0.3)
-        A = A.astype(np.float32); B = B.astype(np.float32)
-        _cases[key] = (sref.align(A, B, 0, 24, step_cost=1.0), sref.align(A, B, 0, 24, step_cost=1.0, dtype=np.float64), truth,
-                       aref.align(A, B, 0, 24, step_cost=1.0))
-    return _cases[key]
-
-
 def test_float32_against_float64():
     differ = total = 0
     worst = 0.0

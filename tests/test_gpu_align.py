@@ -19,13 +19,12 @@ import pytest
 import libllsm2_amd as llsm
 import align_reference as aref
 from gpu_common import report
-from test_align_host import DIFFER_CAP, SEEDS, SIZES, case as host_case
+from align_common import DIFFER_CAP, DIM, FULL_SIZES as SIZES, SEEDS, all_arrays, beq, bits, coded, full_case as host_case, \
+    planes_of, random_code, rows_of
 from verify_utils import GOLDEN, read_wav
 
 pytestmark = pytest.mark.gpu
 
-FS = 44100.0
-NFFT, OSP, OBAP, DIM = 128, 64, 5, 72
 PAIRS = [(1, 1), (1, 7), (7, 1), (2, 63), (63, 64), (64, 65), (65, 129), (129, 200)]
 NA = [p[0] for p in PAIRS]
 NB = [p[1] for p in PAIRS]
@@ -37,56 +36,6 @@ def ctx():
     c = llsm.Context(0)
     yield c
     c.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def beq(a, b):
-    return np.shape(a) == np.shape(b) and np.array_equal(bits(a), bits(b))
-
-
-def coded(ctx, nfrm, code=None, coder=(OSP, OBAP)):
-    """a batch without samples whose utterances have nfrm frames, layer 1 and the coder enabled, CODE uploaded"""
-    b = llsm.Batch(ctx, llsm.make_aoptions(f0_refine=0), FS, [0] * len(nfrm), nfrm)
-    b.enable_layer1(NFFT)
-    if coder:
-        b.enable_coder(*coder)
-        if code is not None:
-            b.upload(llsm.A_CODE, code)
-    return b
-
-
-def random_code(seed, n, integer=False):
-    """n coder vectors: normal features (small integers with `integer`, so that accumulated costs tie often), the voicing
-    column mixed from 0, 1 and values next to the threshold"""
-    rng = np.random.default_rng(seed)
-    c = rng.standard_normal((n, DIM)) * 3
-    if integer:
-        c = np.round(c / 3)
-    c = c.astype(np.float32)
-    c[:, 0] = rng.choice(np.array([0, 1, 1, 0.5, 0.50000006], np.float32), n)
-    return c
-
-
-def rows_of(b, code):
-    return [code[int(b.frm_off[u]):int(b.frm_off[u + 1])] for u in range(b.layout.n_utt)]
-
-
-def planes_of(b, shapes):
-    """plane 6 of batch b cut into the planes of the pairs of the last call"""
-    flat = b.debug_plane(6)
-    assert flat.shape == (sum(n * m for n, m in shapes),)
-    out, at = [], 0
-    for n, m in shapes:
-        out.append(flat[at:at + n * m].reshape(n, m)); at += n * m
-    return out
-
-
-def all_arrays(b):
-    ids = [a for a in range(llsm.A_NARRAYS) if b.L.llsm_gpu_batch_array_bytes(b.h, a) > 0]
-    return {a: b.download(a) for a in ids}
 
 
 @pytest.fixture(scope="module")
@@ -109,7 +58,7 @@ def world(ctx):
 def test_plane_exact(ctx, world, count, first, voicing_cost):
     w = world["random"]
     w["a"].align(w["b"], IDENT, IDENT, first=first, count=count, voicing_cost=voicing_cost)
-    got = planes_of(w["a"], PAIRS)
+    got = planes_of(w["a"], 6, NA, NB)
     for p, (fa, fb) in enumerate(zip(w["ra"], w["rb"])):
         want = aref.dist(fa, fb, first, count, voicing_cost)
         assert beq(got[p], want), (PAIRS[p], int(np.count_nonzero(bits(got[p]) != bits(want))))
@@ -124,7 +73,7 @@ def test_plane_exact(ctx, world, count, first, voicing_cost):
 def test_path_exact(ctx, world, step_cost, kind):
     w = world[kind]
     pos, cost = w["a"].align(w["b"], IDENT, IDENT, first=3, count=24, voicing_cost=5.0, step_cost=step_cost)
-    planes = planes_of(w["a"], PAIRS)
+    planes = planes_of(w["a"], 6, NA, NB)
     assert cost.dtype == np.float32 and cost.shape == (len(PAIRS),)
     ties = 0
     for p, D in enumerate(planes):
@@ -171,7 +120,7 @@ def test_ties_and_forced_borders(ctx, world):
     a = coded(ctx, NA, ca)
     try:
         pos, cost = a.align(w["b"], IDENT, IDENT, **opts)
-        planes = planes_of(a, PAIRS)
+        planes = planes_of(a, 6, NA, NB)
         for p in range(len(PAIRS)):
             if p in nan_pairs:
                 assert not np.any(np.isnan(pos[p])) and pos[p].min() >= 0 and pos[p].max() <= NB[p] - 1, (p, pos[p])
@@ -192,28 +141,28 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     opts = dict(first=3, count=24, step_cost=1.0, voicing_cost=5.0)
     before = all_arrays(a), all_arrays(b)
     pos, cost = a.align(b, IDENT, IDENT, **opts)
-    planes = planes_of(a, PAIRS)
+    planes = planes_of(a, 6, NA, NB)
     # alone
     for p in range(len(PAIRS)):
         p1, c1 = a.align(b, [p], [p], **opts)
-        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(planes_of(a, [PAIRS[p]])[0], planes[p]), p
+        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(planes_of(a, 6, [NA[p]], [NB[p]])[0], planes[p]), p
     # the list reversed
     pr, cr = a.align(b, IDENT[::-1], IDENT[::-1], **opts)
-    rplanes = planes_of(a, PAIRS[::-1])
+    rplanes = planes_of(a, 6, NA[::-1], NB[::-1])
     for p in range(len(PAIRS)):
         q = len(PAIRS) - 1 - p
         assert beq(pr[q], pos[p]) and beq(cr[q], cost[p]) and beq(rplanes[q], planes[p]), p
     # a second call, after other calls have used the scratch
     p2, c2 = a.align(b, IDENT, IDENT, **opts)
     assert all(beq(x, y) for x, y in zip(p2, pos)) and beq(c2, cost)
-    assert all(beq(x, y) for x, y in zip(planes_of(a, PAIRS), planes))
+    assert all(beq(x, y) for x, y in zip(planes_of(a, 6, NA, NB), planes))
     # one batch on both sides
     both = coded(ctx, NA + NB, np.concatenate([w["ca"], w["cb"]]))
     try:
         held = all_arrays(both)
         ps, cs = both.align(both, IDENT, IDENT + len(PAIRS), **opts)
         assert all(beq(x, y) for x, y in zip(ps, pos)) and beq(cs, cost)
-        assert all(beq(x, y) for x, y in zip(planes_of(both, PAIRS), planes))
+        assert all(beq(x, y) for x, y in zip(planes_of(both, 6, NA, NB), planes))
         after = all_arrays(both)
         assert held.keys() == after.keys() and all(beq(held[k], after[k]) for k in held)
     finally:
@@ -222,7 +171,7 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     ub = np.tile(IDENT, 4)
     ua = np.full(32, 5, np.int32)
     pq, cq = a.align(b, ua, ub, **opts)
-    qplanes = planes_of(a, [(NA[5], NB[u]) for u in ub])
+    qplanes = planes_of(a, 6, [NA[5]] * len(ub), [NB[u] for u in ub])
     alone = [a.align(b, [5], [u], **opts) for u in IDENT]
     for k, u in enumerate(ub):
         assert beq(pq[k], alone[u][0][0]) and beq(cq[k], alone[u][1][0]), k

@@ -6,7 +6,7 @@ in float32 applied to the device's own plane 9, bit for bit.  On top of them: a 
 llsm_gpu_batch_align on the device, invariance of a pair's bits under everything around it, the generated pairs of
 tests/test_align_band_host.py under a band of 15 % against the full call, the positions fed to splice, and every refusal.
 
-Batches are those of tests/test_gpu_align.py: layer 1 at nfft 128, the coder at orders 64 + 5, no samples, synthetic
+Batches are those of tests/align_common.py: layer 1 at nfft 128, the coder at orders 64 + 5, no samples, synthetic
 LLSM_GPU_CODE.  The pairs sit below, at and above the 64 rows of a strip of k_align_band_dtw and the 64 x 64 tile of
 k_align_band_dist, with three and five strips whose column windows move (129 x 200, 200 x 129, 257 x 300) and slopes well
 above and below 1 (2 x 63, 10 x 1000, 7 x 1, 200 x 129)."""
@@ -19,8 +19,7 @@ import pytest
 import libllsm2_amd as llsm
 import align_reference as aref
 import align_band_reference as bref
-from test_align_band_host import SEEDS, SIZES
-from test_gpu_align import DIM, all_arrays, beq, coded, planes_of, random_code, rows_of
+from align_common import BAND_SIZES as SIZES, DIM, SEEDS, all_arrays, band_widths, beq, coded, planes_of, random_code, rows_of
 
 pytestmark = pytest.mark.gpu
 
@@ -39,16 +38,6 @@ def ctx():
     c = llsm.Context(0)
     yield c
     c.close()
-
-
-def band_planes_of(b, shapes, bands):
-    """plane 9 of batch b cut into the band planes [na][2 band + 1] of the pairs of the last call"""
-    flat = b.debug_plane(9)
-    assert flat.shape == (sum(s[0] * (2 * w + 1) for s, w in zip(shapes, bands)),)
-    out, at = [], 0
-    for (na, _), w in zip(shapes, bands):
-        out.append(flat[at:at + na * (2 * w + 1)].reshape(na, 2 * w + 1)); at += na * (2 * w + 1)
-    return out
 
 
 def make_world(ctx, ca, cb):
@@ -88,7 +77,7 @@ def test_plane_exact(ctx, world, count, first, voicing_cost):
     want = [aref.dist(fa, fb, first, count, voicing_cost) for fa, fb in zip(w["ra"], w["rb"])]
     for name, bands in BANDS.items():
         w["a"].align_band(w["b"], IDENT, IDENT, bands, first=first, count=count, voicing_cost=voicing_cost)
-        got = band_planes_of(w["a"], PAIRS, bands)
+        got = planes_of(w["a"], 9, NA, band_widths(bands))
         for p in range(len(PAIRS)):
             layout = bref.to_band(want[p], bands[p])
             assert beq(got[p], layout), (PAIRS[p], name, int(np.count_nonzero(got[p].view(np.uint32) != layout.view(np.uint32))))
@@ -103,7 +92,7 @@ def test_path_exact(ctx, world, name, step_cost, kind):
     w = world[kind]
     bands = BANDS[name]
     pos, cost = w["a"].align_band(w["b"], IDENT, IDENT, bands, first=3, count=24, voicing_cost=5.0, step_cost=step_cost)
-    planes = band_planes_of(w["a"], PAIRS, bands)
+    planes = planes_of(w["a"], 9, NA, band_widths(bands))
     assert cost.dtype == np.float32 and cost.shape == (len(PAIRS),)
     for p, P in enumerate(planes):
         na, nb = PAIRS[p]
@@ -128,8 +117,8 @@ def test_full_coverage_is_align(ctx, world, kind):
             pos, cost = w["a"].align_band(w["b"], IDENT, IDENT, bands, **opts)
             assert all(beq(x, y) for x, y in zip(pos, want_pos)) and beq(cost, want_cost), (kind, step_cost)
             assert beq(w["a"].debug_plane(6), plane6)               # plane 6 is the full call's alone
-            full = planes_of(w["a"], PAIRS)
-            for p, P in enumerate(band_planes_of(w["a"], PAIRS, bands)):
+            full = planes_of(w["a"], 6, NA, NB)
+            for p, P in enumerate(planes_of(w["a"], 9, NA, band_widths(bands))):
                 assert beq(bref.from_band(P, NB[p]), full[p]), PAIRS[p]
 
 
@@ -141,28 +130,28 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     bands = np.array(BANDS["5"], np.int32)
     before = all_arrays(a), all_arrays(b)
     pos, cost = a.align_band(b, IDENT, IDENT, bands, **opts)
-    planes = band_planes_of(a, PAIRS, bands)
+    planes = planes_of(a, 9, NA, band_widths(bands))
     # alone
     for p in range(len(PAIRS)):
         p1, c1 = a.align_band(b, [p], [p], int(bands[p]), **opts)
-        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(band_planes_of(a, [PAIRS[p]], [bands[p]])[0], planes[p]), p
+        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(planes_of(a, 9, [NA[p]], band_widths([bands[p]]))[0], planes[p]), p
     # the list reversed
     pr, cr = a.align_band(b, IDENT[::-1], IDENT[::-1], bands[::-1], **opts)
-    rplanes = band_planes_of(a, PAIRS[::-1], bands[::-1])
+    rplanes = planes_of(a, 9, NA[::-1], band_widths(bands[::-1]))
     for p in range(len(PAIRS)):
         q = len(PAIRS) - 1 - p
         assert beq(pr[q], pos[p]) and beq(cr[q], cost[p]) and beq(rplanes[q], planes[p]), p
     # a second call, after other calls have used the scratch
     p2, c2 = a.align_band(b, IDENT, IDENT, bands, **opts)
     assert all(beq(x, y) for x, y in zip(p2, pos)) and beq(c2, cost)
-    assert all(beq(x, y) for x, y in zip(band_planes_of(a, PAIRS, bands), planes))
+    assert all(beq(x, y) for x, y in zip(planes_of(a, 9, NA, band_widths(bands)), planes))
     # one batch on both sides
     both = coded(ctx, NA + NB, np.concatenate([w["ca"], w["cb"]]))
     try:
         held = all_arrays(both)
         ps, cs = both.align_band(both, IDENT, IDENT + len(PAIRS), bands, **opts)
         assert all(beq(x, y) for x, y in zip(ps, pos)) and beq(cs, cost)
-        assert all(beq(x, y) for x, y in zip(band_planes_of(both, PAIRS, bands), planes))
+        assert all(beq(x, y) for x, y in zip(planes_of(both, 9, NA, band_widths(bands)), planes))
         after = all_arrays(both)
         assert held.keys() == after.keys() and all(beq(held[k], after[k]) for k in held)
     finally:
@@ -170,7 +159,7 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     # one pair (129 x 200) under different bands in one call: each has the bits it has alone under its band
     widths = np.array([LEAST[7], 3, 17, 64, 199, 250], np.int32)
     pq, cq = a.align_band(b, [7] * len(widths), [7] * len(widths), widths, **opts)
-    qplanes = band_planes_of(a, [PAIRS[7]] * len(widths), widths)
+    qplanes = planes_of(a, 9, [NA[7]] * len(widths), band_widths(widths))
     D = aref.dist(w["ra"][7], w["rb"][7], 3, 24, 5.0)
     for k, width in enumerate(widths):
         p1, c1 = a.align_band(b, [7], [7], int(width), **opts)

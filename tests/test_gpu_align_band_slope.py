@@ -7,7 +7,7 @@ infinite rows, the band that covers the matrix against llsm_gpu_batch_align_slop
 under everything around it (planes 6, 9 and 12 and every array of both batches untouched), one pair of 17 000 x 17 000 that
 llsm_gpu_batch_align_slope refuses, the positions fed to splice, and every refusal.
 
-Batches are those of tests/test_gpu_align.py: layer 1 at nfft 128, the coder at orders 64 + 5, no samples, synthetic
+Batches are those of tests/align_common.py: layer 1 at nfft 128, the coder at orders 64 + 5, no samples, synthetic
 LLSM_GPU_CODE.  The pairs (na, nb, band) sit below, at and above the 64 rows of a strip of k_align_band_slope_dtw: an empty
 row (3 x 2), a single line (64 x 64 under band 0), every row one cell (64 x 127), 64 empty rows (129 x 65), windows of a few
 columns whose start moves with the strip, a window wider than a strip (band 70), and the band that covers the matrix.
@@ -20,8 +20,8 @@ import pytest
 
 import libllsm2_amd as llsm
 import align_band_slope_reference as kref
-from test_align_band_slope_host import check_properties
-from test_gpu_align import DIM, all_arrays, beq, bits, coded, random_code, rows_of
+from align_common import DIM, all_arrays, band_slope_properties as check_properties, band_widths, beq, bits, coded, planes_of, \
+    random_code, rows_of, same, slices
 
 pytestmark = pytest.mark.gpu
 
@@ -52,27 +52,6 @@ def codes(kind):
         for p in (11, 12, 13):                                      # scattered over 200 x 390, 257 x 300 and 300 x 257
             ca[oa[p] + rng.integers(0, NA[p], 40), 3 + rng.integers(0, 24, 40)] = np.nan
     return ca, cb
-
-
-def slices(code, n):
-    off = np.concatenate([[0], np.cumsum(n)])
-    return [code[off[k]:off[k + 1]] for k in range(len(n))]
-
-
-def planes13_of(b, pairs):
-    """plane 13 of batch b cut into the band planes [na][2 band + 1] of the pairs (na, nb, band) of the last call"""
-    flat = b.debug_plane(13)
-    assert flat.shape == (sum(na * (2 * w + 1) for na, _, w in pairs),)
-    out, at = [], 0
-    for na, _, w in pairs:
-        out.append(flat[at:at + na * (2 * w + 1)].reshape(na, 2 * w + 1)); at += na * (2 * w + 1)
-    return out
-
-
-def same(x, y):
-    """bit for bit, or both NaN"""
-    x = np.asarray(x, np.float32); y = np.asarray(y, np.float32)
-    return x.shape == y.shape and bool(np.all((bits(x) == bits(y)) | (np.isnan(x) & np.isnan(y))))
 
 
 @pytest.fixture(scope="module")
@@ -131,7 +110,7 @@ def test_inputs_cross_the_strips_with_both_moves():
 def test_plane_exact(ctx, world, count, first, voicing_cost):
     w = world["random"]
     w["a"].align_band_slope(w["b"], IDENT, IDENT, BAND, first=first, count=count, voicing_cost=voicing_cost)
-    got = planes13_of(w["a"], PAIRS)
+    got = planes_of(w["a"], 13, NA, band_widths(BAND))
     infinite = 0
     for p, (fa, fb) in enumerate(zip(w["ra"], w["rb"])):
         want = kref.dist_band(fa, fb, BAND[p], first, count, voicing_cost)     # rule D1 inside the rows of the band, +infinity outside
@@ -146,7 +125,7 @@ def test_plane_exact(ctx, world, count, first, voicing_cost):
 def test_path_exact(ctx, world, step_cost, kind):
     w = world[kind]
     pos, cost = w["a"].align_band_slope(w["b"], IDENT, IDENT, BAND, step_cost=step_cost, **OPTS)
-    planes = planes13_of(w["a"], PAIRS)
+    planes = planes_of(w["a"], 13, NA, band_widths(BAND))
     assert cost.dtype == np.float32 and cost.shape == (len(PAIRS),)
     ties = 0
     for p, P in enumerate(planes):
@@ -202,15 +181,15 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     held = a.debug_plane(6), a.debug_plane(9), a.debug_plane(12)
     before = all_arrays(a), all_arrays(b)
     pos, cost = a.align_band_slope(b, IDENT, IDENT, BAND, **opts)
-    planes = planes13_of(a, PAIRS)
+    planes = planes_of(a, 13, NA, band_widths(BAND))
     assert all(beq(a.debug_plane(n), h) for n, h in zip((6, 9, 12), held))
     # alone
     for p in range(len(PAIRS)):
         p1, c1 = a.align_band_slope(b, [p], [p], BAND[p], **opts)
-        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(planes13_of(a, [PAIRS[p]])[0], planes[p]), p
+        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(planes_of(a, 13, [NA[p]], band_widths([BAND[p]]))[0], planes[p]), p
     # the list reversed
     pr, cr = a.align_band_slope(b, IDENT[::-1], IDENT[::-1], BAND[::-1], **opts)
-    rplanes = planes13_of(a, PAIRS[::-1])
+    rplanes = planes_of(a, 13, NA[::-1], band_widths(BAND[::-1]))
     for p in range(len(PAIRS)):
         q = len(PAIRS) - 1 - p
         assert beq(pr[q], pos[p]) and beq(cr[q], cost[p]) and beq(rplanes[q], planes[p]), p
@@ -219,10 +198,10 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     band_pos, band_cost = a.align_band(b, [12], [12], 8, **opts)
     slope_pos, slope_cost = a.align_slope(b, [12, 13], [12, 13], **opts)
     others = a.debug_plane(6), a.debug_plane(9), a.debug_plane(12)
-    assert all(beq(x, y) for x, y in zip(planes13_of(a, PAIRS[::-1]), rplanes))      # none of them wrote plane 13
+    assert all(beq(x, y) for x, y in zip(planes_of(a, 13, NA[::-1], band_widths(BAND[::-1])), rplanes))      # none of them wrote plane 13
     p2, c2 = a.align_band_slope(b, IDENT, IDENT, BAND, **opts)
     assert all(beq(x, y) for x, y in zip(p2, pos)) and beq(c2, cost)
-    assert all(beq(x, y) for x, y in zip(planes13_of(a, PAIRS), planes))
+    assert all(beq(x, y) for x, y in zip(planes_of(a, 13, NA, band_widths(BAND)), planes))
     assert all(beq(a.debug_plane(n), h) for n, h in zip((6, 9, 12), others))
     assert not any(beq(x, y) for x, y in zip(held, others))          # (the other calls did write their own)
     # one pair several times in a row (equal neighbours share their rows of the region's table), the same shape under
@@ -242,7 +221,7 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
         kept = all_arrays(both)
         ps, cs = both.align_band_slope(both, IDENT, IDENT + len(PAIRS), BAND, **opts)
         assert all(beq(x, y) for x, y in zip(ps, pos)) and beq(cs, cost)
-        assert all(beq(x, y) for x, y in zip(planes13_of(both, PAIRS), planes))
+        assert all(beq(x, y) for x, y in zip(planes_of(both, 13, NA, band_widths(BAND)), planes))
         after = all_arrays(both)
         assert kept.keys() == after.keys() and all(beq(kept[k], after[k]) for k in kept)
     finally:
@@ -276,7 +255,7 @@ def test_a_long_pair_that_align_slope_refuses(ctx):
         with pytest.raises(llsm.LlsmError, match="more than 2\\^28"):
             a.align_slope(b, [0], [0], step_cost=1.0, **OPTS)
         pos, cost = a.align_band_slope(b, [0], [0], band, step_cost=1.0, **OPTS)
-        P = planes13_of(a, [(n, n, band)])[0]
+        P = planes_of(a, 13, [n], band_widths([band]))[0]
         assert P.size == 289000
         want = kref.dist_band(ca, cb, band, OPTS["first"], OPTS["count"], OPTS["voicing_cost"])
         assert beq(P, want)

@@ -7,7 +7,7 @@ under everything around it (planes 6 and 9 and every array of both batches untou
 tests/test_align_slope_host.py against float64 and against llsm_gpu_batch_align's cost, the positions fed to splice, and
 every refusal.
 
-Batches are those of tests/test_gpu_align.py: layer 1 at nfft 128, the coder at orders 64 + 5, no samples, synthetic
+Batches are those of tests/align_common.py: layer 1 at nfft 128, the coder at orders 64 + 5, no samples, synthetic
 LLSM_GPU_CODE.  The pairs sit below, at and above the 64 rows of a strip of k_align_slope_dtw, at both ends of what rule L1
 admits (64 x 127 and 129 x 65: every row a single cell or passed through; 3 x 2: an empty row), and with three to five strips
 whose windows move.  test_inputs_cross_the_strips_with_both_moves shows that the paths enter rows 64, 65, 128 and 129 by
@@ -21,9 +21,8 @@ import libllsm2_amd as llsm
 import align_reference as aref
 import align_slope_reference as sref
 from gpu_common import report
-from test_align_host import COST_REL, DIFFER_CAP
-from test_align_slope_host import SEEDS, SIZES, case as host_case, check_properties
-from test_gpu_align import DIM, all_arrays, beq, bits, coded, planes_of, random_code, rows_of
+from align_common import COST_REL, DIFFER_CAP, DIM, SEEDS, SLOPE_SIZES as SIZES, all_arrays, beq, bits, coded, planes_of, random_code, \
+    rows_of, same, slices, slope_case as host_case, slope_properties as check_properties
 
 pytestmark = pytest.mark.gpu
 
@@ -52,27 +51,6 @@ def codes(kind):
         for p in (15, 16):                                          # scattered over 200 x 390 and 257 x 300
             ca[oa[p] + rng.integers(0, NA[p], 40), 3 + rng.integers(0, 24, 40)] = np.nan
     return ca, cb
-
-
-def slices(code, n):
-    off = np.concatenate([[0], np.cumsum(n)])
-    return [code[off[k]:off[k + 1]] for k in range(len(n))]
-
-
-def slope_planes_of(b, shapes):
-    """plane 12 of batch b cut into the planes of the pairs of the last call"""
-    flat = b.debug_plane(12)
-    assert flat.shape == (sum(n * m for n, m in shapes),)
-    out, at = [], 0
-    for n, m in shapes:
-        out.append(flat[at:at + n * m].reshape(n, m)); at += n * m
-    return out
-
-
-def same(x, y):
-    """bit for bit, or both NaN"""
-    x = np.asarray(x, np.float32); y = np.asarray(y, np.float32)
-    return x.shape == y.shape and bool(np.all((bits(x) == bits(y)) | (np.isnan(x) & np.isnan(y))))
 
 
 @pytest.fixture(scope="module")
@@ -118,7 +96,7 @@ def test_inputs_cross_the_strips_with_both_moves():
 def test_plane_exact(ctx, world, count, first, voicing_cost):
     w = world["random"]
     w["a"].align_slope(w["b"], IDENT, IDENT, first=first, count=count, voicing_cost=voicing_cost)
-    got = slope_planes_of(w["a"], PAIRS)
+    got = planes_of(w["a"], 12, NA, NB)
     for p, (fa, fb) in enumerate(zip(w["ra"], w["rb"])):
         want = aref.dist(fa, fb, first, count, voicing_cost)
         assert beq(got[p], want), (PAIRS[p], int(np.count_nonzero(bits(got[p]) != bits(want))))
@@ -130,7 +108,7 @@ def test_plane_exact(ctx, world, count, first, voicing_cost):
 def test_path_exact(ctx, world, step_cost, kind):
     w = world[kind]
     pos, cost = w["a"].align_slope(w["b"], IDENT, IDENT, step_cost=step_cost, **OPTS)
-    planes = slope_planes_of(w["a"], PAIRS)
+    planes = planes_of(w["a"], 12, NA, NB)
     assert cost.dtype == np.float32 and cost.shape == (len(PAIRS),)
     ties = 0
     for p, D in enumerate(planes):
@@ -167,14 +145,14 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     plane6, plane9 = a.debug_plane(6), a.debug_plane(9)
     before = all_arrays(a), all_arrays(b)
     pos, cost = a.align_slope(b, IDENT, IDENT, **opts)
-    planes = slope_planes_of(a, PAIRS)
+    planes = planes_of(a, 12, NA, NB)
     # alone
     for p in range(len(PAIRS)):
         p1, c1 = a.align_slope(b, [p], [p], **opts)
-        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(slope_planes_of(a, [PAIRS[p]])[0], planes[p]), p
+        assert beq(p1[0], pos[p]) and beq(c1[0], cost[p]) and beq(planes_of(a, 12, [NA[p]], [NB[p]])[0], planes[p]), p
     # the list reversed
     pr, cr = a.align_slope(b, IDENT[::-1], IDENT[::-1], **opts)
-    rplanes = slope_planes_of(a, PAIRS[::-1])
+    rplanes = planes_of(a, 12, NA[::-1], NB[::-1])
     for p in range(len(PAIRS)):
         q = len(PAIRS) - 1 - p
         assert beq(pr[q], pos[p]) and beq(cr[q], cost[p]) and beq(rplanes[q], planes[p]), p
@@ -182,10 +160,10 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
     full_pos, full_cost = a.align(b, [16, 0], [16, 0], **opts)
     a.align_band(b, [12], [12], 70, **opts)
     plane6b, plane9b = a.debug_plane(6), a.debug_plane(9)
-    assert all(beq(x, y) for x, y in zip(slope_planes_of(a, PAIRS[::-1]), rplanes))   # neither wrote plane 12
+    assert all(beq(x, y) for x, y in zip(planes_of(a, 12, NA[::-1], NB[::-1]), rplanes))   # neither wrote plane 12
     p2, c2 = a.align_slope(b, IDENT, IDENT, **opts)
     assert all(beq(x, y) for x, y in zip(p2, pos)) and beq(c2, cost)
-    assert all(beq(x, y) for x, y in zip(slope_planes_of(a, PAIRS), planes))
+    assert all(beq(x, y) for x, y in zip(planes_of(a, 12, NA, NB), planes))
     assert beq(a.debug_plane(6), plane6b) and beq(a.debug_plane(9), plane9b)
     assert cost[16] >= full_cost[0] and cost[0] == full_cost[1]
     # one batch on both sides
@@ -194,7 +172,7 @@ def test_a_pair_has_the_bits_it_has_alone(ctx, world):
         held = all_arrays(both)
         ps, cs = both.align_slope(both, IDENT, IDENT + len(PAIRS), **opts)
         assert all(beq(x, y) for x, y in zip(ps, pos)) and beq(cs, cost)
-        assert all(beq(x, y) for x, y in zip(slope_planes_of(both, PAIRS), planes))
+        assert all(beq(x, y) for x, y in zip(planes_of(both, 12, NA, NB), planes))
         after = all_arrays(both)
         assert held.keys() == after.keys() and all(beq(held[k], after[k]) for k in held)
     finally:
