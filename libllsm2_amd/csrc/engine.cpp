@@ -1129,6 +1129,16 @@ static bool hmpp_window_too_long(const llsm_gpu_batch* b) {
   return true;
 }
 
+// k_refine_f0 has rewritten the F0 row on the device: every voiced value lies within 10 % of what it was (the kernel's
+// gate), so 0.9 x the lowest F0 known so far bounds the row from below.  Without this min_f0 kept the value of the
+// upload, and a second analysis of the same row (a new waveform, no new F0) took its 10 % margin from there: frames
+// lower than that left the tile kernel for the per-frame one (HMCZT), and k_utt_fftsize clamped an utterance's
+// transform to a smaller power of two than llsm_get_fftsize's (HMPP) -- in bounds, but not the reference's rows.
+// The bound shrinks with every refinement until a full F0 upload resets it; an unknown F0 stays unknown.
+static void note_refined_f0(llsm_gpu_batch* b) {
+  if(b -> min_f0 > 0 && ! b -> f0_unknown) b -> min_f0 *= 0.9f;
+}
+
 // Peak picking (HMPP) of `nsig` signals: frames whose transform fits the LDS (<= pp_lds_n points) by k_harm_pp, the
 // rest -- F0 below 21.6 Hz at 44.1 kHz, 47 Hz at 96 kHz -- by k_harm_pp_big on global scratch.  pp_nmax: the largest
 // transform the batch can need (from its lowest F0; unknown F0: the largest supported).
@@ -1211,16 +1221,19 @@ extern "C" int llsm_gpu_batch_analyze(llsm_gpu_batch* b) {
   }
   BatchDev d = batch_dev(b, b -> fs);
   LaunchCtx* P = & c -> lc;
-  if(b -> opt.f0_refine) RUN(launch_refine_f0(P, d));
   // lowest F0 of the batch (sizes the LDS of the peak-picking FFT)
   // (unknown -- the F0 row was written through its device pointer --: the largest provision there is)
   float fmin = b -> min_f0 > 0 ? b -> min_f0 : 1.0f;
   fmin *= 0.9f;                                       // refinement may lower F0 by < 10 %
+  if(hmpp && hmpp_window_too_long(b)) return -1;      // (refused before the F0 row is touched)
+  if(b -> opt.f0_refine) {
+    RUN(launch_refine_f0(P, d));
+    note_refined_f0(b);
+  }
   int pp_lds_n = 0, pp_nmax = 0;
   if(hmpp) {
     // one FFT size per utterance (llsm_get_fftsize, dsputils.c:318-326), decided on the device
     // after F0 refinement; LDS is provisioned for the largest size the batch can need
-    if(hmpp_window_too_long(b)) return -1;
     harm_pp_sizes(b, fmin, & pp_lds_n, & pp_nmax);
     if(b -> nfft_u.alloc(L.n_utt)) return -1;
     RUN(launch_utt_fftsize(P, d, pp_nmax, b -> nfft_u.p));
@@ -1320,13 +1333,16 @@ int llsm_engine_batch_harmonics(llsm_gpu_batch* b, int refine_only) {
   const bool hmpp = b -> opt.hm_method == LLSM_AOPTION_HMPP;
   BatchDev d = batch_dev(b, b -> fs);
   LaunchCtx* P = & c -> lc;
-  if(b -> opt.f0_refine || refine_only) RUN(launch_refine_f0(P, d));
-  if(refine_only) return 0;
   float fmin = b -> min_f0 > 0 ? b -> min_f0 : 1.0f;
   fmin *= 0.9f;
+  if(hmpp && ! refine_only && hmpp_window_too_long(b)) return -1;
+  if(b -> opt.f0_refine || refine_only) {
+    RUN(launch_refine_f0(P, d));
+    note_refined_f0(b);
+  }
+  if(refine_only) return 0;
   if(hmpp) {
     int pp_lds_n = 0, pp_nmax = 0;
-    if(hmpp_window_too_long(b)) return -1;
     harm_pp_sizes(b, fmin, & pp_lds_n, & pp_nmax);
     if(b -> nfft_u.alloc(L.n_utt)) return -1;
     RUN(launch_utt_fftsize(P, d, pp_nmax, b -> nfft_u.p));
