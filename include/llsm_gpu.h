@@ -176,6 +176,10 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * that call), laid out as plane 9: pair after pair in list order, each [na][2 band + 1] row-major, entry q of row i column
  * c_i - band + q, +infinity where that column lies outside the band's row [p_i, q_i] (the whole band, not only the region of
  * K1).  Refused until such a call has run; no other call writes it, and that call writes none of planes 6, 9 and 12.
+ * which = 14: the band planes of the last successful llsm_gpu_batch_align_around with this batch as a (rules A1 - A2 below that
+ * call), laid out as plane 9 around that call's centre lines: pair after pair in list order, each [na][2 band + 1] row-major,
+ * entry q of row i column c_i - band + q with c_i = center[pos0 + i], +infinity where that column lies outside [p_i, q_i].
+ * Refused until such a call has run; no other call writes it, and that call writes none of planes 6, 9, 12 and 13.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -491,7 +495,8 @@ int  llsm_gpu_batch_track_f0(llsm_gpu_batch* b, const llsm_gpu_f0_options* opt, 
  * llsm_gpu_align_check is host only: 0, or -1 with the message llsm_gpu_batch_align would give for these options
  * (NULL: the defaults) on batches whose coder has these orders.
  * Known limits: the whole matrix of a pair is searched, so a call holds pairs of 2^28 cells in all -- long material goes
- * through llsm_gpu_batch_align_band below, which searches a band around the diagonal; there are no slope constraints beyond
+ * through llsm_gpu_batch_align_band below, which searches a band around the diagonal, or llsm_gpu_batch_align_around, which
+ * searches one around the path of a coarser alignment; there are no slope constraints beyond
  * monotonicity -- a path may stay on one frame or skip many: llsm_gpu_batch_align_slope below bounds the local slope. */
 typedef struct {
   int     first, count;   /* columns [first, first + count) of LLSM_GPU_CODE are compared; defaults 3 and order_spec
@@ -537,8 +542,9 @@ int  llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pair
  * connected for its pair (the message names the pair and llsm_gpu_align_band_min of it), and a sum of na x (2 band + 1)
  * above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
  * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else, so it has to be as
- * wide as the renditions drift apart; there are no slope constraints beyond monotonicity (llsm_gpu_batch_align_slope below
- * has them over the whole matrix, llsm_gpu_batch_align_band_slope inside this band). */
+ * wide as the renditions drift apart (llsm_gpu_batch_align_around below searches a band around a line of the caller's
+ * instead); there are no slope constraints beyond monotonicity (llsm_gpu_batch_align_slope below has them over the whole
+ * matrix, llsm_gpu_batch_align_band_slope inside this band). */
 int  llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const int* band /* n_pairs half-widths, frames */, const llsm_gpu_align_options* opt /* NULL: defaults */,
        FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
@@ -589,7 +595,8 @@ int  llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* hi);  /* h
  * pair by pair before anything is allocated.  n_pairs == 0 returns 0.
  * Known limits: the whole matrix of D is computed although the region is about a third of a square pair, so the cap holds a
  * pair to about 16 400 x 16 400 -- longer material goes through llsm_gpu_batch_align_band_slope below, the same pattern inside
- * a band; one wavefront walks a pair; P = 1 is the only pattern. */
+ * a band, or llsm_gpu_batch_align_around with slope = 1, inside a band around a line; one wavefront walks a pair; P = 1 is the
+ * only pattern. */
 int  llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi);   /* host only; lo, hi: na entries each, both may be NULL */
 int  llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
@@ -652,13 +659,88 @@ int  llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int 
  * a negative band, a pair that is not admissible under L1 (in the words of llsm_gpu_batch_align_slope), a band that is not
  * connected for the slope pattern on its pair (the message names the pair and llsm_gpu_align_band_slope_min of it), and a sum
  * of na x (2 band + 1) above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
- * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else; P = 1 is the only
- * pattern; the rows of the region are computed on the host, na steps per pair and call. */
+ * Known limits: one wavefront walks a pair; the band follows the straight diagonal and nothing else
+ * (llsm_gpu_batch_align_around below, with slope = 1, follows a line of the caller's); P = 1 is the only pattern; the rows
+ * of the region are computed on the host, na steps per pair and call. */
 int  llsm_gpu_batch_align_band_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const int* band /* n_pairs half-widths, frames */, const llsm_gpu_align_options* opt /* NULL: defaults */,
        FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
 int  llsm_gpu_align_band_slope_min(int na, int nb);                                  /* host only */
 int  llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo, int* hi);     /* host only; na entries each, both may be NULL */
+
+/* ---- alignment inside a band that follows a centre line: the two banded calls above search around the straight diagonal
+ * and nothing else, which holds them to takes recorded against a click -- two freely spoken renditions of five minutes
+ * drift apart by seconds, and the band that holds the drift passes the cap or costs what the whole matrix would.  Here the
+ * caller gives the column c_i around which row i is searched, so that alignment can go from coarse to fine: align a
+ * decimated copy of the pair with llsm_gpu_batch_align_slope (every 16th vector of LLSM_GPU_CODE uploaded to a small batch,
+ * or llsm_gpu_batch_retime + llsm_gpu_batch_encode), turn its pos into a line with llsm_gpu_align_center_line, and search the
+ * fine pair within a few times the decimation of it.  center is a host array of sum_p na(p) columns, pair after pair in
+ * list order (the layout of pos); band one half-width per pair; slope chooses the moves: 0 those of
+ * llsm_gpu_batch_align_band, 1 those of llsm_gpu_batch_align_band_slope.  The contract is that of llsm_gpu_batch_align_band --
+ * the same pos and cost, the same options and llsm_gpu_align_check, synchronous, a refused call returns -1 with a message that
+ * starts with "llsm_gpu_batch_align_around:", launches and allocates nothing and leaves pos and cost untouched;
+ * LLSM_GPU_CODE of both batches is read and no array of either written; a == b is allowed; an utterance may appear in any
+ * number of pairs, each with a line of its own -- with one scratch set of its own on a for both values of slope (the band
+ * planes, llsm_gpu_batch_debug_plane(a, 14, ...), always kept): planes 6, 9, 12 and 13 and the scratch of the four other calls
+ * stay as they were.  A pair's result depends on its own two utterances, its line, its band, slope and the options only.
+ *
+ * The rules, per pair; float32, one rounding per operation, no contraction; integers taken in 64 bits.
+ *  A1. The line and the band.  c_i = center[pos0 + i], pos0 being the pair's offset into pos.  A line is valid when
+ *      0 <= c_i <= nb - 1 for every i and c_{i+1} >= c_i.  Row i spans the columns p_i = max(0, c_i - band) ...
+ *      q_i = min(nb - 1, c_i + band).
+ *      slope = 0: the band is connected when p_0 == 0, q_{na-1} == nb - 1 and p_{i+1} <= q_i + 1 for every i; then every cell
+ *      of it other than (0, 0) has a predecessor of B3 inside it.  The least connected band is max(c_0, nb - 1 - c_{na-1},
+ *      max_i (c_{i+1} - c_i) / 2) in integer division (na == 1: max(c_0, nb - 1 - c_0)).
+ *      slope = 1: the pair must be admissible under L1.  The region is that of the two interval sweeps of K1 over these p and
+ *      q: F_0 = [0, 0] if p_0 <= 0, else empty, and the rest is K1 word for word -- the forward pieces, G_{na-1} = [nb - 1,
+ *      nb - 1] if q_{na-1} >= nb - 1, the backward pieces, row i the intersection of F_i and G_i, an empty row (1, 0).  The
+ *      band is connected when row na - 1 of the region is non-empty.  Connectedness is monotone in band, and the band that
+ *      covers the matrix (band >= nb - 1) is connected for an admissible pair: its region is that of L1.
+ *      That the pieces of a row join into one interval for any line -- so that the sweeps give exactly the cells that lie on
+ *      a path of allowed moves --, that no two consecutive rows of a connected region are empty and that lo and hi do not
+ *      decrease over its non-empty rows under a non-decreasing line is MEASURED by tests/test_align_around_host.py, which
+ *      compares the sweeps with reachability cell by cell under straight and under random lines.  The reason the pieces
+ *      touch: move 0 from a cell of row i - 2 lands inside F_{i-1}, one column left of where move 1 from the same cell lands
+ *      in row i, so the piece of move 1 is never apart from those of moves 0 and 2 out of F_{i-1}.
+ *      llsm_gpu_align_around_rows fills lo and hi (na entries each; either may be NULL, both NULL only asks whether the band
+ *      is connected): for slope = 0 the band's rows p, q, for slope = 1 the region's rows with an empty row as (1, 0).  It
+ *      returns 0, or -1 with a message for na < 1, nb < 1, na above 2^28, a slope that is neither 0 nor 1, a NULL line,
+ *      under slope = 1 a pair that is not admissible (the message names na, nb and the bound), a line that is not valid
+ *      (the message names the row and its value), a negative band, and a band that is not connected (the message names
+ *      the band, na, nb and llsm_gpu_align_around_min of the line).  llsm_gpu_align_around_min returns the least connected
+ *      band -- for slope = 0 the closed form above, for slope = 1 by bisection over [0, nb - 1] --, or -1 with a message
+ *      for what _around_rows refuses before it looks at the band.
+ *      llsm_gpu_align_center_line turns pos_c of an alignment of a coarse pair of na_c x nb_c frames into a line for the
+ *      fine pair of na x nb.  In float64, one rounding per operation: x = (i (na_c - 1)) / (na - 1), k = min(floor(x),
+ *      na_c - 2), y = pos_c[k] + (pos_c[k+1] - pos_c[k]) (x - k) -- y = pos_c[0] where na_c == 1 or na == 1 --,
+ *      s = (nb - 1) / (nb_c - 1), or 0 where nb_c == 1, c_i = min(nb - 1, max(0, floor(y s + 0.5))), and then a running
+ *      maximum, so that the line does not decrease.  The result is always a valid line; the band remains the caller's
+ *      choice, with llsm_gpu_align_around_min as the floor.  Returns 0, or -1 with a message for a size below 1, a NULL array
+ *      and an entry of pos_c that is NaN or outside [0, nb_c - 1] (the message names the entry and its value).
+ *      The three are host only and need no device.
+ *  A2. D[i][j] is rule D1 unchanged, for the cells of the band only (rule B2), in the layout of plane 14.
+ *  A3. slope = 0: rules B3 - B4 over these rows.  slope = 1: rules K3 - K4 over this region and this band.
+ * It follows, and tests/test_gpu_align_around.py holds it to the bit, that with center the diagonal of B1 pos, cost and plane 14
+ * are those of llsm_gpu_batch_align_band and its plane 9 (slope = 0) or of llsm_gpu_batch_align_band_slope and its plane 13
+ * (slope = 1); that with band >= nb - 1 and any valid line pos and cost are those of llsm_gpu_batch_align or
+ * llsm_gpu_batch_align_slope; and that for finite features cost is never below the cost of that full call.
+ *
+ * Refused, each check over all pairs before the next, before anything is allocated, copied or launched: (1) everything
+ * llsm_gpu_batch_align refuses short of its cap, by the same code and in the same order; (2) a slope that is neither 0 nor 1;
+ * with n_pairs > 0 (3) a NULL band or center, (4) a negative band, (5) under slope = 1 a pair that is not admissible under L1,
+ * in the words of llsm_gpu_batch_align_slope, (6) a line that is not valid (the message names the pair, the row and the
+ * value), (7) a band that is not connected (the message names the pair and llsm_gpu_align_around_min of it), and (8) a sum of
+ * na x (2 band + 1) above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
+ * Known limits: one wavefront walks a pair; the coarse pass is the caller's -- no call runs both; under a line that climbs
+ * by whole bands per row the distance tiles of a strip of 64 rows cover far more cells than the band holds. */
+int  llsm_gpu_batch_align_around(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       const int* center /* sum_p na(p) columns, pair after pair in list order: the layout of pos */,
+       const int* band   /* n_pairs half-widths, frames */,
+       int slope         /* 0: the moves of llsm_gpu_batch_align_band; 1: those of llsm_gpu_batch_align_band_slope */,
+       const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos, FP_TYPE* cost /* may be NULL */);
+int  llsm_gpu_align_around_rows(int na, int nb, const int* center, int band, int slope, int* lo, int* hi);  /* host only */
+int  llsm_gpu_align_around_min(int na, int nb, const int* center, int slope);                               /* host only */
+int  llsm_gpu_align_center_line(int na_c, int nb_c, const FP_TYPE* pos_c, int na, int nb, int* center);     /* host only */
 
 /* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
  * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere

@@ -160,6 +160,7 @@ llsm_gpu_align_default_options llsm_gpu_align_check llsm_gpu_batch_align
 llsm_gpu_batch_align_band llsm_gpu_align_band_min llsm_gpu_align_band_rows
 llsm_gpu_batch_align_slope llsm_gpu_align_slope_rows
 llsm_gpu_batch_align_band_slope llsm_gpu_align_band_slope_min llsm_gpu_align_band_slope_rows
+llsm_gpu_batch_align_around llsm_gpu_align_around_rows llsm_gpu_align_around_min llsm_gpu_align_center_line
 llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select llsm_gpu_batch_select_chain
 """.split()
 
@@ -260,6 +261,14 @@ def load():
         L.llsm_gpu_batch_align_band_slope.argtypes = [vp, vp, C.c_int, P_int, P_int, P_int, C.POINTER(AlignOptions), P_fp, P_fp]
         L.llsm_gpu_align_band_slope_min.argtypes = [C.c_int, C.c_int]
         L.llsm_gpu_align_band_slope_rows.argtypes = [C.c_int, C.c_int, C.c_int, P_int, P_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the band around a line)
+        L.llsm_gpu_batch_align_around.argtypes = [vp, vp, C.c_int, P_int, P_int, P_int, P_int, C.c_int, C.POINTER(AlignOptions), P_fp, P_fp]
+        L.llsm_gpu_align_around_rows.argtypes = [C.c_int, C.c_int, P_int, C.c_int, C.c_int, P_int, P_int]
+        L.llsm_gpu_align_around_min.argtypes = [C.c_int, C.c_int, P_int, C.c_int]
+        L.llsm_gpu_align_center_line.argtypes = [C.c_int, C.c_int, P_fp, C.c_int, C.c_int, P_int]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -499,6 +508,41 @@ def align_band_slope_rows(na, nb, band):
     _check(load().llsm_gpu_align_band_slope_rows(int(na), int(nb), int(band), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
            "align_band_slope_rows")
     return lo, hi
+
+
+def align_around_rows(na, nb, center, band, slope=False):
+    """(lo, hi): the first and the last column of every row of an na x nb pair within `band` columns of the centre line
+    `center` (na ints), int32 [na] each: the band's rows, or with slope the rows of the region of the slope pattern, lo > hi
+    (1, 0) where no path stops on the row (llsm_gpu_align_around_rows, rule A1 of llsm_gpu_batch_align_around); a line that
+    is not valid, a band that is negative or not connected and, with slope, a pair that is not admissible are refused"""
+    c = np.ascontiguousarray(center, np.int32)
+    assert c.shape == (max(int(na), 0),), (c.shape, na)
+    lo = np.zeros(len(c), np.int32); hi = np.zeros(len(c), np.int32)
+    _check(load().llsm_gpu_align_around_rows(int(na), int(nb), c.ctypes.data_as(P_int), int(band), int(slope),
+                                             lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)), "align_around_rows")
+    return lo, hi
+
+
+def align_around_min(na, nb, center, slope=False):
+    """the least band that is connected around the centre line `center` of an na x nb pair, for the plain moves or with slope
+    for the slope pattern (llsm_gpu_align_around_min, rule A1)"""
+    c = np.ascontiguousarray(center, np.int32)
+    assert c.shape == (max(int(na), 0),), (c.shape, na)
+    r = load().llsm_gpu_align_around_min(int(na), int(nb), c.ctypes.data_as(P_int), int(slope))
+    if r < 0:
+        raise LlsmError("align_around_min: " + load().llsm_gpu_last_error().decode())
+    return int(r)
+
+
+def align_center_line(pos_c, nb_c, na, nb):
+    """the positions pos_c of an alignment of a coarse pair (len(pos_c) x nb_c frames) as the centre line of the fine pair
+    of na x nb frames, int32 [na]: interpolated, scaled, rounded and made non-decreasing (llsm_gpu_align_center_line)"""
+    pc = np.ascontiguousarray(pos_c, np.float32)
+    assert pc.ndim == 1, pc.shape
+    c = np.zeros(max(int(na), 0), np.int32)
+    _check(load().llsm_gpu_align_center_line(len(pc), int(nb_c), pc.ctypes.data_as(P_fp), int(na), int(nb),
+                                             c.ctypes.data_as(P_int)), "align_center_line")
+    return c
 
 
 def make_select_options(**kw):
@@ -758,7 +802,8 @@ class Batch:
         0 ... 15, then their bank frames; absent slots 1e30 and -1), and the join costs, total_frames x 256 (entry 16 a + j),
         of the last select_chain with this batch as the target; 12: the distance planes of the last align_slope with this
         batch as a, pair after pair, each na x nb; 13: the band planes of the last align_band_slope with this batch as a,
-        laid out as plane 9)"""
+        laid out as plane 9; 14: the band planes of the last align_around with this batch as a, laid out as plane 9 around
+        that call's centre lines)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())
@@ -782,8 +827,9 @@ class Batch:
         _check(self.L.llsm_gpu_batch_decode(self.h, int(use_layer1)), "decode")
 
     # ---- alignment (llsm_gpu.h): LLSM_GPU_CODE of two batches -> positions for splice and path costs
-    def _align(self, call, name, other, utt_a, utt_b, band, options):
-        """the four alignment calls: `call` of the library under `name`, with one band per pair unless band is None"""
+    def _align(self, call, name, other, utt_a, utt_b, band, options, before=(), after=()):
+        """the five alignment calls: `call` of the library under `name`, with one band per pair unless band is None;
+        before and after: the arguments next to the band"""
         o = make_align_options(**options)
         ua = np.ascontiguousarray(utt_a, np.int32); ub = np.ascontiguousarray(utt_b, np.int32)
         assert ua.ndim == 1 and ua.shape == ub.shape, (ua.shape, ub.shape)
@@ -793,7 +839,7 @@ class Batch:
         na = np.zeros(len(ua), np.int64); na[inside] = nfrm[ua[inside]]
         pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
         _check(call(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
-                    *(bd.ctypes.data_as(P_int) for bd in bands), C.byref(o), pos.ctypes.data_as(P_fp),
+                    *before, *(bd.ctypes.data_as(P_int) for bd in bands), *after, C.byref(o), pos.ctypes.data_as(P_fp),
                     cost.ctypes.data_as(P_fp)), name)
         return np.split(pos, np.cumsum(na)[:-1]) if len(ua) else [], cost
 
@@ -821,6 +867,22 @@ class Batch:
         [1/2, 2] for utterances whose full matrices align_slope refuses.  band: an int, or one int per pair; a pair that
         align_slope refuses and a band below align_band_slope_min of the pair are refused.  Returns what align_band returns"""
         return self._align(self.L.llsm_gpu_batch_align_band_slope, "align_band_slope", other, utt_a, utt_b, band, options)
+
+    def align_around(self, other, utt_a, utt_b, center, band, slope=False, **options):
+        """align within `band` columns of a centre line per pair (llsm_gpu_batch_align_around): the fine pass of a
+        coarse-to-fine alignment, whose lines align_center_line makes from the positions of the coarse pass.  center: a
+        list with one int array per pair (as many columns as the utterance of this batch has frames), or all of them as one
+        flat array; band: an int, or one int per pair; slope: the moves of align_band_slope instead of those of align_band.
+        Returns what align_band returns"""
+        flat = isinstance(center, np.ndarray) and center.ndim == 1
+        c = np.ascontiguousarray(center if flat else np.concatenate([np.asarray(x).reshape(-1) for x in center] or [np.zeros(0)]), np.int32)
+        ua = np.asarray(utt_a).reshape(-1)
+        nfrm = np.diff(self.frm_off)
+        need = int(sum(nfrm[u] for u in ua if 0 <= u < len(nfrm)))  # (an index outside is the library's to refuse)
+        if len(c) != need:
+            raise ValueError("align_around: center has %d columns, the pairs have %d frames" % (len(c), need))
+        return self._align(self.L.llsm_gpu_batch_align_around, "align_around", other, utt_a, utt_b, band, options,
+                           before=(c.ctypes.data_as(P_int),), after=(int(slope),))
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders
     def select(self, bank, opt=None, **options):

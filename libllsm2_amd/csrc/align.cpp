@@ -17,10 +17,17 @@
 //   llsm_gpu_batch_align_band_slope  the slope pattern inside the band (rules K1 - K4, DESIGN.md section 28: the band planes
 //                                    of k_align_band_dist, the region's rows as a table, k_align_slope_dtw_t<true>), with
 //                                    scratch of its own
+//   llsm_gpu_align_around_min / _rows   host only: the same two questions for a band around a centre line of the caller's
+//                                    (rule A1), for either pattern
+//   llsm_gpu_align_center_line       host only: the positions of a coarse alignment as the centre line of a fine one
+//   llsm_gpu_batch_align_around      either pattern inside a band around a centre line per pair (rules A1 - A3, DESIGN.md
+//                                    section 30: the kernels of the banded calls instantiated for ALIGN_GEO_LINE, which read
+//                                    the centre of a row from a table), with scratch of its own
 //
-// The four calls are one function, align_run, told apart by an AlignMode of two bits (band, slope: batch.h): the name in the
+// The five calls are one function, align_run, told apart by an AlignMode (band, slope, around: batch.h): the name in the
 // messages, the scratch set, the steps of a strip (strip_steps) and the kernel instantiations follow from it.  Every check
-// runs before anything is allocated, copied or launched.  The scratch lives on batch a, grow-only, one set per mode.
+// runs before anything is allocated, copied or launched.  The scratch lives on batch a, grow-only, one set per call.
+// Wherever a function takes `line`, NULL stands for the straight diagonal of rule B1, computed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +44,9 @@ const long long kMaxCells = 1ll << 28;
 
 int refuse(const std::string& why, const char* who = kAlign) { llsm_set_error(std::string(who) + ": " + why); return -1; }
 
+// c_i of an na x nb pair: the caller's line (rule A1), or without one the diagonal of rule B1
+int center_at(const int* line, int i, int na, int nb) { return line ? line[i] : align_band_center(i, na, nb); }
+
 // rule B1: the least connected band of an na x nb pair (na, nb >= 1).  The last row ends on nb - 1 whatever the band
 // (c = nb - 1 there) unless it is the only row, and row i + 1 starts no later than one past the end of row i iff
 // 2 band + 1 >= c_{i+1} - c_i.
@@ -50,6 +60,27 @@ int band_min(int na, int nb) {
   return gap / 2;                                                   // ceil((gap - 1) / 2) for gap >= 0
 }
 
+// rule A1 without the slope pattern: the least connected band around a valid line.  Row 0 starts on column 0 iff band >= c_0,
+// the last row ends on nb - 1 iff band >= nb - 1 - c_{na-1}, and the rows in between touch as in band_min (the clamps to
+// the matrix never part two rows: c_{i+1} <= nb - 1 and c_i >= 0).
+int around_min(int na, int nb, const int* line) {
+  int least = std::max(line[0], nb - 1 - line[na - 1]);
+  for(int i = 0; i + 1 < na; i ++) least = std::max(least, (line[i + 1] - line[i]) / 2);
+  return least;
+}
+
+// rule A1: empty if `line` is a valid centre line of an na x nb pair, else the first row that is not and its value
+std::string line_fault(int na, int nb, const int* line) {
+  for(int i = 0; i < na; i ++) {
+    if(line[i] < 0 || line[i] > nb - 1)
+      return "center[" + std::to_string(i) + "] = " + std::to_string(line[i]) + " lies outside [0, " + std::to_string(nb - 1) + "]";
+    if(i > 0 && line[i] < line[i - 1])
+      return "center[" + std::to_string(i) + "] = " + std::to_string(line[i]) + " is below center[" + std::to_string(i - 1) + "] = " +
+        std::to_string(line[i - 1]);
+  }
+  return "";
+}
+
 // rule L1: empty if an na x nb pair (na, nb >= 1) is admissible under the slope pattern, else the bound that fails
 std::string slope_bound(int na, int nb) {
   const long long ra = (long long)na - 1, rb = (long long)nb - 1;
@@ -58,7 +89,8 @@ std::string slope_bound(int na, int nb) {
   return "";
 }
 
-// rule K1: the rows of the region of an admissible na x nb pair (na, nb >= 1) under the slope pattern inside a band >= 0, by
+// rule K1: the rows of the region of an admissible na x nb pair (na, nb >= 1) under the slope pattern inside a band >= 0
+// around the diagonal or, rule A1, around a valid line (where row 0 need not hold column 0, and F_0 is then empty), by
 // the two sweeps over intervals; an empty row is (1, 0).  Returns whether the band is connected for the pattern, i.e. whether
 // the last row is non-empty.  A piece with lower end > upper end is empty and contributes nothing.
 struct Interval {
@@ -69,15 +101,15 @@ struct Interval {
     if(empty()) { a = lo; b = hi; } else { a = std::min(a, lo); b = std::max(b, hi); }
   }
 };
-bool band_slope_rows(int na, int nb, int band, std::vector<int2>& rows) {
+bool band_slope_rows(int na, int nb, int band, std::vector<int2>& rows, const int* line = nullptr) {
   using std::max; using std::min;
   std::vector<long long> p((size_t)na), q((size_t)na);
   for(int i = 0; i < na; i ++) {
-    const long long c = align_band_center(i, na, nb);
+    const long long c = center_at(line, i, na, nb);
     p[i] = max(c - band, 0ll); q[i] = min(c + band, (long long)nb - 1);
   }
   std::vector<Interval> F((size_t)na);
-  F[0].a = 0; F[0].b = 0;
+  if(p[0] <= 0) { F[0].a = 0; F[0].b = 0; }
   for(int i = 1; i < na; i ++) {
     const Interval& u = F[i - 1];
     if(! u.empty()) {
@@ -112,6 +144,16 @@ int band_slope_min(int na, int nb) {
   std::vector<int2> rows;
   int band = 0;
   while(band < nb - 1 && ! band_slope_rows(na, nb, band, rows)) band ++;
+  return band;
+}
+// the same around a valid line, where the least band may be large: by bisection over [0, nb - 1]
+int around_slope_min(int na, int nb, const int* line) {
+  std::vector<int2> rows;
+  int below = -1, band = nb - 1;                                    // `below` is not connected (or -1), `band` is
+  while(band - below > 1) {
+    const int mid = below + (band - below) / 2;
+    if(band_slope_rows(na, nb, mid, rows, line)) band = mid; else below = mid;
+  }
   return band;
 }
 
@@ -150,10 +192,10 @@ int tile_floor(int j) { return j >= 0 ? j / ALIGN_TILE * ALIGN_TILE : -((-j + AL
 // rows [i0, i0 + 63] of a pair, a strip of the path kernels and a row of tiles of the distance kernel: the first column of
 // its first row and the last of its last as the plane stores them (under a band they may lie outside the matrix).  Returns
 // the last row.
-int strip_span(bool banded, const AlignPair& q, int i0, int& jlo, int& jhi) {
+int strip_span(bool banded, const AlignPair& q, const int* line, int i0, int& jlo, int& jhi) {
   const int i1 = std::min(i0 + 63, q.na - 1);
-  jlo = banded ? align_band_center(i0, q.na, q.nb) - q.band : 0;
-  jhi = banded ? align_band_center(i1, q.na, q.nb) + q.band : q.nb - 1;
+  jlo = banded ? center_at(line, i0, q.na, q.nb) - q.band : 0;
+  jhi = banded ? center_at(line, i1, q.na, q.nb) + q.band : q.nb - 1;
   return i1;
 }
 
@@ -161,10 +203,12 @@ int strip_span(bool banded, const AlignPair& q, int i0, int& jlo, int& jhi) {
 // which each kernel finds the same way.  Without the slope pattern the window is the span within the matrix.  Under it a
 // strip that has a successor takes one step more, as the first row of the successor may be entered past column jhi, and
 // the window is, by rule L1, lo of the first row and hi of the last (neither decreases with the row), or inside a band, by
-// rule K1, the least lo and the largest hi of the non-empty rows among the pair's rows of the region, `region`.
-int strip_steps(int mode, const AlignPair& q, int i0, const int2* region) {
+// rule K1, the least lo and the largest hi of the non-empty rows among the pair's rows of the region, `region`.  Around a
+// line c does not decrease either, and a connected band has c_{i+1} - c_i <= 2 band + 1, so the window of a strip is at most
+// 63 (2 band + 1) + 2 band + 1 columns.
+int strip_steps(int mode, const AlignPair& q, const int* line, int i0, const int2* region) {
   int jlo, jhi, unused;
-  const int i1 = strip_span(mode & ALIGN_BAND, q, i0, jlo, jhi);
+  const int i1 = strip_span(mode & ALIGN_BAND, q, line, i0, jlo, jhi);
   if(! (mode & ALIGN_SLOPE)) { jlo = std::max(jlo, 0); jhi = std::min(jhi, q.nb - 1); }
   else if(mode & ALIGN_BAND) {
     jlo = q.nb - 1; jhi = 0;
@@ -175,13 +219,15 @@ int strip_steps(int mode, const AlignPair& q, int i0, const int2* region) {
   return std::max(jhi - jlo, 0) + 1 + i1 - i0 + ((mode & ALIGN_SLOPE) && i1 + 1 < q.na ? 1 : 0);
 }
 
-// The four calls, told apart by `mode` (AlignMode: batch.h): the name the messages carry and the scratch set on a follow
+// The five calls, told apart by `mode` (AlignMode: batch.h): the name the messages carry and the scratch set on a follow
 // from it.  With ALIGN_BAND the planes are band planes, else band is not read and the planes hold the whole matrix of every
-// pair.  The checks run in the order in which the calls have always made them.
-int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, int mode,
-  const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  const bool banded = mode & ALIGN_BAND, slope = mode & ALIGN_SLOPE, bslope = banded && slope;
-  const char* who = kAlignCalls[mode].name;
+// pair.  The checks run in the order in which the calls have always made them.  ALIGN_AROUND comes with ALIGN_BAND, with the
+// centre lines of all pairs in `center` and with the caller's `slope` as `pattern`, which becomes the ALIGN_SLOPE bit once it
+// has been checked; that call makes its checks in the order of its header, each over all pairs before the next.
+int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, int mode, int pattern,
+  const int* center, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
+  const bool banded = mode & ALIGN_BAND, around = mode & ALIGN_AROUND;
+  const char* who = kAlignCalls[align_call(mode)].name;
   if(! a || ! b) return refuse("NULL batch", who);
   if(n_pairs < 0) return refuse("n_pairs < 0", who);
   if(a -> ctx != b -> ctx) return refuse("the batches belong to different contexts", who);
@@ -194,8 +240,40 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   if(check(& o, a -> coder_os, a -> coder_ob, who)) return -1;
   if(n_pairs == 0) return 0;
   if(! utt_a || ! utt_b) return refuse("NULL utterance list", who);
-  if(banded && ! band) return refuse("NULL band", who);
+  if(banded && ! around && ! band) return refuse("NULL band", who);
   if(! pos) return refuse("NULL pos", who);
+  auto pair_of = [](int p) { return "pair " + std::to_string(p) + ": "; };   // (only a refusal pays for it)
+  // empty, or why the utterances of pair p cannot be aligned
+  auto pair_fault = [&](int p) -> std::string {
+    const int ua = utt_a[p], ub = utt_b[p];
+    if(ua < 0 || ua >= a -> lay.n_utt) return pair_of(p) + "utterance " + std::to_string(ua) + " is outside batch a";
+    if(ub < 0 || ub >= b -> lay.n_utt) return pair_of(p) + "utterance " + std::to_string(ub) + " is outside batch b";
+    if(a -> nfrm[ua] <= 0 || b -> nfrm[ub] <= 0) return pair_of(p) + "an utterance without frames";
+    return "";
+  };
+  auto inadmissible = [&](int p, int na, int nb) -> std::string {
+    const std::string bound = slope_bound(na, nb);
+    return bound.empty() ? "" : pair_of(p) + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound;
+  };
+  if(around) {                                                      // checks 1 - 6 of llsm_gpu_batch_align_around (7 and 8: below)
+    for(int p = 0; p < n_pairs; p ++) { const std::string why = pair_fault(p); if(! why.empty()) return refuse(why, who); }
+    if(pattern != 0 && pattern != 1) return refuse("slope = " + std::to_string(pattern) + " is neither 0 nor 1", who);
+    if(pattern) mode |= ALIGN_SLOPE;
+    if(! band || ! center) return refuse("NULL band or center", who);
+    for(int p = 0; p < n_pairs; p ++) if(band[p] < 0) return refuse(pair_of(p) + "band < 0", who);
+    for(int p = 0; p < n_pairs && pattern; p ++) {
+      const std::string why = inadmissible(p, a -> nfrm[utt_a[p]], b -> nfrm[utt_b[p]]);
+      if(! why.empty()) return refuse(why, who);
+    }
+    long long at = 0;
+    for(int p = 0; p < n_pairs; p ++) {
+      const int na = a -> nfrm[utt_a[p]];
+      const std::string why = line_fault(na, b -> nfrm[utt_b[p]], center + at);
+      if(! why.empty()) return refuse(pair_of(p) + why, who);
+      at += na;
+    }
+  }
+  const bool slope = mode & ALIGN_SLOPE, bslope = banded && slope;
   // the cells of pair r's plane as far as its utterances exist; a band plane is held below 2^61 so that the total of any
   // list fits 64 bits
   auto plane_cells = [&](int r) -> long long {
@@ -208,33 +286,42 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   std::vector<int2> table, region;                                  // rule K1: the rows of the region of all pairs, and of one
   std::vector<AlignPair> pairs((size_t)n_pairs);
   long long cells = 0, rows = 0, frames = 0, steps = 0, n_tiles = 0;
+  bool over = false;                                                // around a line: the cap is passed, and refused after the last band
   for(int p = 0; p < n_pairs; p ++) {
     const int ua = utt_a[p], ub = utt_b[p], bd = banded ? band[p] : 0;
     auto pair = [p] { return "pair " + std::to_string(p) + ": "; };   // (only a refusal pays for it)
-    if(ua < 0 || ua >= a -> lay.n_utt) return refuse(pair() + "utterance " + std::to_string(ua) + " is outside batch a", who);
-    if(ub < 0 || ub >= b -> lay.n_utt) return refuse(pair() + "utterance " + std::to_string(ub) + " is outside batch b", who);
+    const std::string fault = pair_fault(p);
+    if(! fault.empty()) return refuse(fault, who);
     const int na = a -> nfrm[ua], nb = b -> nfrm[ub];
-    if(na <= 0 || nb <= 0) return refuse(pair() + "an utterance without frames", who);
+    const int* line = around ? center + frames : nullptr;           // (frames: the rows of the pairs before this one)
     if(bd < 0) return refuse(pair() + "band < 0", who);
-    const int least = banded && ! slope ? band_min(na, nb) : 0;
+    const int least = ! banded || slope ? 0 : around ? around_min(na, nb, line) : band_min(na, nb);
     if(bd < least)
       return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
-        std::to_string(nb) + " frames: llsm_gpu_align_band_min is " + std::to_string(least), who);
+        std::to_string(nb) + " frames: " + (around ? "llsm_gpu_align_around_min is " : "llsm_gpu_align_band_min is ") +
+        std::to_string(least), who);
     if(slope) {
-      const std::string bound = slope_bound(na, nb);
-      if(! bound.empty()) return refuse(pair() + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound, who);
+      const std::string why = inadmissible(p, na, nb);
+      if(! why.empty()) return refuse(why, who);
     }
     // (a pair of the shape and band of the pair before it shares that pair's rows of the table: equal takes are common)
-    const bool as_before = bslope && p > 0 && na == pairs[p - 1].na && nb == pairs[p - 1].nb && bd == pairs[p - 1].band;
-    if(bslope && ! as_before && ! band_slope_rows(na, nb, bd, region))
+    const bool as_before = bslope && ! around && p > 0 && na == pairs[p - 1].na && nb == pairs[p - 1].nb && bd == pairs[p - 1].band;
+    if(bslope && ! as_before && ! band_slope_rows(na, nb, bd, region, line))
       return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for the slope pattern on " + std::to_string(na) +
-        " x " + std::to_string(nb) + " frames: llsm_gpu_align_band_slope_min is " + std::to_string(band_slope_min(na, nb)), who);
+        " x " + std::to_string(nb) + " frames: " + (around ? "llsm_gpu_align_around_min is " + std::to_string(around_slope_min(na, nb, line))
+        : "llsm_gpu_align_band_slope_min is " + std::to_string(band_slope_min(na, nb))), who);
+    if(over) {                                                      // only the bands of the remaining pairs are still looked at
+      if(cells < (1ll << 61)) cells += plane_cells(p);
+      frames += na;
+      continue;
+    }
     AlignPair& q = pairs[p];
     q.a0 = a -> frm_off[ua]; q.na = na; q.b0 = b -> frm_off[ub]; q.nb = nb;
     q.cell0 = (int)cells; q.row0 = (int)rows; q.pos0 = (int)frames; q.band = bd; q.mv0 = steps;
     q.pad = as_before ? pairs[p - 1].pad : (int)table.size();       // where the pair's rows of the region start
     if(bslope && ! as_before) table.insert(table.end(), region.begin(), region.end());
     cells += plane_cells(p);                                        // (checked below: the offsets above are only used if it fits)
+    if(cells > kMaxCells && around) { over = true; frames += na; continue; }
     if(cells > kMaxCells) {                                         // the total of the whole list, for the message
       for(int r = p + 1; r < n_pairs && (! banded || cells < (1ll << 61)); r ++) cells += plane_cells(r);
       return refuse(std::string(banded ? "the band planes hold " : "the distance planes hold ") + std::to_string(cells) +
@@ -243,39 +330,45 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     // the moves of a strip: one entry per anti-diagonal of its column window, as many as the widest strip of the pair has
     q.steps = 0;
     for(int i0 = 0, jlo, jhi; i0 < na; i0 += 64) {
-      strip_span(banded, q, i0, jlo, jhi);
+      strip_span(banded, q, line, i0, jlo, jhi);
       n_tiles += (jhi - tile_floor(jlo)) / ALIGN_TILE + 1;
-      q.steps = std::max(q.steps, strip_steps(mode, q, i0, table.data() + q.pad));
+      q.steps = std::max(q.steps, strip_steps(mode, q, line, i0, table.data() + q.pad));
     }
     rows += slope ? 2ll * nb : nb; frames += na;
     steps += (long long)((na + 63) / 64) * q.steps;
   }
+  if(over)
+    return refuse("the band planes hold " + std::to_string(cells) + " cells, more than 2^28 = " + std::to_string(kMaxCells), who);
   // accepted: from here on this call's scratch on a changes (and the other call's, its plane among it, does not)
-  llsm_gpu_batch::AlignScratch& sc = a -> align[mode];
+  llsm_gpu_batch::AlignScratch& sc = a -> align[align_call(mode)];
   std::vector<int4> tiles; tiles.reserve((size_t)n_tiles);
   for(int p = 0; p < n_pairs; p ++)                                 // the tiles of the matrix that meet the rows' columns, overhang included
     for(int i0 = 0, jlo, jhi; i0 < pairs[p].na; i0 += ALIGN_TILE) {
-      strip_span(banded, pairs[p], i0, jlo, jhi);
+      strip_span(banded, pairs[p], around ? center + pairs[p].pos0 : nullptr, i0, jlo, jhi);
       for(int j0 = tile_floor(jlo); j0 <= jhi; j0 += ALIGN_TILE) tiles.push_back(make_int4(p, i0, j0, 0));
     }
   hipSetDevice(a -> ctx -> device);
   const size_t n_out = (size_t)frames + (size_t)n_pairs;
   if(sc.plane.alloc((size_t)cells) || sc.row.alloc((size_t)rows) || sc.out.alloc(n_out) || sc.moves.alloc((size_t)steps) ||
-     sc.pairs.alloc(pairs.size()) || sc.tiles.alloc(tiles.size()) || sc.region.alloc(table.size())) return -1;
+     sc.pairs.alloc(pairs.size()) || sc.tiles.alloc(tiles.size()) || sc.region.alloc(table.size()) ||
+     (around && sc.center.alloc((size_t)frames))) return -1;
   sc.cells = 0;                                                     // the planes are being rewritten
   LaunchCtx* P = & a -> ctx -> lc;
   // (pageable sources: the copies have left the vectors when the calls return, and run in stream order)
   HIP_OK(hipMemcpyAsync(sc.pairs.p, pairs.data(), pairs.size() * sizeof(AlignPair), hipMemcpyHostToDevice, P -> stream));
   HIP_OK(hipMemcpyAsync(sc.tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, P -> stream));
   if(bslope) HIP_OK(hipMemcpyAsync(sc.region.p, table.data(), table.size() * sizeof(int2), hipMemcpyHostToDevice, P -> stream));
+  if(around) HIP_OK(hipMemcpyAsync(sc.center.p, center, (size_t)frames * sizeof(int), hipMemcpyHostToDevice, P -> stream));
+  const AlignGeo geo = around ? ALIGN_GEO_LINE : banded ? ALIGN_GEO_BAND : ALIGN_GEO_FULL;
   AlignDev d;
   d.code_a = (const float*)a -> arr[LLSM_GPU_CODE]; d.code_b = (const float*)b -> arr[LLSM_GPU_CODE];
   d.dim = a -> coder_os + a -> coder_ob + 3; d.first = o.first; d.count = o.count;
   d.step_cost = o.step_cost; d.voicing_cost = o.voicing_cost;
   d.pairs = sc.pairs.p; d.n_pairs = n_pairs;
-  int rc = launch_align_dist(P, banded, d, sc.tiles.p, (int)tiles.size(), sc.plane.p);
-  if(! rc) rc = slope ? launch_align_slope_dtw(P, banded, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames)
-                      : launch_align_dtw(P, banded, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames);
+  const int* lines = around ? sc.center.p : nullptr;
+  int rc = launch_align_dist(P, geo, d, sc.tiles.p, (int)tiles.size(), sc.plane.p, lines);
+  if(! rc) rc = slope ? launch_align_slope_dtw(P, geo, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames, lines)
+                      : launch_align_dtw(P, geo, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames, lines);
   if(rc) return refuse(std::string("launch failed: ") + hipGetErrorString((hipError_t)rc), who);
   // into memory of our own first: a failed copy leaves pos and cost untouched
   std::vector<float> host(n_out);
@@ -290,7 +383,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
 
 extern "C" int llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_FULL, nullptr, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_FULL, 0, nullptr, nullptr, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- inside a diagonal band (rules B1 - B4)
@@ -317,7 +410,7 @@ extern "C" int llsm_gpu_align_band_rows(int na, int nb, int band, int* lo, int* 
 
 extern "C" int llsm_gpu_batch_align_band(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_BAND, band, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_BAND, 0, nullptr, band, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- local slopes within [1/2, 2] (rules L1 - L4)
@@ -336,7 +429,7 @@ extern "C" int llsm_gpu_align_slope_rows(int na, int nb, int* lo, int* hi) {
 
 extern "C" int llsm_gpu_batch_align_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_SLOPE, nullptr, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_SLOPE, 0, nullptr, nullptr, opt, pos, cost);
 }
 
 // ---------------------------------------------------------------- the slope pattern inside the band (rules K1 - K4)
@@ -378,5 +471,93 @@ extern "C" int llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo,
 
 extern "C" int llsm_gpu_batch_align_band_slope(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_BAND | ALIGN_SLOPE, band, opt, pos, cost);
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_BAND | ALIGN_SLOPE, 0, nullptr, band, opt, pos, cost);
+}
+
+// ---------------------------------------------------------------- either pattern around a centre line (rules A1 - A3)
+namespace {
+// empty, or why the two host calls below refuse a pair, its pattern and its line
+std::string around_pair(int na, int nb, const int* center, int slope) {
+  if(na < 1 || nb < 1) return "na < 1 or nb < 1 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ")";
+  // (the sweeps hold a few words per row; a pair of more rows than a call has cells fits no call)
+  if(na > kMaxCells) return "na = " + std::to_string(na) + " exceeds 2^28, the cells of a call";
+  if(slope != 0 && slope != 1) return "slope = " + std::to_string(slope) + " is neither 0 nor 1";
+  if(! center) return "NULL center";
+  if(slope) {
+    const std::string bound = slope_bound(na, nb);
+    if(! bound.empty()) return std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound;
+  }
+  return line_fault(na, nb, center);
+}
+}  // namespace
+
+extern "C" int llsm_gpu_align_around_min(int na, int nb, const int* center, int slope) {
+  const char* who = "llsm_gpu_align_around_min";
+  const std::string why = around_pair(na, nb, center, slope);
+  if(! why.empty()) return refuse(why, who);
+  try { return slope ? around_slope_min(na, nb, center) : around_min(na, nb, center); }
+  catch(const std::bad_alloc&) { return refuse("out of memory for " + std::to_string(na) + " rows", who); }
+}
+
+extern "C" int llsm_gpu_align_around_rows(int na, int nb, const int* center, int band, int slope, int* lo, int* hi) {
+  const char* who = "llsm_gpu_align_around_rows";
+  const std::string why = around_pair(na, nb, center, slope);
+  if(! why.empty()) return refuse(why, who);
+  if(band < 0) return refuse("band < 0 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ", band = " + std::to_string(band) + ")", who);
+  auto unconnected = [&](int least) {
+    return refuse("a band of " + std::to_string(band) + " is not connected" + (slope ? " for the slope pattern" : "") + " around this line on " +
+      std::to_string(na) + " x " + std::to_string(nb) + " frames: llsm_gpu_align_around_min is " + std::to_string(least), who);
+  };
+  if(! slope) {
+    const int least = around_min(na, nb, center);
+    if(band < least) return unconnected(least);
+    for(int i = 0; i < na && (lo || hi); i ++) {
+      if(lo) lo[i] = (int)std::max((long long)center[i] - band, 0ll);
+      if(hi) hi[i] = (int)std::min((long long)center[i] + band, (long long)nb - 1);
+    }
+    return 0;
+  }
+  std::vector<int2> rows;
+  try { if(! band_slope_rows(na, nb, band, rows, center)) return unconnected(around_slope_min(na, nb, center)); }
+  catch(const std::bad_alloc&) { return refuse("out of memory for " + std::to_string(na) + " rows", who); }
+  for(int i = 0; i < na && (lo || hi); i ++) {
+    if(lo) lo[i] = rows[i].x;
+    if(hi) hi[i] = rows[i].y;
+  }
+  return 0;
+}
+
+// Every operation below is one float64 operation of llsm_gpu.h's recipe, in its order.
+extern "C" int llsm_gpu_align_center_line(int na_c, int nb_c, const FP_TYPE* pos_c, int na, int nb, int* center) {
+  const char* who = "llsm_gpu_align_center_line";
+  if(na_c < 1 || nb_c < 1 || na < 1 || nb < 1)
+    return refuse("a size below 1 (na_c = " + std::to_string(na_c) + ", nb_c = " + std::to_string(nb_c) + ", na = " + std::to_string(na) +
+      ", nb = " + std::to_string(nb) + ")", who);
+  if(! pos_c || ! center) return refuse("NULL pos_c or center", who);
+  for(int k = 0; k < na_c; k ++)
+    if(! (pos_c[k] >= 0 && pos_c[k] <= (FP_TYPE)(nb_c - 1)))         // (a NaN fails both comparisons)
+      return refuse("pos_c[" + std::to_string(k) + "] = " + std::to_string(pos_c[k]) + " is NaN or outside [0, " + std::to_string(nb_c - 1) + "]", who);
+  const double s = nb_c > 1 ? (double)(nb - 1) / (double)(nb_c - 1) : 0.0;
+  long long top = 0;
+  for(int i = 0; i < na; i ++) {
+    double y = pos_c[0];
+    if(na_c > 1 && na > 1) {
+      const double prod = (double)i * (double)(na_c - 1);
+      const double x = prod / (double)(na - 1);
+      const long long k = std::min((long long)std::floor(x), (long long)na_c - 2);
+      const double rise = (double)pos_c[k + 1] - (double)pos_c[k], frac = x - (double)k;
+      const double part = rise * frac;
+      y = (double)pos_c[k] + part;
+    }
+    const double scaled = y * s;
+    const long long c = (long long)std::floor(scaled + 0.5);
+    top = std::max(top, std::min((long long)nb - 1, std::max(0ll, c)));
+    center[i] = (int)top;
+  }
+  return 0;
+}
+
+extern "C" int llsm_gpu_batch_align_around(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
+  const int* utt_b, const int* center, const int* band, int slope, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
+  return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_AROUND | ALIGN_BAND, slope, center, band, opt, pos, cost);
 }

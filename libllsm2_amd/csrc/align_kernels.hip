@@ -1,11 +1,21 @@
 // align_kernels.hip -- alignment of utterance pairs: llsm_gpu_batch_align (rules D1 - D3: llsm_gpu.h),
 // llsm_gpu_batch_align_band (rules B1 - B4, section 25), llsm_gpu_batch_align_slope (rules L1 - L4, section 27; its planes are
 // k_align_dist_t's full ones) and llsm_gpu_batch_align_band_slope (rules K1 - K4, section 28; its planes are k_align_dist_t's
-// band ones); the path kernel of the last two, k_align_slope_dtw_t, is described above it; host side: align.cpp.  Three kernel
-// templates, each instantiated for the two geometries:
+// band ones); the path kernel of the last two, k_align_slope_dtw_t, is described above it; and llsm_gpu_batch_align_around
+// (rules A1 - A3, section 30), which runs the band instantiations of all three around a centre line of the caller's; host
+// side: align.cpp.  Three kernel templates, each instantiated for the three geometries (AlignGeo: kernels.h):
 //   full    row i spans columns 0 ... nb - 1 and is stored as it is: off = 0, width = nb, all of it known when compiling
-//   band    row i spans lo_i = max(off_i, 0) ... hi_i = min(off_i + 2 band, nb - 1), off_i = align_band_center(i) - band, and
-//           entry q of its row of the plane [na][width = 2 band + 1] is column off_i + q
+//   band    row i spans lo_i = max(off_i, 0) ... hi_i = min(off_i + 2 band, nb - 1), off_i = c_i - band with c_i =
+//           align_band_center(i), and entry q of its row of the plane [na][width = 2 band + 1] is column off_i + q
+//   line    the band with c_i read from a device table of ints, center[pair.pos0 + i] (align_center): one read-only load
+//           where the band computes -- per row of a tile in k_align_dist_t (the off[] staged in LDS), per lane and strip
+//           for its own row and the row above in the path kernels, and once per strip in the walks back -- so the step
+//           loops are the band's.  What is said of the band below holds for any line that does not decrease (rule A1), as
+//           it rests on two facts alone: all lanes of a strip count their steps from one wlo, and lo and hi of the rows do
+//           not decrease (without the slope pattern; with it the window is a reduction over the rows).  That covers the
+//           distance between the reads and the writes of the hand-over rows and that every entry of a band plane is
+//           written once: a row's entries are the columns off_i ... off_i + 2 band, all within the strip's tiles, which
+//           reach from the first row's off to the last row's off + 2 band.
 //
 //   k_align_dist_t   D1 / B2: the distance planes of all pairs in one launch.  A workgroup of 256 threads takes a tile of
 //                    64 x 64 cells of one pair's matrix from the host's tile table; wavefront w owns rows 16 w ... 16 w + 15
@@ -55,6 +65,13 @@
 #include "kernels.h"
 #include "dev_common.h"
 #include "launch.h"
+
+// c_i of pair p (0 <= i < na): rule B1's diagonal, computed, or with ALIGN_GEO_LINE rule A1's line, one load from the table
+template <int GEO>
+DEV int align_center(const int* __restrict__ center, const AlignPair& p, int i) {
+  if constexpr(GEO == ALIGN_GEO_LINE) return center[(size_t)p.pos0 + i];
+  else return align_band_center(i, p.na, p.nb);
+}
 
 // ---------------------------------------------------------------- D1: distance planes
 #define AD_NT 256
@@ -119,8 +136,10 @@ DEV void align_tile_sums(const float* __restrict__ A, const float* __restrict__ 
 
 // Lane l is on column j0 + l of the matrix, which with BAND may lie outside it; entry q = j - off_i of row i of the plane
 // is stored if it is within the row (full: q = j)
-template <bool BAND>
-__global__ __launch_bounds__(AD_NT) void k_align_dist_t(AlignDev d, const int4* __restrict__ tiles, float* __restrict__ plane) {
+template <int GEO>
+__global__ __launch_bounds__(AD_NT) void k_align_dist_t(AlignDev d, const int4* __restrict__ tiles, float* __restrict__ plane,
+  const int* __restrict__ center) {
+  constexpr bool BAND = GEO != ALIGN_GEO_FULL;
   __shared__ __attribute__((aligned(16))) float sa[ALIGN_TILE * AD_AS];
   __shared__ float sb[AD_KC * AD_BS];
   __shared__ int va[ALIGN_TILE], vb[ALIGN_TILE], off[BAND ? ALIGN_TILE : 1];
@@ -134,7 +153,7 @@ __global__ __launch_bounds__(AD_NT) void k_align_dist_t(AlignDev d, const int4* 
   if(tid < ALIGN_TILE) {
     const int i = min(i0 + tid, p.na - 1);
     va[tid] = A[(size_t)i * d.dim] > 0.5f;
-    if constexpr(BAND) off[tid] = align_band_center(i, p.na, p.nb) - p.band;
+    if constexpr(BAND) off[tid] = align_center<GEO>(center, p, i) - p.band;
   } else if(tid < 2 * ALIGN_TILE) {
     const int jb = min(j0 + tid - ALIGN_TILE, p.nb - 1);
     vb[tid - ALIGN_TILE] = B[(size_t)(BAND ? max(jb, 0) : jb) * d.dim] > 0.5f;
@@ -177,9 +196,10 @@ DEV void dtw_load(DtwBlock& b, const float* __restrict__ drow, const float* hand
   }
 }
 
-template <bool BAND>
+template <int GEO>
 __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* __restrict__ plane, uint4* __restrict__ moves,
-  float* __restrict__ hand_rows, float* __restrict__ out, int cost0) {
+  float* __restrict__ hand_rows, float* __restrict__ out, int cost0, const int* __restrict__ center) {
+  constexpr bool BAND = GEO != ALIGN_GEO_FULL;
   const int lane = threadIdx.x;
   const AlignPair p = d.pairs[blockIdx.x];
   const int na = p.na, nb = p.nb, band = p.band, width = BAND ? 2 * band + 1 : nb;
@@ -195,9 +215,9 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
     // BAND: the ranges of this lane's row and of the row above; an empty range (1, 0) where there is no such row
     int off = 0, lo = 1, hi = 0, plo = 1, phi = 0;
     if constexpr(BAND) if(i < na) {
-      const int c = align_band_center(i, na, nb);
+      const int c = align_center<GEO>(center, p, i);
       off = c - band; lo = max(off, 0); hi = min(c + band, nb - 1);
-      if(i > 0) { const int cp = align_band_center(i - 1, na, nb); plo = max(cp - band, 0); phi = min(cp + band, nb - 1); }
+      if(i > 0) { const int cp = align_center<GEO>(center, p, i - 1); plo = max(cp - band, 0); phi = min(cp + band, nb - 1); }
     }
     const int wlo = BAND ? __shfl(lo, 0) : 0, whi = BAND ? __shfl(hi, rows - 1) : nb - 1, nsteps = whi - wlo + rows;
     const float* drow = D + (size_t)min(i, na - 1) * width;
@@ -257,7 +277,7 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
   for(int guard = na + nb; guard > 0; guard --) {
     if(i == 0 && j == 0) break;
     const int s = i >> 6, l = i & (WAVE - 1);
-    if constexpr(BAND) if(s != cur_s) wlo = max(align_band_center(s * WAVE, na, nb) - band, 0);
+    if constexpr(BAND) if(s != cur_s) wlo = max(align_center<GEO>(center, p, s * WAVE) - band, 0);
     const int t = j - wlo + l, blk = t & ~(WAVE - 1);
     if(BAND && (t < 0 || t >= per_strip)) break;                      // (a cell outside the band: no stored move leads there)
     if(s != cur_s || blk != cur_b) {
@@ -311,11 +331,11 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
 // The walk back reads the masks as k_align_dtw_t does, finding a strip's wlo again as the forward pass found it.  Every move
 // leaves its row, so pos[i] follows from the cell and the move: columns j - 1 and j under move 2, else j alone; move 1 passes
 // (i - 1, j) and nothing else of row i - 1.  Each move lowers i and j by one at the least: at most min(na, nb) - 1 moves.
-// What BAND changes, each under `if constexpr`:
+// What BAND (either band geometry) changes, each under `if constexpr`:
 //   rows     <false> rule L1 from align_slope_row for rows i, i - 1 and i - 2; the ranges of rows i - 1 and i - 2 moved one
 //            column right are [a0, b0] and [a1, b1], and c0 is a0.  <true> the region's rows (rule K1) from the host's table,
 //            one {lo, hi} per row, an empty row lo > hi, loaded for the same three rows once per strip, and the band's rows
-//            p ... q from align_band_center; K3's comparisons fold into the three ranges: move 0 needs j - 1 in row i - 1 of
+//            p ... q from align_center (the diagonal or the line); K3's comparisons fold into the three ranges: move 0 needs j - 1 in row i - 1 of
 //            the region; move 1 needs j - 1 in row i - 2 of the region and j in row i - 1 of the band; move 2 needs j - 2 in
 //            row i - 1 of the region and j - 1 >= p_i (j - 1 <= q_i follows from j being in the region).  On a cell outside
 //            the band the sum above holds +infinity or a clamped read, and no candidate uses it: those comparisons ask for
@@ -348,9 +368,11 @@ DEV void band_slope_window(int lo, int hi, int nb, int& wlo, int& whi) {
   for(int o = WAVE / 2; o > 0; o >>= 1) { wlo = min(wlo, __shfl_xor(wlo, o)); whi = max(whi, __shfl_xor(whi, o)); }
 }
 
-template <bool BAND>
+template <int GEO>
 __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const float* __restrict__ plane,
-  const int2* __restrict__ region, uint4* __restrict__ moves, float* hand_rows, float* __restrict__ out, int cost0) {
+  const int2* __restrict__ region, uint4* __restrict__ moves, float* hand_rows, float* __restrict__ out, int cost0,
+  const int* __restrict__ center) {
+  constexpr bool BAND = GEO != ALIGN_GEO_FULL;
   const int lane = threadIdx.x;
   const AlignPair p = d.pairs[blockIdx.x];
   const int na = p.na, nb = p.nb, band = p.band, width = BAND ? 2 * band + 1 : nb;
@@ -372,7 +394,7 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
     if constexpr(BAND) {
       if(i < na) {
         const int2 r = tab[i];
-        const int c = align_band_center(i, na, nb);
+        const int c = align_center<GEO>(center, p, i);
         lo = r.x; hi = r.y; off = c - band;
         if(i >= 1) {
           const int2 r1 = tab[i - 1];
@@ -380,7 +402,7 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
         }
         if(i >= 2) {
           const int2 r2 = tab[i - 2];
-          const int cp = align_band_center(i - 1, na, nb);
+          const int cp = align_center<GEO>(center, p, i - 1);
           a1 = max(r2.x + 1, max(cp - band, 0)); b1 = min(r2.y + 1, min(cp + band, nb - 1));
         }
       }
@@ -483,24 +505,28 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
 }
 
 // ---------------------------------------------------------------- launchers
-int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* tiles, int n_tiles, float* plane) {
+int launch_align_dist(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const int4* tiles, int n_tiles, float* plane, const int* center) {
   if(n_tiles == 0) return 0;
-  if(band) LAUNCH("k_align_band_dist", k_align_dist_t<true>, dim3(n_tiles), dim3(AD_NT), 0, d, tiles, plane);
-  else LAUNCH("k_align_dist", k_align_dist_t<false>, dim3(n_tiles), dim3(AD_NT), 0, d, tiles, plane);
+  if(geo == ALIGN_GEO_LINE) LAUNCH("k_align_line_dist", k_align_dist_t<ALIGN_GEO_LINE>, dim3(n_tiles), dim3(AD_NT), 0, d, tiles, plane, center);
+  else if(geo == ALIGN_GEO_BAND) LAUNCH("k_align_band_dist", k_align_dist_t<ALIGN_GEO_BAND>, dim3(n_tiles), dim3(AD_NT), 0, d, tiles, plane, center);
+  else LAUNCH("k_align_dist", k_align_dist_t<ALIGN_GEO_FULL>, dim3(n_tiles), dim3(AD_NT), 0, d, tiles, plane, center);
   return 0;
 }
 
-int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0) {
+int launch_align_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0,
+  const int* center) {
   if(d.n_pairs == 0) return 0;
-  if(band) LAUNCH("k_align_band_dtw", k_align_dtw_t<true>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0);
-  else LAUNCH("k_align_dtw", k_align_dtw_t<false>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0);
+  if(geo == ALIGN_GEO_LINE) LAUNCH("k_align_line_dtw", k_align_dtw_t<ALIGN_GEO_LINE>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0, center);
+  else if(geo == ALIGN_GEO_BAND) LAUNCH("k_align_band_dtw", k_align_dtw_t<ALIGN_GEO_BAND>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0, center);
+  else LAUNCH("k_align_dtw", k_align_dtw_t<ALIGN_GEO_FULL>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0, center);
   return 0;
 }
 
-int launch_align_slope_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
-  float* row, float* out, int cost0) {
+int launch_align_slope_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
+  float* row, float* out, int cost0, const int* center) {
   if(d.n_pairs == 0) return 0;
-  if(band) LAUNCH("k_align_band_slope_dtw", k_align_slope_dtw_t<true>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0);
-  else LAUNCH("k_align_slope_dtw", k_align_slope_dtw_t<false>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0);
+  if(geo == ALIGN_GEO_LINE) LAUNCH("k_align_line_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_LINE>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
+  else if(geo == ALIGN_GEO_BAND) LAUNCH("k_align_band_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_BAND>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
+  else LAUNCH("k_align_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_FULL>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
   return 0;
 }

@@ -100,12 +100,16 @@ template <class T> struct DevBuf {
   void release() { llsm_dev_free(p); p = nullptr; n = 0; }        // callers synchronise the stream first
 };
 
-// The four alignment calls (align.cpp): two bits, inside a diagonal band and under the slope pattern.  A mode indexes the
-// batch's scratch sets and this table of the call's name and of its plane of llsm_gpu_batch_debug_plane.
-enum AlignMode { ALIGN_FULL = 0, ALIGN_BAND = 1, ALIGN_SLOPE = 2 };
+// The five alignment calls (align.cpp): two bits, inside a band and under the slope pattern, tell the first four apart, and
+// a third, ALIGN_AROUND, marks llsm_gpu_batch_align_around, whose band follows the caller's centre line and which is one call
+// for both patterns.  align_call(mode) indexes the batch's scratch sets and this table of the call's name and of its plane of
+// llsm_gpu_batch_debug_plane.
+enum AlignMode { ALIGN_FULL = 0, ALIGN_BAND = 1, ALIGN_SLOPE = 2, ALIGN_AROUND = 4 };
+enum { ALIGN_CALLS = 5 };
 struct AlignCall { const char* name; int plane; };
-static const AlignCall kAlignCalls[4] = {{"llsm_gpu_batch_align", 6}, {"llsm_gpu_batch_align_band", 9},
-  {"llsm_gpu_batch_align_slope", 12}, {"llsm_gpu_batch_align_band_slope", 13}};
+static const AlignCall kAlignCalls[ALIGN_CALLS] = {{"llsm_gpu_batch_align", 6}, {"llsm_gpu_batch_align_band", 9},
+  {"llsm_gpu_batch_align_slope", 12}, {"llsm_gpu_batch_align_band_slope", 13}, {"llsm_gpu_batch_align_around", 14}};
+static inline int align_call(int mode) { return mode & ALIGN_AROUND ? 4 : mode; }
 
 struct llsm_gpu_batch {
   llsm_gpu_context* ctx;
@@ -196,17 +200,19 @@ struct llsm_gpu_batch {
   // F0 tracking (llsm_gpu_batch_track_f0): the candidate plane of the last call, [total_frames][24] (plane 5 of
   // llsm_gpu_batch_debug_plane once a call has run), and one word of back pointers per frame -- grow-only
   DevBuf<float> f0_cand; DevBuf<unsigned> f0_bp; bool f0_cand_filled = false;
-  // alignment (align.cpp), scratch of the batch given as a, one set per call, indexed by the call's AlignMode, so that each
-  // of planes 6, 9, 12 and 13 (kAlignCalls) stays what the last call of its own kind left: the planes of the last
+  // alignment (align.cpp), scratch of the batch given as a, one set per call, indexed by align_call of its AlignMode, so that
+  // each of planes 6, 9, 12, 13 and 14 (kAlignCalls) stays what the last call of its own kind left: the planes of the last
   // successful call (`cells` floats, 0: no call yet), the row one strip of 64 rows hands to the next (two rows under the
   // slope pattern), the device block [pos of every pair | cost of every pair], the moves (2 bits per lane and step of the
-  // path kernel), the pair and tile tables and, under ALIGN_BAND | ALIGN_SLOPE alone, the rows of the region (rule K1: one
-  // {lo, hi} per row of every pair) -- all grow-only
+  // path kernel), the pair and tile tables, under ALIGN_BAND | ALIGN_SLOPE alone the rows of the region (rule K1: one
+  // {lo, hi} per row of every pair) and, under ALIGN_AROUND alone, the centre lines (rule A1: one int per row of every pair)
+  // -- all grow-only
   struct AlignScratch {
     DevBuf<float> plane, row, out; DevBuf<uint4> moves; DevBuf<AlignPair> pairs; DevBuf<int4> tiles; DevBuf<int2> region;
+    DevBuf<int> center;
     long long cells = 0;
-    void release() { plane.release(); row.release(); out.release(); moves.release(); pairs.release(); tiles.release(); region.release(); }
-  } align[4];
+    void release() { plane.release(); row.release(); out.release(); moves.release(); pairs.release(); tiles.release(); region.release(); center.release(); }
+  } align[ALIGN_CALLS];
   // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
   // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful
   // llsm_gpu_batch_select; sel_frames 0: no call yet), the back pointers (3 bits per state at bit 8 j, one word pair per

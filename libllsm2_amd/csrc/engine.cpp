@@ -632,12 +632,13 @@ extern "C" int llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq) {
 // llsm_gpu_batch_select_chain with this batch as t; only such a call writes them.  12: the distance planes of the last
 // successful llsm_gpu_batch_align_slope with this batch as a, pair after pair, each [na][nb]; only such a call writes it.
 // 13: the band planes of the last successful llsm_gpu_batch_align_band_slope with this batch as a, laid out as plane 9; only
-// such a call writes it.
+// such a call writes it.  14: the band planes of the last successful llsm_gpu_batch_align_around with this batch as a, laid
+// out as plane 9 around that call's centre lines; only such a call writes it.
 // dst == NULL: only the size.  Returns the number of floats of the plane, -1 without one.
 extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap) {
-  if(! b || which < 0 || which > 13) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
+  if(! b || which < 0 || which > 14) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
   int mode = -1;                                                      // of the alignment call whose plane `which` is
-  for(int m = 0; m < 4; m ++) if(kAlignCalls[m].plane == which) mode = m;
+  for(int m = 0; m < ALIGN_CALLS; m ++) if(kAlignCalls[m].plane == which) mode = m;
   DevBuf<float>& src = mode >= 0 ? b -> align[mode].plane :
                       which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : which == 3 ? b -> colored :
                       which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : which == 7 ? b -> sel_p7 : which == 8 ? b -> sel_p8 :

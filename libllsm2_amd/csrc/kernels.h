@@ -332,8 +332,9 @@ int launch_f0_median(LaunchCtx* P, const F0Dev& d, const float* raw, float* f0);
 // rules T2 - T5 over the candidate plane: f0[nframes]; bp: one word per frame of scratch
 int launch_f0_viterbi(LaunchCtx* P, const F0Dev& d, const float* plane, const F0Track& t, unsigned* bp, float* f0);
 
-// ---- alignment of utterance pairs: whole matrix, inside a diagonal band, whole matrix under the slope pattern, or the slope
-// pattern inside the band (align.cpp, align_kernels.hip; rules D1 - D3, B1 - B4, L1 - L4 and K1 - K4: llsm_gpu.h)
+// ---- alignment of utterance pairs: whole matrix, inside a diagonal band, whole matrix under the slope pattern, the slope
+// pattern inside the band, or either pattern inside a band around a centre line of the caller's (align.cpp,
+// align_kernels.hip; rules D1 - D3, B1 - B4, L1 - L4, K1 - K4 and A1 - A3: llsm_gpu.h)
 // The centre column of row i of an na x nb pair, rule B1: the diagonal rounded half up.  Row i spans columns
 // max(0, c - band) ... min(nb - 1, c + band); entry q of its row of the band plane is column c - band + q.
 __host__ __device__ static inline int align_band_center(int i, int na, int nb) {
@@ -354,20 +355,28 @@ __host__ __device__ static inline void align_slope_row(long long i, int na, int 
 // of the region (rule K1) start at entry pad of the table.
 struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
 #define ALIGN_TILE 64                                  // k_align_dist_t: cells per side of a workgroup's tile
+// The geometry of a row, which every kernel template is instantiated for: the whole matrix; the band of rule B1, whose
+// centre is align_band_center; the band of rule A1, whose centre c_i of pair p is center[p.pos0 + i] of a device table (the
+// pair's offset into pos is its offset into the concatenated centre lines): the last argument of the launchers, sum of na
+// ints, read under ALIGN_GEO_LINE alone.  It is an argument of its own behind the others, not a member of AlignDev, so
+// that the kernels of the other two geometries keep their argument layout and with it their machine code.
+enum AlignGeo { ALIGN_GEO_FULL = 0, ALIGN_GEO_BAND = 1, ALIGN_GEO_LINE = 2 };
 struct AlignDev {
   const float* code_a; const float* code_b; int dim, first, count; float step_cost, voicing_cost;
   const AlignPair* pairs; int n_pairs;
 };
 // D1 / B2: tiles[t] = (pair, first row, first column -- which may be negative in a band --, 0) of tile t; the planes of all
-// pairs in one launch, with `band` in the band layout, every entry written, +infinity where its column lies outside the matrix
-int launch_align_dist(LaunchCtx* P, bool band, const AlignDev& d, const int4* tiles, int n_tiles, float* plane);
+// pairs in one launch, under a band geometry in the band layout, every entry written, +infinity where its column lies outside
+// the matrix
+int launch_align_dist(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const int4* tiles, int n_tiles, float* plane, const int* center);
 // D2 - D3 / B3 - B4 over the planes, one wavefront per pair: out[pair.pos0 + i] = pos[i], out[cost0 + p] = cost of pair p
-int launch_align_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0);
-// L3 - L4 over whole-matrix planes or, with `band`, K3 - K4 over band planes, one wavefront per pair; region (read with
-// `band` alone): {lo, hi} of every row of every pair (an empty row: lo > hi), pair p's from entry pairs[p].pad; row: two
-// hand-over rows of nb floats per pair, out as above
-int launch_align_slope_dtw(LaunchCtx* P, bool band, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
-  float* row, float* out, int cost0);
+int launch_align_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0,
+  const int* center);
+// L3 - L4 over whole-matrix planes or, under a band geometry, K3 - K4 over band planes, one wavefront per pair; region (read
+// under a band geometry alone): {lo, hi} of every row of every pair (an empty row: lo > hi), pair p's from entry
+// pairs[p].pad; row: two hand-over rows of nb floats per pair, out as above
+int launch_align_slope_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
+  float* row, float* out, int cost0, const int* center);
 
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5 and C1 - C6: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame
