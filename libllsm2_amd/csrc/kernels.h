@@ -169,22 +169,8 @@ int launch_harm_pp(LaunchCtx* P, const BatchDev& d, const float* sig, size_t sig
   int* nhar_out, float* ampl, float* phse);
 int launch_rt_template(LaunchCtx* P, const float* colored, int ntemplate_ext, int nch, int nch_active,
   int ntemplate, int S, float* tpl);
-int launch_rt_rings(LaunchCtx* P, int S, float* mod, float* sinr, float* noiser, int cap, int nch,
-  int mod_curr, int sin_curr, int noise_curr, int nhop, int nwin, const float* envf,
-  const float* frames_sin, const float* f0, const int* has_nm, const int* nhar);
-int launch_rt_rings_excite(LaunchCtx* P, int S, float* mod, float* sinr, float* noiser, int cap, int nch,
-  int mod_curr, int sin_curr, int noise_curr, int nhop, int nwin, const float* envf, const float* frames_sin,
-  const float* f0, const int* has_nm, const int* nhar, const float* tpl, float* excr, int ntemplate, int exc_curr,
-  int exc_cycle, float* exc_frame);
-int launch_rt_excite(LaunchCtx* P, int S, const float* mod, const float* tpl, float* excr, int cap,
-  int nch, int ntemplate, int mod_curr, int exc_curr, int exc_cycle, int curr_nhop, int nx,
-  int nwin_frame, float* exc_frame);
-int launch_rt_mix(LaunchCtx* P, int S, float* noiser, const float* sinr, int cap, int noise_curr,
-  int sin_curr, int sin_pos, int nfft, const float* nframes_in, const int* live, int next_nhop,
-  int out_stride, float* out);
 
-// llsmrt: one hop in two launches (k_rt_front: envelope frames beside the harmonic frame, ring adds, excitation; k_rt_back:
-// noise filter of a pair of streams on four wavefronts, noise-ring add, the hop's output samples)
+// ---- llsmrt: one hop of one stream group (rt.cpp)
 // the per-stream parameter rows of a hop where the host packed them (pinned, device-mapped); f0 == nullptr: none
 struct RtPbpOp;
 struct RtRows {
@@ -194,22 +180,41 @@ struct RtRows {
 };
 // pulse-by-pulse bookkeeping of the hop inside k_rt_front / k_rt_hop (k_rt_pbp's arguments); ops == nullptr: none
 struct RtPbpArgs { RtPbpOp* ops; float* frwd; float* bkwd; int dual_curr; const float* pulse_out; int pulse_stride; };
-// host != nullptr: every workgroup first moves its stream's rows (as many harmonics as the frame has) from *host into
-// the device rows of d / cyc_shift / has_nm, then works on those
-int launch_rt_front(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, const float* f0_sin, const float* cyc_shift,
-  float* envf, float* frames_sin, int lds_harmonics, float* mod, float* sinr, float* noiser, int cap, int mod_curr,
-  int sin_curr, int noise_curr, int nhop, const int* has_nm, const float* tpl, float* excr, int ntemplate, int exc_curr,
-  int exc_cycle, float* exc_frame, const RtRows* host = nullptr, const RtPbpArgs* pbp = nullptr);
-int launch_rt_hop(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, const float* f0_sin, const float* cyc_shift,
-  float* envf, float* frames_sin, int lds_harmonics, float* mod, float* sinr, float* noiser, int cap, int mod_curr,
-  int sin_curr, int noise_curr, int nhop, const int* has_nm, const float* tpl, float* excr, int ntemplate, int exc_curr,
-  int exc_cycle, float* exc_frame, const RtRows* host, float fnyq_conf, float inv_wsqr, int N, int logN, const float2* tw,
-  int tw_nmax, float* nframes, int* live, int sin_pos, int next_nhop, int out_stride, float* out, const RtPbpArgs* pbp = nullptr,
-  bool on_chip = true);
-int launch_rt_back(LaunchCtx* P, const BatchDev& d, const float* exc_frame, float fnyq_conf, float fs_syn, int nwin,
-  const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax, float* nframes, int* live,
-  float* noiser, const float* sinr, int cap, int noise_curr, int sin_curr, int sin_pos, int next_nhop, int out_stride,
-  float* out);
+// Everything the device work of one hop reads.  rt.cpp fills one per hop (rt_hop_record); a launcher below unpacks it, and
+// is the only place that knows the parameter order of its kernel.
+struct RtHop {
+  // stream rows: the S streams as a batch of S one-frame "utterances" (d.f0: F0 of the envelope frames; f0_sin: of the
+  // harmonic frames -- the same row unless the buffer synthesises pulse by pulse)
+  BatchDev d; const float* f0_sin; const float* cyc_shift; const int* has_nm;
+  // window (Hann, nwin = 2 nhop) and the transform of the noise filter
+  int nwin; const float* win; float inv_wsqr; int N, logN; const float2* tw; int tw_nmax; float fnyq; int lds_harmonics;
+  // rings [S][cap] (mod: [S][nchannel][cap]) and their cursors as the kernels of THIS hop must see them (the dual buffer's:
+  // pbp.dual_curr); excitation templates [S][nchannel][ntemplate]
+  float *mod, *sinr, *noiser, *excr; int cap;
+  int mod_curr, sin_curr, noise_curr, exc_curr, exc_cycle, sin_pos;
+  const float* tpl; int ntemplate;
+  // temporaries of the hop (k_rt_hop2 keeps them on chip); hop lengths and the output rows [S][2][out_stride]
+  float *envf, *frames_sin, *exc_frame, *nframes; int* live;
+  int nhop, next_nhop, out_stride; float* out;
+  // host.f0 != nullptr: every workgroup first moves its stream's rows (as many harmonics as the frame has) from the pinned
+  // rows into the device rows of d / cyc_shift / has_nm, then works on those
+  RtRows host; RtPbpArgs pbp;
+};
+// The form a hop takes under llsm_gpu_rt_fused(mode): five single-purpose launches (mode 0); k_rt_front + k_rt_back (1, and
+// 2 / 3 where the LDS of one launch does not hold the transform); k_rt_hop (2); k_rt_hop2, the hop's temporaries on chip
+// (3, where its per-thread slots and its LDS hold the hop; else k_rt_hop)
+enum RtHopForm { RT_HOP_FIVE, RT_HOP_TWO, RT_HOP_ONE, RT_HOP_CHIP };
+RtHopForm rt_hop_form(const RtHop& h, int mode);
+int launch_rt_front(LaunchCtx* P, const RtHop& h);    // envelope frames beside the harmonic frame, ring adds, excitation
+int launch_rt_back(LaunchCtx* P, const RtHop& h);     // noise filter of a pair of streams, noise-ring add, output samples
+int launch_rt_hop(LaunchCtx* P, const RtHop& h);      // RT_HOP_ONE: both halves in one launch
+int launch_rt_hop2(LaunchCtx* P, const RtHop& h);     // RT_HOP_CHIP
+// the single-purpose kernels.  launch_rt_rings and launch_rt_excite also run outside a hop (rt.cpp blank_heads,
+// reset_state) on a record of which they read the rings, cursors and rows only; the excitation mixer's span is explicit
+int launch_rt_rings(LaunchCtx* P, const RtHop& h);
+int launch_rt_rings_excite(LaunchCtx* P, const RtHop& h);
+int launch_rt_excite(LaunchCtx* P, const RtHop& h, int curr_nhop, int nx, int nwin_frame);
+int launch_rt_mix(LaunchCtx* P, const RtHop& h);
 
 
 // ---- layer 1 / pulse-by-pulse synthesis (l1_kernels.hip) ----
@@ -242,8 +247,7 @@ struct PbpSeg { double state, rate; int j0, j1, dir, len; int out_off, pad; };
 
 // llsmrt, PbP path: per-stream operations of one hop on the dual (pulse) buffer and the sinusoid ring
 struct RtPbpOp { int add_off, add_size, rd_off, rd_on, term_off, term_size, pad0, pad1; };
-int launch_rt_pbp(LaunchCtx* P, int S, const RtPbpOp* ops, float* frwd, float* bkwd, int cap, int dual_curr,
-  float* sinr, int sin_curr, int nhop, const float* win, const float* pulse_out, int pulse_stride);
+int launch_rt_pbp(LaunchCtx* P, const RtHop& h);       // k_rt_pbp on h.pbp (the five-launch form; the others carry it)
 int launch_coder_encode(LaunchCtx* P, int order_spec, int order_bap, int ns, int npsd, float fnyq, float liprad,
   const float* melaxis, int nframes, const float* f0, const float* rd, const float* psd, const float* vtmagn,
   const int* nvsphse, float* enc);

@@ -4389,128 +4389,107 @@ int launch_rt_template(LaunchCtx* P, const float* colored, int ntemplate_ext, in
     colored, ntemplate_ext, nch, nch_active, ntemplate, tpl);
   return 0;
 }
-int launch_rt_rings(LaunchCtx* P, int S, float* mod, float* sinr, float* noiser, int cap, int nch,
-  int mod_curr, int sin_curr, int noise_curr, int nhop, int nwin, const float* envf,
-  const float* frames_sin, const float* f0, const int* has_nm, const int* nhar) {
-  LAUNCH("k_rt_rings", k_rt_rings, dim3(S), dim3(256), 0, mod, sinr, noiser, cap, nch, mod_curr,
-    sin_curr, noise_curr, nhop, nwin, envf, frames_sin, f0, has_nm, nhar);
+// llsmrt, one hop (kernels.h RtHop): each launcher unpacks the record into the parameter order of its kernel
+int launch_rt_rings(LaunchCtx* P, const RtHop& h) {
+  LAUNCH("k_rt_rings", k_rt_rings, dim3(h.d.nframes), dim3(256), 0, h.mod, h.sinr, h.noiser, h.cap, h.d.nchannel, h.mod_curr,
+    h.sin_curr, h.noise_curr, h.nhop, h.nwin, h.envf, h.frames_sin, h.f0_sin, h.has_nm, h.d.nhar);
   return 0;
 }
-int launch_rt_excite(LaunchCtx* P, int S, const float* mod, const float* tpl, float* excr, int cap,
-  int nch, int ntemplate, int mod_curr, int exc_curr, int exc_cycle, int curr_nhop, int nx,
-  int nwin_frame, float* exc_frame) {
-  LAUNCH("k_rt_excite", k_rt_excite, dim3(S), dim3(256), 0, mod, tpl, excr, cap, nch, ntemplate,
-    mod_curr, exc_curr, exc_cycle, curr_nhop, nx, nwin_frame, exc_frame);
+int launch_rt_excite(LaunchCtx* P, const RtHop& h, int curr_nhop, int nx, int nwin_frame) {
+  LAUNCH("k_rt_excite", k_rt_excite, dim3(h.d.nframes), dim3(256), 0, h.mod, h.tpl, h.excr, h.cap, h.d.nchannel, h.ntemplate,
+    h.mod_curr, h.exc_curr, h.exc_cycle, curr_nhop, nx, nwin_frame, h.exc_frame);
   return 0;
 }
-int launch_rt_rings_excite(LaunchCtx* P, int S, float* mod, float* sinr, float* noiser, int cap, int nch,
-  int mod_curr, int sin_curr, int noise_curr, int nhop, int nwin, const float* envf, const float* frames_sin,
-  const float* f0, const int* has_nm, const int* nhar, const float* tpl, float* excr, int ntemplate, int exc_curr,
-  int exc_cycle, float* exc_frame) {
-  LAUNCH("k_rt_rings_excite", k_rt_rings_excite, dim3(S), dim3(256), 0, mod, sinr, noiser, cap, nch, mod_curr, sin_curr,
-    noise_curr, nhop, nwin, envf, frames_sin, f0, has_nm, nhar, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame);
+int launch_rt_rings_excite(LaunchCtx* P, const RtHop& h) {
+  LAUNCH("k_rt_rings_excite", k_rt_rings_excite, dim3(h.d.nframes), dim3(256), 0, h.mod, h.sinr, h.noiser, h.cap, h.d.nchannel,
+    h.mod_curr, h.sin_curr, h.noise_curr, h.nhop, h.nwin, h.envf, h.frames_sin, h.f0_sin, h.has_nm, h.d.nhar, h.tpl, h.excr,
+    h.ntemplate, h.exc_curr, h.exc_cycle, h.exc_frame);
   return 0;
 }
-int launch_rt_mix(LaunchCtx* P, int S, float* noiser, const float* sinr, int cap, int noise_curr,
-  int sin_curr, int sin_pos, int nfft, const float* nframes_in, const int* live, int next_nhop,
-  int out_stride, float* out) {
-  LAUNCH("k_rt_mix", k_rt_mix, dim3(S), dim3(256), 0, noiser, sinr, cap, noise_curr, sin_curr,
-    sin_pos, nfft, nframes_in, live, next_nhop, out_stride, out);
+int launch_rt_mix(LaunchCtx* P, const RtHop& h) {
+  LAUNCH("k_rt_mix", k_rt_mix, dim3(h.d.nframes), dim3(256), 0, h.noiser, h.sinr, h.cap, h.noise_curr, h.sin_curr,
+    h.sin_pos, h.N, h.nframes, h.live, h.next_nhop, h.out_stride, h.out);
   return 0;
 }
 
 // the <NCH, ME, NTS> instantiation of a hop kernel: the envelope shape of the streams and the column tiles of their frames
 template <class F>
-static int with_rt_shape(const BatchDev& d, const SynthTiles& t, F&& f) {
-  return with_env_shape(d.nchannel, d.maxnhar_e, [&](auto nch, auto me) {
-    return with_tiles(t.NT, [&](auto nts) { return f(nch, me, nts); });
+static int with_rt_shape(const RtHop& h, F&& f) {
+  const SynthTiles t = synth_tiles(h.nwin);
+  return with_env_shape(h.d.nchannel, h.d.maxnhar_e, [&](auto nch, auto me) {
+    return with_tiles(t.NT, [&](auto nts) { return f(nch, me, nts, t); });
   });
 }
-// llsmrt, one hop in two launches (k_rt_front, k_rt_back).  d: the per-stream rows as a batch of S one-frame "utterances".
-int launch_rt_front(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, const float* f0_sin, const float* cyc_shift,
-  float* envf, float* frames_sin, int lds_harmonics, float* mod, float* sinr, float* noiser, int cap, int mod_curr,
-  int sin_curr, int noise_curr, int nhop, const int* has_nm, const float* tpl, float* excr, int ntemplate, int exc_curr,
-  int exc_cycle, float* exc_frame, const RtRows* host, const RtPbpArgs* pbp) {
-  const int S = d.nframes;
-  if(S == 0) return 0;
-  RtRows hr; std::memset(& hr, 0, sizeof(hr));
-  if(host) hr = *host;
-  RtPbpArgs pa; std::memset(& pa, 0, sizeof(pa));
-  if(pbp) pa = *pbp;
-  const SynthTiles t = synth_tiles(nwin);
-  const size_t lds = (lds_harmonics + 4) * sizeof(float2);
-  return with_rt_shape(d, t, [&](auto nch, auto me, auto nts) {
-    LAUNCH("k_rt_front", (k_rt_front<nch, me, nts>), dim3(S), dim3(256), lds,
-      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, envf,
-      f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, cyc_shift, frames_sin, mod, sinr, noiser, cap, mod_curr, sin_curr,
-      noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame, hr, d.npsd, d.psd, pa);
+// LDS of k_rt_hop (the harmonic frames of a pair of streams, then the pair's transform; both multiples of 16) and of k_rt_hop2
+static size_t rt_hop_lds(const RtHop& h) {
+  return std::max((size_t)2 * (h.lds_harmonics + 4) * sizeof(float2), nf_pair_lds(h.N, h.d.npsd));
+}
+static size_t rt_hop2_lds(const RtHop& h) {
+  const int nx0 = std::max(h.N, 2 * (h.lds_harmonics + 4)), nch = h.d.nchannel, me_rt = h.d.maxnhar_e > 0 ? h.d.maxnhar_e : 1;
+  return nf_pair_lds(h.N, h.d.npsd, (size_t)(nx0 - h.N) * sizeof(float2) +
+    ((size_t)2 * nch * h.nwin + 5 * (size_t)h.nwin + 2 * (size_t)(nch + 2 * nch * me_rt) + 8) * sizeof(float));
+}
+RtHopForm rt_hop_form(const RtHop& h, int mode) {
+  if(mode <= 0) return RT_HOP_FIVE;
+  // one launch: its LDS holds transforms up to 2 048 points (the rows of N = 4 096 alone are 8 bytes over the 64 KB)
+  if(mode == 1 || rt_hop_lds(h) > 64 * 1024) return RT_HOP_TWO;
+  // the on-chip form where its per-thread slots and its LDS fit
+  const int nhop_now = h.nwin / 2, me_rt = h.d.maxnhar_e > 0 ? h.d.maxnhar_e : 1;
+  const bool chip = mode > 2 && h.nwin == 2 * nhop_now && h.nwin <= 256 * RT2_JW && nhop_now <= 512 && h.N <= 256 * 2 * RT2_JN &&
+    h.N > nhop_now && h.next_nhop <= 512 && h.next_nhop <= h.N && h.N < h.cap && h.nwin < h.cap && nhop_now < h.ntemplate &&
+    h.d.nchannel * me_rt <= 256 && h.d.npsd <= 1024 && rt_hop2_lds(h) <= 64 * 1024;
+  return chip ? RT_HOP_CHIP : RT_HOP_ONE;
+}
+int launch_rt_front(LaunchCtx* P, const RtHop& h) {
+  const BatchDev& d = h.d;
+  if(d.nframes == 0) return 0;
+  return with_rt_shape(h, [&](auto nch, auto me, auto nts, const SynthTiles& t) {
+    LAUNCH("k_rt_front", (k_rt_front<nch, me, nts>), dim3(d.nframes), dim3(256), (h.lds_harmonics + 4) * sizeof(float2),
+      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, h.nwin, h.win, h.envf,
+      h.f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, h.cyc_shift, h.frames_sin, h.mod, h.sinr, h.noiser, h.cap,
+      h.mod_curr, h.sin_curr, h.noise_curr, h.nhop, h.has_nm, h.tpl, h.excr, h.ntemplate, h.exc_curr, h.exc_cycle, h.exc_frame,
+      h.host, d.npsd, d.psd, h.pbp);
     return 0;
   });
 }
-int launch_rt_back(LaunchCtx* P, const BatchDev& d, const float* exc_frame, float fnyq_conf, float fs_syn, int nwin,
-  const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax, float* nframes, int* live,
-  float* noiser, const float* sinr, int cap, int noise_curr, int sin_curr, int sin_pos, int next_nhop, int out_stride,
-  float* out) {
-  const int S = d.nframes;
+int launch_rt_back(LaunchCtx* P, const RtHop& h) {
+  const BatchDev& d = h.d; const int S = d.nframes;
   if(S == 0) return 0;
-  LAUNCH("k_rt_back", k_rt_back, dim3((S + 1) / 2), dim3(256), nf_pair_lds(N, d.npsd), exc_frame, S, d.psd, d.psdres, d.has_psdres, d.npsd,
-    fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, N, logN, tw, tw_nmax, nframes, live, noiser, sinr, cap, noise_curr,
-    sin_curr, sin_pos, next_nhop, out_stride, out);
+  LAUNCH("k_rt_back", k_rt_back, dim3((S + 1) / 2), dim3(256), nf_pair_lds(h.N, d.npsd), h.exc_frame, S, d.psd, d.psdres,
+    d.has_psdres, d.npsd, h.fnyq, d.thop, d.fs, h.nwin, h.win, h.inv_wsqr, h.N, h.logN, h.tw, h.tw_nmax, h.nframes, h.live,
+    h.noiser, h.sinr, h.cap, h.noise_curr, h.sin_curr, h.sin_pos, h.next_nhop, h.out_stride, h.out);
   return 0;
 }
-
-// llsmrt, one hop in ONE launch (harmonic-model buffers): the arguments of launch_rt_front and launch_rt_back
-int launch_rt_hop(LaunchCtx* P, const BatchDev& d, int nwin, const float* win, const float* f0_sin, const float* cyc_shift,
-  float* envf, float* frames_sin, int lds_harmonics, float* mod, float* sinr, float* noiser, int cap, int mod_curr,
-  int sin_curr, int noise_curr, int nhop, const int* has_nm, const float* tpl, float* excr, int ntemplate, int exc_curr,
-  int exc_cycle, float* exc_frame, const RtRows* host, float fnyq_conf, float inv_wsqr, int N, int logN, const float2* tw,
-  int tw_nmax, float* nframes, int* live, int sin_pos, int next_nhop, int out_stride, float* out, const RtPbpArgs* pbp,
-  bool on_chip) {
-  const int S = d.nframes;
+int launch_rt_hop2(LaunchCtx* P, const RtHop& h) {
+  const BatchDev& d = h.d; const int S = d.nframes, cap = h.cap;
   if(S == 0) return 0;
-  RtRows hr; std::memset(& hr, 0, sizeof(hr));
-  if(host) hr = *host;
-  RtPbpArgs pa; std::memset(& pa, 0, sizeof(pa));
-  if(pbp) pa = *pbp;
-  const SynthTiles t = synth_tiles(nwin);
-  const int lds_half = lds_harmonics + 4;
-  const size_t lds = std::max((size_t)2 * lds_half * sizeof(float2), nf_pair_lds(N, d.npsd));   // both multiples of 16
-  if(lds > 64 * 1024) return -1002;
-  // the on-chip form (k_rt_hop2) where its per-thread slots and its LDS fit
-  const bool hop2_ok = on_chip;
-  {
-    const int nx0 = std::max(N, 2 * lds_half);
-    const int me_rt = d.maxnhar_e > 0 ? d.maxnhar_e : 1;
-    const size_t lds2 = nf_pair_lds(N, d.npsd, (size_t)(nx0 - N) * sizeof(float2) +
-      ((size_t)2 * d.nchannel * nwin + 5 * (size_t)nwin + 2 * (size_t)(d.nchannel + 2 * d.nchannel * me_rt) + 8) * sizeof(float));
-    const int nhop_now = nwin / 2;
-    if(hop2_ok && nwin == 2 * nhop_now && nwin <= 256 * RT2_JW && nhop_now <= 512 && N <= 256 * 2 * RT2_JN && N > nhop_now &&
-       next_nhop <= 512 && next_nhop <= N && N < cap && nwin < cap && nhop_now < ntemplate && d.nchannel * me_rt <= 256 &&
-       d.npsd <= 1024 &&
-       lds2 <= 64 * 1024) {
-      // the sinusoid samples a hop hands out lie behind the window it adds to (sin_pos is negative enough) unless the hop
-      // length jumped; pulse-by-pulse buffers add to the ring at positions of their own: those read them at the end
-      const int early_out = (sin_pos + next_nhop <= -nwin && ! pa.ops) ? 1 : 0;
-      auto ring_host = [cap](int curr, int lag) { return ((curr + lag) % cap + cap) % cap; };
-      RtRingBase rb;
-      rb.mod0 = ring_host(mod_curr, -nwin); rb.sin0 = ring_host(sin_curr, -nwin); rb.exc0 = ring_host(exc_curr, -nwin);
-      rb.noi0 = ring_host(noise_curr, -N); rb.out0 = ring_host(sin_curr, sin_pos); rb.tpl0 = exc_cycle % ntemplate;
-      return with_rt_shape(d, t, [&](auto nch, auto me, auto nts) {
-        LAUNCH("k_rt_hop2", (k_rt_hop2<nch, me, nts>), dim3((S + 1) / 2), dim3(512), lds2,
-          d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win,
-          f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, cyc_shift, mod, sinr, noiser, cap, mod_curr, sin_curr,
-          noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, hr, d.npsd, d.psd, lds_half,
-          S, d.psdres, d.has_psdres, fnyq_conf, inv_wsqr, N, logN, tw, tw_nmax, sin_pos, next_nhop, out_stride, out, pa, early_out, rb);
-        return 0;
-      });
-    }
-  }
-  return with_rt_shape(d, t, [&](auto nch, auto me, auto nts) {
-    LAUNCH("k_rt_hop", (k_rt_hop<nch, me, nts>), dim3((S + 1) / 2), dim3(512), lds,
-      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, nwin, win, envf,
-      f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, cyc_shift, frames_sin, mod, sinr, noiser, cap, mod_curr, sin_curr,
-      noise_curr, nhop, has_nm, tpl, excr, ntemplate, exc_curr, exc_cycle, exc_frame, hr, d.npsd, d.psd, lds_half,
-      S, d.psdres, d.has_psdres, fnyq_conf, inv_wsqr, N, logN, tw, tw_nmax, nframes, live, sin_pos, next_nhop, out_stride, out, pa);
+  // the sinusoid samples a hop hands out lie behind the window it adds to (sin_pos is negative enough) unless the hop
+  // length jumped; pulse-by-pulse buffers add to the ring at positions of their own: those read them at the end
+  const int early_out = (h.sin_pos + h.next_nhop <= -h.nwin && ! h.pbp.ops) ? 1 : 0;
+  auto ring_host = [cap](int curr, int lag) { return ((curr + lag) % cap + cap) % cap; };
+  RtRingBase rb;
+  rb.mod0 = ring_host(h.mod_curr, -h.nwin); rb.sin0 = ring_host(h.sin_curr, -h.nwin); rb.exc0 = ring_host(h.exc_curr, -h.nwin);
+  rb.noi0 = ring_host(h.noise_curr, -h.N); rb.out0 = ring_host(h.sin_curr, h.sin_pos); rb.tpl0 = h.exc_cycle % h.ntemplate;
+  return with_rt_shape(h, [&](auto nch, auto me, auto nts, const SynthTiles& t) {
+    LAUNCH("k_rt_hop2", (k_rt_hop2<nch, me, nts>), dim3((S + 1) / 2), dim3(512), rt_hop2_lds(h),
+      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, h.nwin, h.win,
+      h.f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, h.cyc_shift, h.mod, h.sinr, h.noiser, h.cap, h.mod_curr,
+      h.sin_curr, h.noise_curr, h.nhop, h.has_nm, h.tpl, h.excr, h.ntemplate, h.exc_curr, h.exc_cycle, h.host, d.npsd, d.psd,
+      h.lds_harmonics + 4, S, d.psdres, d.has_psdres, h.fnyq, h.inv_wsqr, h.N, h.logN, h.tw, h.tw_nmax, h.sin_pos, h.next_nhop,
+      h.out_stride, h.out, h.pbp, early_out, rb);
+    return 0;
+  });
+}
+int launch_rt_hop(LaunchCtx* P, const RtHop& h) {
+  const BatchDev& d = h.d; const int S = d.nframes;
+  if(S == 0) return 0;
+  return with_rt_shape(h, [&](auto nch, auto me, auto nts, const SynthTiles& t) {
+    LAUNCH("k_rt_hop", (k_rt_hop<nch, me, nts>), dim3((S + 1) / 2), dim3(512), rt_hop_lds(h),
+      d.f0, d.nhar_e, d.eenv_ampl, d.eenv_phse, d.edc, d.nchannel, d.maxnhar_e, d.fs, h.nwin, h.win, h.envf,
+      h.f0_sin, d.nhar, d.ampl, d.phse, d.maxnhar, d.thop, t.L, h.cyc_shift, h.frames_sin, h.mod, h.sinr, h.noiser, h.cap,
+      h.mod_curr, h.sin_curr, h.noise_curr, h.nhop, h.has_nm, h.tpl, h.excr, h.ntemplate, h.exc_curr, h.exc_cycle, h.exc_frame,
+      h.host, d.npsd, d.psd, h.lds_harmonics + 4, S, d.psdres, d.has_psdres, h.fnyq, h.inv_wsqr, h.N, h.logN, h.tw, h.tw_nmax,
+      h.nframes, h.live, h.sin_pos, h.next_nhop, h.out_stride, h.out, h.pbp);
     return 0;
   });
 }

@@ -1435,10 +1435,9 @@ int launch_pbp_pulse(LaunchCtx* P, const L1Dev& d, const PbpJob* jobs, int njobs
   if(njobs <= PBP_WIDE_BELOW) return real ? go(int_c<256>{}, std::true_type{}) : go(int_c<256>{}, std::false_type{});
   return real ? go(int_c<PBP_NT>{}, std::true_type{}) : go(int_c<PBP_NT>{}, std::false_type{});
 }
-int launch_rt_pbp(LaunchCtx* P, int S, const RtPbpOp* ops, float* frwd, float* bkwd, int cap, int dual_curr,
-  float* sinr, int sin_curr, int nhop, const float* win, const float* pulse_out, int pulse_stride) {
-  LAUNCH("k_rt_pbp", k_rt_pbp, dim3(S), dim3(256), 0, ops, frwd, bkwd, cap, dual_curr, sinr, sin_curr, nhop, win,
-    pulse_out, pulse_stride);
+int launch_rt_pbp(LaunchCtx* P, const RtHop& h) {
+  LAUNCH("k_rt_pbp", k_rt_pbp, dim3(h.d.nframes), dim3(256), 0, h.pbp.ops, h.pbp.frwd, h.pbp.bkwd, h.cap, h.pbp.dual_curr,
+    h.sinr, h.sin_curr, h.nhop, h.win, h.pbp.pulse_out, h.pbp.pulse_stride);
   return 0;
 }
 int launch_l1_projection(LaunchCtx* P, const L1Dev& d, double fs, double* proj) {

@@ -201,12 +201,25 @@ void update_cycle(RtBuffer* b) {
   b -> noise_curr = (b -> noise_curr + b -> curr_nhop) % b -> ninternal;
 }
 
+// The part of a hop record (kernels.h RtHop) that is the buffer's own: streams, rings and their cursors as they stand,
+// templates, temporaries.  All a launch outside a hop needs; rt_hop_record adds the rest.
+RtHop rt_ring_record(const RtBuffer* b) {
+  RtHop h; std::memset(& h, 0, sizeof(h));
+  h.d.n_utt = h.d.nframes = b -> S; h.d.nchannel = b -> nchannel;
+  h.mod = b -> mod.p; h.sinr = b -> sinr.p; h.noiser = b -> noiser.p; h.excr = b -> excr.p; h.cap = b -> ninternal;
+  h.mod_curr = b -> mod_curr; h.sin_curr = b -> sin_curr; h.noise_curr = b -> noise_curr; h.exc_curr = b -> exc_curr;
+  h.exc_cycle = b -> exc_cycle; h.sin_pos = b -> sin_pos; h.tpl = b -> tpl.p; h.ntemplate = b -> ntemplate;
+  h.envf = b -> envf.p; h.frames_sin = b -> frames_sin.p; h.exc_frame = b -> exc_frame.p; h.nframes = b -> nframes.p; h.live = b -> live.p;
+  return h;
+}
+
 // zero the curr_nhop samples before the ring heads (what llsm_ringbuffer_appendblank leaves behind when no
 // feed follows): the ring kernel of a hop with no voiced / noise-model stream does exactly that
 bool blank_heads(RtBuffer* b, LaunchCtx* P) {
-  return launch_rt_rings(P, b -> S, b -> mod.p, b -> sinr.p, b -> noiser.p, b -> ninternal, b -> nchannel, b -> mod_curr,
-    b -> sin_curr, b -> noise_curr, b -> curr_nhop, 2 * b -> curr_nhop, b -> envf.p, b -> frames_sin.p, b -> d_psdres.p,
-    b -> d_zero.p, b -> d_zero.p) == 0;
+  RtHop h = rt_ring_record(b); h.nhop = b -> curr_nhop; h.nwin = 2 * b -> curr_nhop;
+  h.f0_sin = b -> d_psdres.p;                           // a row of zeros: no stream is voiced, ...
+  h.has_nm = b -> d_zero.p; h.d.nhar = b -> d_zero.p;   // ... has a noise model or harmonics
+  return launch_rt_rings(P, h) == 0;
 }
 
 // device-side state of llsm_create_rtsynth_buffer (llsmrt.c:186-221); `create` = 0: llsm_rtsynth_buffer_clear
@@ -260,8 +273,8 @@ bool reset_state(RtBuffer* b, bool create) {
   for(int i = 0; i < 5; i ++) {
     const int nx = b -> ninternal / 5;
     b -> exc_curr = (b -> exc_curr + nx) % cap;
-    if(launch_rt_excite(P, S, b -> mod.p, b -> tpl.p, b -> excr.p, cap, nch, b -> ntemplate, b -> mod_curr,
-         b -> exc_curr, b -> exc_cycle, b -> curr_nhop, nx, 0, nullptr)) return fail("llsmrt: k_rt_excite launch failed");
+    RtHop h = rt_ring_record(b); h.exc_frame = nullptr;   // (a frame length of 0: the ring alone is filled)
+    if(launch_rt_excite(P, h, b -> curr_nhop, nx, 0)) return fail("llsmrt: k_rt_excite launch failed");
     b -> exc_cycle = (b -> exc_cycle + nx) % b -> ntemplate;
   }
   return hipStreamSynchronize(st) == hipSuccess;
@@ -664,50 +677,48 @@ std::mutex g_pack_pool_mx;                              // one feed at a time us
 const int kPackMin = [] { const char* e = std::getenv("LLSM_RT_PACK_MIN"); const int v = (e && *e) ? std::atoi(e) : 128; return v > 1 ? v : 2; }();
 }
 
-// One hop for every stream of the group: frames[s] is the frame of stream s (llsmrt.c:505-521).
-static void feed_group(RtBuffer* b, llsm_container** frames, bool force_pipe = false) {
-  // LLSM_TIMING=1: phase times of a feed (packing the frames | enqueue | device + completion | rings and prev_nm),
-  // averaged over 200 hops, on stderr
-  static const bool timing = std::getenv("LLSM_TIMING") != nullptr;
+// LLSM_TIMING=1: phase times of a feed (packing the frames | enqueue | device + completion | rings and prev_nm),
+// averaged over 200 hops, on stderr
+using RtTime = std::chrono::steady_clock::time_point;
+static bool rt_timing() { static const bool on = std::getenv("LLSM_TIMING") != nullptr; return on; }
+static RtTime now() { return std::chrono::steady_clock::now(); }
+static double us(RtTime a, RtTime c) { return std::chrono::duration<double, std::micro>(c - a).count(); }
+static thread_local double pack_sched = 0, pack_copy = 0;            // inside `pack`: pulse trackers | layer-1 row copies
+static void report_timing(RtBuffer* b, RtTime t_0, RtTime t_1, RtTime t_2, RtTime t_3) {
   static thread_local double acc[4] = {0, 0, 0, 0}; static thread_local int nacc = 0;
-  static thread_local double pack_sched = 0, pack_copy = 0;          // inside `pack`: pulse trackers | layer-1 row copies
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) {
-    return std::chrono::duration<double, std::micro>(c - a).count(); };
-  // Pipelined feeds (llsm_gpu_rt_pipeline): the previous hop may still be on the device.  It used the OTHER copy of the
-  // pinned blocks, so this hop is packed and enqueued behind it first and the previous hop's samples are appended
-  // after that (complete_pending below) -- the device goes from one hop's kernel to the next without waiting for the host.
-  const bool pipe = force_pipe || g_rt_pipeline.load() > 0;   // (force_pipe: the inner hops of llsm_rtsynth_group_feed_many)
-  if(! pipe) complete_pending(b);
-  const auto t_0 = now();
-  (void)hipSetDevice(llsm_engine_device(b -> ctx));
-  LaunchCtx* P = llsm_engine_launch_ctx(b -> ctx);
-  update_cycle(b);
-  b -> h_params = b -> h_params0 + (size_t)b -> blk * b -> params_bytes;
-  for(auto& v : b -> h_views) {                         // (memcpy: the views are float* / int* / struct pointers behind void**)
-    void* q = (void*)(b -> h_params + v.second);
-    std::memcpy((void*)v.first, & q, sizeof(q));
+  acc[0] += us(t_0, t_1); acc[1] += us(t_1, t_2); acc[2] += us(t_2, t_3); acc[3] += us(t_3, now());
+  if(++ nacc < 200) return;
+  if(llsm_rt2_timing_fetch) {                           // (-DRT2_TIMING builds only)
+    unsigned long long ts[16]; llsm_rt2_timing_fetch(ts);
+    std::fprintf(stderr, "[noise filter] levels + frame into X %.2f, forward transform %.2f, power spectrum %.2f, filter %.2f, inverse transform %.2f us\n",
+      (ts[9] - ts[6]) * 0.01, (ts[10] - ts[9]) * 0.01, (ts[11] - ts[10]) * 0.01, (ts[12] - ts[11]) * 0.01, (ts[7] - ts[12]) * 0.01);
+    std::fprintf(stderr, "[k_rt_hop2, workgroup 0] requests %.2f, rows over the link %.2f, write early samples .. frames in LDS %.2f, barrier %.2f, "
+      "rings + excitation %.2f, pulses %.2f, noise filter %.2f, noise ring + samples %.2f us\n",
+      (ts[1] - ts[0]) * 0.01, (ts[2] - ts[1]) * 0.01, (ts[3] - ts[2]) * 0.01, (ts[4] - ts[3]) * 0.01, (ts[5] - ts[4]) * 0.01,
+      (ts[6] - ts[5]) * 0.01, (ts[7] - ts[6]) * 0.01, (ts[8] - ts[7]) * 0.01);
   }
-  b -> h_out = b -> h_out0 + (size_t)b -> blk * b -> out_elems;
-  const int S = b -> S, nch = b -> nchannel, cap = b -> ninternal, me = b -> me > 0 ? b -> me : 1;
-  const int nhop = b -> curr_nhop, nwin = 2 * nhop, npsd = b -> npsd, mh = b -> maxnhar;
-  WinEntry* we = (nhop > b -> max_hop || b -> next_nhop > b -> max_hop || nhop < 1) ? nullptr : get_window(b, nhop);
-  if(! we) {                                            // keep the output length consistent: one hop of silence
-    complete_pending(b);
-    if(nhop > b -> max_hop || b -> next_nhop > b -> max_hop) llsm_set_error("llsmrt: hop exceeds buffer");
-    if(b -> next_nhop > 0 && b -> next_nhop < (1 << 16)) append_outputs(b, nullptr);
-    return;
-  }
-  // ---- frames -> parameter rows (llsmrt.c:255-291), written straight into the pinned block
+  if(pack_sched > 0) std::fprintf(stderr, "[llsmrt pack] pulse trackers %.1f us, vocal-tract / source-phase rows %.1f us per hop\n", pack_sched / 200, pack_copy / 200);
+  pack_sched = pack_copy = 0;
+  std::fprintf(stderr, "[llsmrt feed, %d streams] pack %.1f us, enqueue %.1f us, device + completion %.1f us, rings + prev_nm %.1f us\n",
+    b -> S, acc[0] / nacc, acc[1] / nacc, acc[2] / nacc, acc[3] / nacc);
+  acc[0] = acc[1] = acc[2] = acc[3] = 0; nacc = 0;
+}
+
+// ---- A hop in three phases: pack_frames | enqueue_hop | collect_hop (feed_group below).  RtPacked: what packing found out
+struct RtPacked { bool truncated = false, any_sel = false, any_sin = false; int size_max = 64; };
+
+// Pack: frames -> parameter rows (llsmrt.c:255-291), written straight into the pinned block of this hop; pulse-by-pulse
+// buffers run their pulse trackers
+static RtPacked pack_frames(RtBuffer* b, llsm_container** frames) {
+  const bool timing = rt_timing();
+  const int S = b -> S, nch = b -> nchannel, me = b -> me > 0 ? b -> me : 1, nhop = b -> curr_nhop, mh = b -> maxnhar;
   float *f0v = b -> h_f0.p, *cyc = b -> h_cyc.p, *ampl = b -> h_ampl.p, *phse = b -> h_phse.p;
-  float *edc = b -> h_edc.p, *eamp = b -> h_eamp.p, *ephs = b -> h_ephs.p, *psd = b -> h_psd.p;
+  float *edc = b -> h_edc.p, *eamp = b -> h_eamp.p, *ephs = b -> h_ephs.p;
   int *nharv = b -> h_nhar.p, *nhev = b -> h_nhar_e.p, *hasnm = b -> h_has_nm.p;
   for(int k = 0; k < 3; k ++)                           // (the pulse pool behind it is written where it is used)
     std::memset(b -> h_params + b -> zero_rng[k][0], 0, b -> zero_rng[k][1] - b -> zero_rng[k][0]);
   for(size_t k = 0; k < (size_t)S * nch; k ++) edc[k] = 1e-5f;
-  bool truncated = false, any_sel = false, any_sin = false;
-  int size_max = 64;
-  b -> njobs_hop = 0; b -> npulses_hop = 0;
+  RtPacked pk; b -> njobs_hop = 0; b -> npulses_hop = 0;
   std::atomic<bool> trunc_any{false};
   // the rows every buffer carries (harmonic model, envelope harmonics, band energies) of streams [lo, hi)
   auto pack_rows = [&](int lo, int hi) {
@@ -744,156 +755,141 @@ static void feed_group(RtBuffer* b, llsm_container** frames, bool force_pipe = f
     }
     if(tr) trunc_any.store(true, std::memory_order_relaxed);
   };
-  {
-    bool pooled = false;
-    if(S >= kPackMin) {
-      std::unique_lock<std::mutex> pl(g_pack_pool_mx, std::try_to_lock);
-      if(pl.owns_lock()) { g_pack_pool.run(S, pack_rows); pooled = true; }
-    }
-    if(! pooled) pack_rows(0, S);
+  bool pooled = false;
+  if(S >= kPackMin) {
+    std::unique_lock<std::mutex> pl(g_pack_pool_mx, std::try_to_lock);
+    if(pl.owns_lock()) { g_pack_pool.run(S, pack_rows); pooled = true; }
   }
-  truncated = trunc_any.load();
+  if(! pooled) pack_rows(0, S);
+  pk.truncated = trunc_any.load();
   for(int s2 = 0; b -> l1 && s2 < S; s2 ++) {
     llsm_container* frame = frames[s2];
-    llsm_hmframe* hm = (llsm_hmframe*)llsm_container_get(frame, LLSM_FRAME_HM);
-    {
-      // llsmrt.c:295-304: without VSPHSE / RD, or unvoiced, the deterministic part of this hop is empty
-      FP_TYPE* vs = (FP_TYPE*)llsm_container_get(frame, LLSM_FRAME_VSPHSE);
-      FP_TYPE* vt = (FP_TYPE*)llsm_container_get(frame, LLSM_FRAME_VTMAGN);
-      FP_TYPE* rd = (FP_TYPE*)llsm_container_get(frame, LLSM_FRAME_RD);
-      b -> h_hashm.p[s2] = hm != NULL;
-      if(vs && rd && vt && f0v[s2] != 0 && llsm_fparray_length(vs) > 0 && llsm_fparray_length(vt) >= b -> nspec) {
-        int n = llsm_fparray_length(vs); if(n > mh) { n = mh; truncated = true; }
-        b -> h_rd.p[s2] = *rd; b -> h_nvs.p[s2] = n;
-        b -> h_vsphse.p[(size_t)s2 * mh] = vs[0];         // (the pulse tracker's phase reference)
-        // a stream whose pulse group cannot be placed (error text set) keeps an empty op and no job: its hop carries
-        // no pulses, the other streams of the group are not touched
-        const int jobs_before = b -> njobs_hop;
-        const auto ts0 = timing ? now() : t_0;
-        (void)schedule_pbp(b, s2, frame, f0v[s2], nhop);
-        const auto ts1 = timing ? now() : t_0;
-        // the source-phase and vocal-tract rows travel only on the hops whose kernels read them: a pulse group placed
-        // (k_pbp_pulse) or harmonic rows to rebuild (k_l1_to_l0)
-        if(b -> njobs_hop > jobs_before || b -> h_sel.p[s2]) {
-          std::memcpy(b -> h_vsphse.p + (size_t)s2 * mh, vs, sizeof(float) * (size_t)n);
-          std::memcpy(b -> h_vtmagn.p + (size_t)s2 * b -> nspec, vt, sizeof(float) * (size_t)b -> nspec);
-        }
-        if(timing) { pack_sched += us(ts0, ts1); pack_copy += us(ts1, now()); }
-        any_sel |= b -> h_sel.p[s2] != 0; any_sin |= b -> h_f0sin.p[s2] > 0;
-        if(b -> h_ops.p[s2].add_size > 0) size_max = std::max(size_max, b -> h_ops.p[s2].add_size);
-      }
+    // llsmrt.c:295-304: without VSPHSE / RD, or unvoiced, the deterministic part of this hop is empty
+    FP_TYPE* vs = (FP_TYPE*)llsm_container_get(frame, LLSM_FRAME_VSPHSE);
+    FP_TYPE* vt = (FP_TYPE*)llsm_container_get(frame, LLSM_FRAME_VTMAGN);
+    FP_TYPE* rd = (FP_TYPE*)llsm_container_get(frame, LLSM_FRAME_RD);
+    b -> h_hashm.p[s2] = llsm_container_get(frame, LLSM_FRAME_HM) != NULL;
+    if(!(vs && rd && vt && f0v[s2] != 0 && llsm_fparray_length(vs) > 0 && llsm_fparray_length(vt) >= b -> nspec)) continue;
+    int n = llsm_fparray_length(vs); if(n > mh) { n = mh; pk.truncated = true; }
+    b -> h_rd.p[s2] = *rd; b -> h_nvs.p[s2] = n;
+    b -> h_vsphse.p[(size_t)s2 * mh] = vs[0];             // (the pulse tracker's phase reference)
+    // a stream whose pulse group cannot be placed (error text set) keeps an empty op and no job: its hop carries
+    // no pulses, the other streams of the group are not touched
+    const int jobs_before = b -> njobs_hop;
+    const RtTime ts0 = timing ? now() : RtTime();
+    (void)schedule_pbp(b, s2, frame, f0v[s2], nhop);
+    const RtTime ts1 = timing ? now() : RtTime();
+    // the source-phase and vocal-tract rows travel only on the hops whose kernels read them: a pulse group placed
+    // (k_pbp_pulse) or harmonic rows to rebuild (k_l1_to_l0)
+    if(b -> njobs_hop > jobs_before || b -> h_sel.p[s2]) {
+      std::memcpy(b -> h_vsphse.p + (size_t)s2 * mh, vs, sizeof(float) * (size_t)n);
+      std::memcpy(b -> h_vtmagn.p + (size_t)s2 * b -> nspec, vt, sizeof(float) * (size_t)b -> nspec);
     }
+    if(timing) { pack_sched += us(ts0, ts1); pack_copy += us(ts1, now()); }
+    pk.any_sel |= b -> h_sel.p[s2] != 0; pk.any_sin |= b -> h_f0sin.p[s2] > 0;
+    if(b -> h_ops.p[s2].add_size > 0) pk.size_max = std::max(pk.size_max, b -> h_ops.p[s2].add_size);
   }
-  if(truncated) llsm_set_error("llsmrt: frame carries more harmonics than the stream rows hold (truncated)");
-  const auto t_1 = now();
+  if(pk.truncated) llsm_set_error("llsmrt: frame carries more harmonics than the stream rows hold (truncated)");
+  return pk;
+}
+
+// The record of this hop from the buffer as update_cycle left it; the excitation ring moves with the hop, so its cursor is
+// advanced here.  direct: the kernels read the pinned parameter rows themselves; direct_out: they write the pinned samples
+static RtHop rt_hop_record(const RtBuffer* b, const WinEntry* we, bool direct, bool direct_out) {
+  RtHop h = rt_ring_record(b);
+  BatchDev& d = h.d;
+  d.maxnhar = b -> maxnhar; d.maxnhar_e = b -> me; d.npsd = b -> npsd; d.thop = b -> thop; d.fs = b -> fs; d.rel_winsize = 4;
+  d.frm_utt = b -> d_frm_utt.p; d.frm_off = b -> d_frm_off.p;
+  d.f0 = b -> d_f0.p; d.nhar = b -> d_nhar.p; d.ampl = b -> d_ampl.p; d.phse = b -> d_phse.p;
+  d.psd = b -> d_psd.p; d.psdres = b -> d_psdres.p; d.has_psdres = b -> d_zero.p;
+  d.edc = b -> d_edc.p; d.nhar_e = b -> d_nhar_e.p; d.eenv_ampl = b -> d_eamp.p; d.eenv_phse = b -> d_ephs.p;
+  h.f0_sin = b -> l1 ? b -> d_f0sin.p : d.f0;           // (pulse by pulse: sinusoids only where the state machine asks for them)
+  h.cyc_shift = b -> d_cyc.p; h.has_nm = b -> d_has_nm.p;
+  h.nhop = b -> curr_nhop; h.nwin = 2 * h.nhop; h.win = we -> w.p; h.inv_wsqr = we -> inv_wsqr;
+  h.N = b -> nfft; h.logN = ilog2(b -> nfft); h.tw = llsm_engine_twiddles(b -> ctx, & h.tw_nmax);
+  h.fnyq = b -> fnyq; h.lds_harmonics = b -> maxnhar; h.exc_curr = (b -> exc_curr + h.nhop) % h.cap;
+  // output rows at the hop's own length (rounded to 16 samples), not the buffer's maximum: half the bytes to copy back
+  h.next_nhop = b -> next_nhop; h.out_stride = (b -> next_nhop + 15) & ~15; h.out = direct_out ? b -> h_out : b -> out.p;
+  if(direct) {                                          // (pinned host memory is mapped into the device's address space)
+    RtRows& r = h.host;
+    r.f0 = b -> h_f0.p; r.cyc = b -> h_cyc.p; r.nhar = b -> h_nhar.p; r.nhar_e = b -> h_nhar_e.p;
+    r.has_nm = b -> h_has_nm.p; r.ampl = b -> h_ampl.p; r.phse = b -> h_phse.p; r.edc = b -> h_edc.p;
+    r.eamp = b -> h_eamp.p; r.ephs = b -> h_ephs.p; r.psd = b -> h_psd2[b -> psd_cur];
+    if(b -> l1) { r.f0sin = b -> h_f0sin.p; r.ops = b -> h_ops.p; }
+  }
+  if(b -> l1) {
+    RtPbpArgs& a = h.pbp; a.ops = b -> d_ops.p; a.frwd = b -> dual_f.p; a.bkwd = b -> dual_b.p; a.dual_curr = b -> dual_curr;
+    a.pulse_out = b -> pulse_out.p; a.pulse_stride = b -> pulse_max;
+  }
+  return h;
+}
+
+// Enqueue: copy in, the launches of the form rt_hop_form chooses, copy out (or neither: direct), read-back of rebuilt harmonic
+// rows, the hop's event; optionally as one replayed graph.  Nonzero on failure; *ostride: the row stride of the output block
+static int enqueue_hop(RtBuffer* b, LaunchCtx* P, const WinEntry* we, const RtPacked& pk, int* ostride) {
+  const int S = b -> S, mh = b -> maxnhar;
   hipStream_t st = P -> stream;
   // LLSM_RT_GRAPH=1: the whole hop (copy in, launches, copy out) goes to the device as ONE graph launch.
   // Hops that hand rebuilt harmonic models back into pageable host memory keep the plain enqueue.
-  bool capturing = g_rt_graph.load() > 0 && st != nullptr && ! P -> prof_begin && !(b -> l1 && any_sel) &&
+  bool capturing = g_rt_graph.load() > 0 && st != nullptr && ! P -> prof_begin && !(b -> l1 && pk.any_sel) &&
     hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
   const int fuse_mode = g_rt_fused.load();
-  const bool fused = fuse_mode > 0, one_launch = fuse_mode > 1 && b -> nfft <= 2048;   // (k_rt_hop's LDS)
   // direct: no copy in and no copy out.  The first kernel of the hop moves the rows it and the second need (a few
   // hundred of a row's nfft harmonic slots) from the pinned block into the device rows, the second writes the samples
   // into the pinned output block; each copy was a dependent blit launch of 8 - 15 us around kernels of 14 us
   // (tools/ubench/host_io.hip).  Pulse-by-pulse buffers: the pulse kernel reads its groups, pulses and layer-1 rows from
   // the pinned block as well; only a hop that rebuilds harmonic rows on the device (a frame without a harmonic model
   // at the onset / end of pulse-by-pulse synthesis) keeps the copy in.
-  const bool direct_out = fused && ! capturing && g_rt_direct.load() > 0;      // samples straight into the pinned block
-  const bool direct = direct_out && !(b -> l1 && any_sel);
+  const bool direct_out = fuse_mode > 0 && ! capturing && g_rt_direct.load() > 0;      // samples straight into the pinned block
+  const bool direct = direct_out && !(b -> l1 && pk.any_sel);
+  const RtHop h = rt_hop_record(b, we, direct, direct_out);
+  const RtHopForm form = rt_hop_form(h, fuse_mode);
+  *ostride = h.out_stride;
   // one copy; the kernels below are ordered after it on the stream, and the pinned block is not
   // touched again before the synchronisation at the end of this call
-  if(! direct) std::memcpy(psd, b -> h_psd2[b -> psd_cur], sizeof(float) * (size_t)S * npsd);
+  if(! direct) std::memcpy(b -> h_psd.p, b -> h_psd2[b -> psd_cur], sizeof(float) * (size_t)S * b -> npsd);
   size_t copy_bytes = b -> params_fixed + sizeof(PbpPulse) * (size_t)b -> npulses_hop;
-  if(b -> l1 && (any_sin || any_sel)) copy_bytes = b -> params_bytes;       // the harmonic rows behind the pulse pool as well
+  if(b -> l1 && (pk.any_sin || pk.any_sel)) copy_bytes = b -> params_bytes;    // the harmonic rows behind the pulse pool as well
   int rc = direct ? 0 : hipMemcpyAsync(b -> d_params.p, b -> h_params, copy_bytes, hipMemcpyHostToDevice, st) != hipSuccess;
-  BatchDev d; std::memset(& d, 0, sizeof(d));
-  d.n_utt = S; d.nframes = S; d.maxnhar = mh; d.maxnhar_e = b -> me; d.npsd = npsd;
-  d.nchannel = nch; d.thop = b -> thop; d.fs = b -> fs; d.rel_winsize = 4;
-  d.frm_utt = b -> d_frm_utt.p; d.frm_off = b -> d_frm_off.p;
-  d.f0 = b -> d_f0.p; d.nhar = b -> d_nhar.p; d.ampl = b -> d_ampl.p; d.phse = b -> d_phse.p;
-  d.psd = b -> d_psd.p; d.psdres = b -> d_psdres.p; d.has_psdres = b -> d_zero.p;
-  d.edc = b -> d_edc.p; d.nhar_e = b -> d_nhar_e.p; d.eenv_ampl = b -> d_eamp.p; d.eenv_phse = b -> d_ephs.p;
-  RtRows host; std::memset(& host, 0, sizeof(host));
-  if(direct) {                                          // (pinned host memory is mapped into the device's address space)
-    host.f0 = b -> h_f0.p; host.cyc = b -> h_cyc.p; host.nhar = b -> h_nhar.p; host.nhar_e = b -> h_nhar_e.p;
-    host.has_nm = b -> h_has_nm.p; host.ampl = b -> h_ampl.p; host.phse = b -> h_phse.p; host.edc = b -> h_edc.p;
-    host.eamp = b -> h_eamp.p; host.ephs = b -> h_ephs.p; host.psd = b -> h_psd2[b -> psd_cur];
-    if(b -> l1) { host.f0sin = b -> h_f0sin.p; host.ops = b -> h_ops.p; }
-  }
-  RtPbpArgs pbp; std::memset(& pbp, 0, sizeof(pbp));
-  if(b -> l1) {
-    pbp.ops = b -> d_ops.p; pbp.frwd = b -> dual_f.p; pbp.bkwd = b -> dual_b.p; pbp.dual_curr = b -> dual_curr;
-    pbp.pulse_out = b -> pulse_out.p; pbp.pulse_stride = b -> pulse_max;
-  }
-  int tw_nmax = 0; const float2* tw = llsm_engine_twiddles(b -> ctx, & tw_nmax);
-  // feed_deterministic: envelope frames + harmonic frame, then the ring adds.  g_rt_fused (default): the hop is two
-  // launches -- k_rt_front (envelope frames beside the harmonic frame, ring adds, excitation) and k_rt_back (noise filter
-  // on four wavefronts per pair of streams, noise ring, output samples); 0: the five single-purpose launches
-  if(! fused) rc |= launch_env_frames(P, d, b -> fs, nwin, we -> w.p, b -> envf.p);
-  const float* f0_sin = d.f0;
+  if(form == RT_HOP_FIVE) rc |= launch_env_frames(P, h.d, b -> fs, h.nwin, h.win, h.envf);
   if(b -> l1) {
     L1Dev ld; std::memset(& ld, 0, sizeof(ld));
     ld.nframes = S; ld.maxnhar = mh; ld.nspec = b -> nspec; ld.fnyq = b -> fnyq; ld.lip_radius = b -> lip_radius;
     ld.f0 = b -> d_f0.p; ld.nhar = b -> d_nhar.p; ld.ampl = b -> d_ampl.p; ld.phse = b -> d_phse.p;
     ld.rd = b -> d_rd.p; ld.vtmagn = b -> d_vtmagn.p; ld.vsphse = b -> d_vsphse.p; ld.nvsphse = b -> d_nvs.p;
     ld.has_hm = b -> d_hashm.p;
-    if(any_sel) rc |= launch_l1_to_l0(P, ld, b -> maxnhar_conf, 1, b -> d_sel.p, tw, tw_nmax);
+    if(pk.any_sel) rc |= launch_l1_to_l0(P, ld, b -> maxnhar_conf, 1, b -> d_sel.p, h.tw, h.tw_nmax);
     if(b -> njobs_hop > 0) {
       if(direct) {                                      // (no l1_to_l0 on this hop: nothing on the device is newer than the pinned rows)
         ld.f0 = b -> h_f0.p; ld.rd = b -> h_rd.p; ld.vtmagn = b -> h_vtmagn.p; ld.vsphse = b -> h_vsphse.p; ld.nvsphse = b -> h_nvs.p;
       }
       rc |= launch_pbp_pulse(P, ld, direct ? b -> h_jobs.p : b -> d_jobs.p, b -> njobs_hop, direct ? b -> h_pulses.p : b -> d_pulses.p,
-        size_max, b -> fs, tw, tw_nmax, b -> pulse_out.p);
+        pk.size_max, b -> fs, h.tw, h.tw_nmax, b -> pulse_out.p);
     }
-    f0_sin = b -> d_f0sin.p;                            // sinusoids only where the state machine asks for them
   }
-  b -> exc_curr = (b -> exc_curr + nhop) % cap;
-  const int exc_cycle_hop = b -> exc_cycle;
-  if(one_launch) { }                                    // (below, with the second half of the hop)
-  else if(fused)
-    rc |= launch_rt_front(P, d, nwin, we -> w.p, f0_sin, b -> d_cyc.p, b -> envf.p, b -> frames_sin.p, mh, b -> mod.p,
-      b -> sinr.p, b -> noiser.p, cap, b -> mod_curr, b -> sin_curr, b -> noise_curr, nhop, b -> d_has_nm.p, b -> tpl.p,
-      b -> excr.p, b -> ntemplate, b -> exc_curr, b -> exc_cycle, b -> exc_frame.p, direct ? & host : nullptr,
-      b -> l1 ? & pbp : nullptr);
-  else {
-    BatchDev ds = d; ds.f0 = (float*)f0_sin;
-    rc |= launch_synth_frames(P, ds, nwin, we -> w.p, b -> d_cyc.p, b -> frames_sin.p, mh);
-    // ring adds + run_excitation_buffers(curr_nhop) in one launch (the excitation reads only its own stream's envelope
-    // ring); the pulse-by-pulse adds into the sinusoid ring follow
-    rc |= launch_rt_rings_excite(P, S, b -> mod.p, b -> sinr.p, b -> noiser.p, cap, nch, b -> mod_curr, b -> sin_curr,
-      b -> noise_curr, nhop, nwin, b -> envf.p, b -> frames_sin.p, f0_sin, b -> d_has_nm.p, b -> d_nhar.p,
-      b -> tpl.p, b -> excr.p, b -> ntemplate, b -> exc_curr, b -> exc_cycle, b -> exc_frame.p);
+  // feed_deterministic (envelope frames + harmonic frame, then the ring adds and the excitation), feed_filter on the
+  // previous frame's noise model (rows at -200 dB are skipped: no prev_nm yet) and feed_mix, in the form of this hop
+  switch(form) {
+    case RT_HOP_CHIP: rc |= launch_rt_hop2(P, h); break;
+    case RT_HOP_ONE: rc |= launch_rt_hop(P, h); break;
+    case RT_HOP_TWO: rc |= launch_rt_front(P, h); rc |= launch_rt_back(P, h); break;
+    case RT_HOP_FIVE: {
+      BatchDev ds = h.d; ds.f0 = (float*)h.f0_sin;
+      rc |= launch_synth_frames(P, ds, h.nwin, h.win, h.cyc_shift, h.frames_sin, h.lds_harmonics);
+      // ring adds + run_excitation_buffers(curr_nhop) in one launch (the excitation reads only its own stream's envelope
+      // ring); the pulse-by-pulse adds into the sinusoid ring follow (the fused kernels carry them themselves)
+      rc |= launch_rt_rings_excite(P, h);
+      if(b -> l1) rc |= launch_rt_pbp(P, h);
+      rc |= launch_noise_filter(P, h.d, h.exc_frame, nullptr, nullptr, h.fnyq, b -> fs, h.nwin, h.win, h.inv_wsqr, h.N, h.logN,
+        h.tw, h.tw_nmax, h.nframes, h.live, 1);
+      rc |= launch_rt_mix(P, h);
+    }
   }
-  b -> exc_cycle = (b -> exc_cycle + nhop) % b -> ntemplate;
-  if(b -> l1) {
-    if(! fused)                                         // (k_rt_front / k_rt_hop carry it themselves)
-      rc |= launch_rt_pbp(P, S, b -> d_ops.p, b -> dual_f.p, b -> dual_b.p, cap, b -> dual_curr, b -> sinr.p, b -> sin_curr,
-        nhop, we -> w.p, b -> pulse_out.p, b -> pulse_max);
-    b -> dual_curr = (b -> dual_curr + nhop) % cap;
-  }
-  // feed_filter on the previous frame's noise model (rows at -200 dB are skipped: no prev_nm yet), then feed_mix.
-  // Output rows are packed at the hop's own length (rounded to 16 samples), not at the buffer's maximum: the copy back
-  // is half the bytes at the nominal hop
-  const int ostride = (b -> next_nhop + 15) & ~15;
-  if(one_launch)
-    rc |= launch_rt_hop(P, d, nwin, we -> w.p, f0_sin, b -> d_cyc.p, b -> envf.p, b -> frames_sin.p, mh, b -> mod.p,
-      b -> sinr.p, b -> noiser.p, cap, b -> mod_curr, b -> sin_curr, b -> noise_curr, nhop, b -> d_has_nm.p, b -> tpl.p,
-      b -> excr.p, b -> ntemplate, b -> exc_curr, exc_cycle_hop, b -> exc_frame.p, direct ? & host : nullptr,
-      b -> fnyq, we -> inv_wsqr, b -> nfft, ilog2(b -> nfft), tw, tw_nmax, b -> nframes.p, b -> live.p, b -> sin_pos,
-      b -> next_nhop, ostride, direct_out ? b -> h_out : b -> out.p, b -> l1 ? & pbp : nullptr, fuse_mode > 2);
-  else if(fused)
-    rc |= launch_rt_back(P, d, b -> exc_frame.p, b -> fnyq, b -> fs, nwin, we -> w.p, we -> inv_wsqr, b -> nfft,
-      ilog2(b -> nfft), tw, tw_nmax, b -> nframes.p, b -> live.p, b -> noiser.p, b -> sinr.p, cap, b -> noise_curr,
-      b -> sin_curr, b -> sin_pos, b -> next_nhop, ostride, direct_out ? b -> h_out : b -> out.p);
-  else {
-    rc |= launch_noise_filter(P, d, b -> exc_frame.p, nullptr, nullptr, b -> fnyq, b -> fs, nwin, we -> w.p,
-      we -> inv_wsqr, b -> nfft, ilog2(b -> nfft), tw, tw_nmax, b -> nframes.p, b -> live.p, 1);
-    rc |= launch_rt_mix(P, S, b -> noiser.p, b -> sinr.p, cap, b -> noise_curr, b -> sin_curr, b -> sin_pos,
-      b -> nfft, b -> nframes.p, b -> live.p, b -> next_nhop, ostride, b -> out.p);
-  }
+  // the hop is enqueued: the buffer's cursors move on (the record keeps what the kernels were given)
+  b -> exc_curr = h.exc_curr; b -> exc_cycle = (h.exc_cycle + h.nhop) % b -> ntemplate;
+  if(b -> l1) b -> dual_curr = (h.pbp.dual_curr + h.nhop) % h.cap;
   if(! direct_out)
-    rc |= hipMemcpyAsync(b -> h_out, b -> out.p, sizeof(float) * S * 2 * ostride, hipMemcpyDeviceToHost, st) != hipSuccess;
+    rc |= hipMemcpyAsync(b -> h_out, b -> out.p, sizeof(float) * S * 2 * h.out_stride, hipMemcpyDeviceToHost, st) != hipSuccess;
   if(capturing) {
     hipGraph_t g = nullptr;
     rc |= hipStreamEndCapture(st, & g) != hipSuccess;
@@ -909,46 +905,50 @@ static void feed_group(RtBuffer* b, llsm_container** frames, bool force_pipe = f
     }
     if(g) (void)hipGraphDestroy(g);
   }
-  if(b -> l1 && any_sel) {                              // HM rows rebuilt from layer 1 go back onto the callers' frames
+  if(b -> l1 && pk.any_sel) {                              // HM rows rebuilt from layer 1 go back onto the callers' frames
     float* hb = b -> hm_back.data();
     rc |= hipMemcpyAsync(hb, b -> d_ampl.p, sizeof(float) * (size_t)S * mh, hipMemcpyDeviceToHost, st) != hipSuccess;
     rc |= hipMemcpyAsync(hb + (size_t)S * mh, b -> d_phse.p, sizeof(float) * (size_t)S * mh, hipMemcpyDeviceToHost, st) != hipSuccess;
     rc |= hipMemcpyAsync(hb + (size_t)S * mh * 2, b -> d_nhar.p, sizeof(int) * S, hipMemcpyDeviceToHost, st) != hipSuccess;
   }
   // behind this hop's last device operation: what complete_pending waits for when the hop is left in flight
-  rc |= hipEventRecord(b -> hop_done[b -> blk], st) != hipSuccess;
+  return rc | (hipEventRecord(b -> hop_done[b -> blk], st) != hipSuccess);
+}
+
+// Collect: the next hop's level rows while the device works; then the hop is left in flight (pipelined feeds) or waited
+// for, its samples go into the rings and rebuilt harmonic models back onto the callers' frames.  t_0, t_1: LLSM_TIMING
+static void collect_hop(RtBuffer* b, LaunchCtx* P, llsm_container** frames, const RtPacked& pk, int rc, int ostride, bool pipe,
+                        RtTime t_0, RtTime t_1) {
+  const int S = b -> S, mh = b -> maxnhar, npsd = b -> npsd, nxt = b -> psd_cur ^ 1;
   // the hop before this one (pipelined feeds): both are on the device now, so its samples can be collected -- and the
   // level rows it read (h_psd2[psd_cur ^ 1], written below for the hop AFTER this one) are free again once it is done
   complete_pending(b);
   // prev_nm with PSDRES folded in (llsmrt.c:513-520): the NEXT hop's filter target.  It depends on the callers' frames only,
   // so it is formed here, while the device works on this hop, not after the synchronisation
-  {
-    const int nxt = b -> psd_cur ^ 1;
-    for(int s2 = 0; s2 < S; s2 ++) {
-      llsm_nmframe* nm = (llsm_nmframe*)llsm_container_get(frames[s2], LLSM_FRAME_NM);
-      FP_TYPE* resvec = (FP_TYPE*)llsm_container_get(frames[s2], LLSM_FRAME_PSDRES);
-      b -> has_prev[s2] = nm != NULL;
-      float* pp = b -> h_psd2[nxt] + (size_t)s2 * npsd;
-      if(nm) {
-        const int np = std::min(npsd, nm -> npsd), nr = resvec ? std::min(npsd, llsm_fparray_length(resvec)) : 0;
-        const float bias = (float)(0.375 / 2.3025851 * 10.0);
-        std::memcpy(pp, nm -> psd, sizeof(float) * (size_t)np);
-        for(int j = np; j < npsd; j ++) pp[j] = -120.0f;
-        for(int j = 0; j < nr; j ++) pp[j] += resvec[j] - bias;
-        b -> psd_blank[nxt][s2] = 0;
-      } else if(! b -> psd_blank[nxt][s2]) {
-        std::fill(pp, pp + npsd, -200.0f);
-        b -> psd_blank[nxt][s2] = 1;
-      }
+  for(int s2 = 0; s2 < S; s2 ++) {
+    llsm_nmframe* nm = (llsm_nmframe*)llsm_container_get(frames[s2], LLSM_FRAME_NM);
+    FP_TYPE* resvec = (FP_TYPE*)llsm_container_get(frames[s2], LLSM_FRAME_PSDRES);
+    b -> has_prev[s2] = nm != NULL;
+    float* pp = b -> h_psd2[nxt] + (size_t)s2 * npsd;
+    if(nm) {
+      const int np = std::min(npsd, nm -> npsd), nr = resvec ? std::min(npsd, llsm_fparray_length(resvec)) : 0;
+      const float bias = (float)(0.375 / 2.3025851 * 10.0);
+      std::memcpy(pp, nm -> psd, sizeof(float) * (size_t)np);
+      for(int j = np; j < npsd; j ++) pp[j] = -120.0f;
+      for(int j = 0; j < nr; j ++) pp[j] += resvec[j] - bias;
+      b -> psd_blank[nxt][s2] = 0;
+    } else if(! b -> psd_blank[nxt][s2]) {
+      std::fill(pp, pp + npsd, -200.0f);
+      b -> psd_blank[nxt][s2] = 1;
     }
-    b -> psd_cur = nxt;
   }
-  const auto t_2 = now();
+  b -> psd_cur = nxt;
+  const RtTime t_2 = now();
   // Pipelined: return now; the hop's samples are appended when the next feed starts (or a consumer runs dry).  The host
   // side of the next hop -- the caller's pulls, packing its frames -- then runs beside this hop's kernels instead of
   // after them.  Hops that hand rebuilt harmonic models back onto the caller's frames stay synchronous (the frame is the
   // caller's and may be gone by the next feed).
-  if(! rc && pipe && !(b -> l1 && any_sel)) {
+  if(! rc && pipe && !(b -> l1 && pk.any_sel)) {
     std::lock_guard<std::mutex> lock(b -> pend_mtx);
     b -> pending_ostride = ostride; b -> pending_blk = b -> blk; b -> pending_nhop = b -> next_nhop;
     b -> pending = true;
@@ -956,14 +956,14 @@ static void feed_group(RtBuffer* b, llsm_container** frames, bool force_pipe = f
     return;
   }
   b -> blk ^= 1;
-  const bool dev_failed = rc || hipStreamSynchronize(st) != hipSuccess;
-  const auto t_3 = now();
+  const bool dev_failed = rc || hipStreamSynchronize(P -> stream) != hipSuccess;
+  const RtTime t_3 = now();
   if(dev_failed) {
     llsm_set_error("llsmrt: feed failed on the device");
     append_outputs(b, nullptr);                         // the consumer still gets next_nhop (silent) samples
   } else {
     append_outputs(b, b -> h_out, ostride);
-    if(b -> l1 && any_sel) {
+    if(b -> l1 && pk.any_sel) {
       const float* hb = b -> hm_back.data(); const int* nh = (const int*)(hb + (size_t)S * mh * 2);
       for(int s2 = 0; s2 < S; s2 ++) {
         if(! b -> h_sel.p[s2]) continue;
@@ -974,25 +974,39 @@ static void feed_group(RtBuffer* b, llsm_container** frames, bool force_pipe = f
       }
     }
   }
-  if(timing) {
-    acc[0] += us(t_0, t_1); acc[1] += us(t_1, t_2); acc[2] += us(t_2, t_3); acc[3] += us(t_3, now());
-    if(++ nacc == 200) {
-      if(llsm_rt2_timing_fetch) {                           // (-DRT2_TIMING builds only)
-        unsigned long long ts[16]; llsm_rt2_timing_fetch(ts);
-        std::fprintf(stderr, "[noise filter] levels + frame into X %.2f, forward transform %.2f, power spectrum %.2f, filter %.2f, inverse transform %.2f us\n",
-          (ts[9] - ts[6]) * 0.01, (ts[10] - ts[9]) * 0.01, (ts[11] - ts[10]) * 0.01, (ts[12] - ts[11]) * 0.01, (ts[7] - ts[12]) * 0.01);
-        std::fprintf(stderr, "[k_rt_hop2, workgroup 0] requests %.2f, rows over the link %.2f, write early samples .. frames in LDS %.2f, barrier %.2f, "
-          "rings + excitation %.2f, pulses %.2f, noise filter %.2f, noise ring + samples %.2f us\n",
-          (ts[1] - ts[0]) * 0.01, (ts[2] - ts[1]) * 0.01, (ts[3] - ts[2]) * 0.01, (ts[4] - ts[3]) * 0.01, (ts[5] - ts[4]) * 0.01,
-          (ts[6] - ts[5]) * 0.01, (ts[7] - ts[6]) * 0.01, (ts[8] - ts[7]) * 0.01);
-      }
-      if(pack_sched > 0) std::fprintf(stderr, "[llsmrt pack] pulse trackers %.1f us, vocal-tract / source-phase rows %.1f us per hop\n", pack_sched / 200, pack_copy / 200);
-      pack_sched = pack_copy = 0;
-      std::fprintf(stderr, "[llsmrt feed, %d streams] pack %.1f us, enqueue %.1f us, device + completion %.1f us, rings + prev_nm %.1f us\n",
-        b -> S, acc[0] / nacc, acc[1] / nacc, acc[2] / nacc, acc[3] / nacc);
-      acc[0] = acc[1] = acc[2] = acc[3] = 0; nacc = 0;
-    }
+  if(rt_timing()) report_timing(b, t_0, t_1, t_2, t_3);
+}
+
+// One hop for every stream of the group: frames[s] is the frame of stream s (llsmrt.c:505-521).
+static void feed_group(RtBuffer* b, llsm_container** frames, bool force_pipe = false) {
+  // Pipelined feeds (llsm_gpu_rt_pipeline): the previous hop may still be on the device.  It used the OTHER copy of the
+  // pinned blocks, so this hop is packed and enqueued behind it first and the previous hop's samples are appended
+  // after that (collect_hop) -- the device goes from one hop's kernel to the next without waiting for the host.
+  const bool pipe = force_pipe || g_rt_pipeline.load() > 0;   // (force_pipe: the inner hops of llsm_rtsynth_group_feed_many)
+  if(! pipe) complete_pending(b);
+  const RtTime t_0 = now();
+  (void)hipSetDevice(llsm_engine_device(b -> ctx));
+  LaunchCtx* P = llsm_engine_launch_ctx(b -> ctx);
+  update_cycle(b);
+  b -> h_params = b -> h_params0 + (size_t)b -> blk * b -> params_bytes;
+  for(auto& v : b -> h_views) {                         // (memcpy: the views are float* / int* / struct pointers behind void**)
+    void* q = (void*)(b -> h_params + v.second);
+    std::memcpy((void*)v.first, & q, sizeof(q));
   }
+  b -> h_out = b -> h_out0 + (size_t)b -> blk * b -> out_elems;
+  const int nhop = b -> curr_nhop;
+  WinEntry* we = (nhop > b -> max_hop || b -> next_nhop > b -> max_hop || nhop < 1) ? nullptr : get_window(b, nhop);
+  if(! we) {                                            // keep the output length consistent: one hop of silence
+    complete_pending(b);
+    if(nhop > b -> max_hop || b -> next_nhop > b -> max_hop) llsm_set_error("llsmrt: hop exceeds buffer");
+    if(b -> next_nhop > 0 && b -> next_nhop < (1 << 16)) append_outputs(b, nullptr);
+    return;
+  }
+  const RtPacked pk = pack_frames(b, frames);
+  const RtTime t_1 = now();
+  int ostride = 0;
+  const int rc = enqueue_hop(b, P, we, pk, & ostride);
+  collect_hop(b, P, frames, pk, rc, ostride, pipe, t_0, t_1);
 }
 
 void llsm_rtsynth_buffer_feed(llsm_rtsynth_buffer* dst, llsm_container* frame) {

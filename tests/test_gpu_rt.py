@@ -347,6 +347,50 @@ def test_rt_launch_modes_agree(o64, thop):
         assert rel_rms(runs["five"][1][s], runs["copies"][1][s]) < 2e-6, s
 
 
+@pytest.mark.parametrize("thop", [0.011, 0.020])
+def test_rt_launch_modes_agree_where_the_form_changes(o64, thop):
+    """The shapes at which rt_hop_form (kernels.hip) decides differently, at 48 kHz, three streams, about 40 hops:
+    thop 0.011 -- a hop of 528 samples, a window of 1 056 over k_rt_hop2's 1 024 slots, a 2 048-point transform: modes 2
+    and 3 both run k_rt_hop; thop 0.020 -- a hop of 960 samples and a 4 096-point transform, which the LDS of one launch
+    does not hold: modes 2 and 3 go out as k_rt_front + k_rt_back.  Whatever the form, the fused modes agree bit for bit,
+    and the five launches differ by the float32 rounding of the noise part only."""
+    L = llsm.load()
+    fs, S, nhops = 48000.0, 3, 40
+    ao = llsm.make_aoptions(f0_refine=0, thop=thop)
+    chunks, nfrm = [], None
+    for s in range(S):
+        x, _ = make_speechlike(60 + s, nx=int(nhops * thop * fs), fs=fs, thop=thop)
+        n = int(len(x) / fs / thop)
+        t = np.arange(n) * thop
+        f0 = (110 + 45 * s + 25 * np.sin(2 * np.pi * 1.7 * t + s)).astype(np.float32)
+        f0[:3] = 0; f0[n // 2: n // 2 + 5] = 0
+        pr, _ = oracle_analyze(o64, ao, fs, x, f0)
+        chunks.append(chunk_from_oracle(L, ao, pr, fs)); nfrm = n
+    so = llsm.make_soptions(fs)
+    prev_f, prev_d = L.llsm_gpu_rt_fused(-1), L.llsm_gpu_rt_direct(-1)
+    try:
+        runs = {}
+        for mode in (0, 1, 2, 3):
+            L.llsm_gpu_rt_fused(mode)
+            runs[mode] = _group_run(L, so, chunks, nfrm, 4343)
+    finally:
+        L.llsm_gpu_rt_fused(prev_f); L.llsm_gpu_rt_direct(prev_d)
+    for ch in chunks:
+        L.llsm_delete_chunk(ch)
+    for s in range(S):
+        for mode in (0, 1, 2, 3):
+            print("stream %d mode %d: %d samples, sinusoid rms %.4f, noise rel_rms to mode 1 %.3g" % (
+                s, mode, len(runs[mode][0][s]), np.sqrt(np.mean(runs[mode][0][s] ** 2)), rel_rms(runs[mode][1][s], runs[1][1][s])))
+        assert len(runs[0][0][s]) == len(runs[1][0][s]) == len(runs[2][0][s]) == len(runs[3][0][s])
+        assert len(runs[0][1][s]) == len(runs[1][1][s]) == len(runs[2][1][s]) == len(runs[3][1][s]) == len(runs[1][0][s])
+        assert np.sqrt(np.mean(runs[1][0][s] ** 2)) > 0.01
+        for mode in (2, 3):
+            assert np.array_equal(runs[mode][0][s], runs[1][0][s]), (mode, s)
+            assert np.array_equal(runs[mode][1][s], runs[1][1][s]), (mode, s)
+        assert np.array_equal(runs[0][0][s], runs[1][0][s]), s                  # the sinusoid path is the same arithmetic
+        assert rel_rms(runs[0][1][s], runs[1][1][s]) < 2e-6, s
+
+
 def test_pipelined_consumer_never_blocks_on_another_streams_ring(o64):
     """ADVICE r4 (rt.cpp complete_pending): pipelined feeds, a group of two streams with a ring barely larger than two
     hops, an idle producer, and ONE thread draining the streams one after another.  After three feeds two hops lie in
