@@ -10,7 +10,8 @@ kernels after the envelope are not: given the planes they read, their output is 
            4 Y + 5e-5 dB, Y that utterance's distance between the float32 and the float64 restatement on the same planes
            (tests/psd_stage_reference.py; proven against the oracle by tests/test_psd_stage_host.py).
 
-Plane 0 (the envelope) is an input here and is never judged.  Frame counts sit below, at and above one, two and three
+Plane 0 (the envelope) is an input here and is never judged: tests/test_gpu_spgm_env.py is its judge, value by value
+against float64 of the uploaded samples and F0.  Frame counts sit below, at and above one, two and three
 chunks of KAL_CHUNK = 8 frames (the checkpoint spacing, the prefetch distance, the rotation of the register buffers) with
 unlike neighbours, so that a wavefront straddling utterances has lanes of different length; the PSD sizes put a dozen
 utterances, two, one or half of one on a wavefront.
