@@ -85,8 +85,14 @@ template <class T> struct PinVec {
   T& operator[](size_t i) { return p[i]; } const T& operator[](size_t i) const { return p[i]; }
 };
 
+// grow-only device array that owns its block (llsm_dev_malloc / llsm_dev_free, the caching pool of engine.cpp).  The pool's
+// rule binds whoever destroys one: the streams that used the block are synchronised first (llsm_gpu_delete_batch does, before
+// `delete b`; a local DevBuf lives in a function that synchronises before it returns).
 template <class T> struct DevBuf {
   T* p = nullptr; size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int alloc(size_t count) {
     if(count <= n && p) return 0;
     if(p) { hipDeviceSynchronize(); llsm_dev_free(p); }   // regrow: earlier launches may still read it
@@ -97,7 +103,7 @@ template <class T> struct DevBuf {
     n = count;
     return 0;
   }
-  void release() { llsm_dev_free(p); p = nullptr; n = 0; }        // callers synchronise the stream first
+  void release() { llsm_dev_free(p); p = nullptr; n = 0; }        // an early free; callers synchronise the stream first
 };
 
 // The five alignment calls (align.cpp): two bits, inside a band and under the slope pattern, tell the first four apart, and
@@ -211,7 +217,6 @@ struct llsm_gpu_batch {
     DevBuf<float> plane, row, out; DevBuf<uint4> moves; DevBuf<AlignPair> pairs; DevBuf<int4> tiles; DevBuf<int2> region;
     DevBuf<int> center;
     long long cells = 0;
-    void release() { plane.release(); row.release(); out.release(); moves.release(); pairs.release(); tiles.release(); region.release(); center.release(); }
   } align[ALIGN_CALLS];
   // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
   // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful

@@ -406,6 +406,19 @@ static int channel_chain(const llsm_gpu_batch* b, float fs, int c, bool* hp0, fl
 static const int kParamIds[11] = {LLSM_GPU_F0, LLSM_GPU_NHAR, LLSM_GPU_AMPL, LLSM_GPU_PHSE, LLSM_GPU_PSD, LLSM_GPU_PSDRES, LLSM_GPU_HAS_PSDRES,
                                   LLSM_GPU_EDC, LLSM_GPU_NHAR_E, LLSM_GPU_EENV_AMPL, LLSM_GPU_EENV_PHSE};
 
+// The Chebyshev sections k_filtfilt reads, each with its block tables: index 2 * row + highpass.  One table per batch, and
+// one per context for one-shot filtering (llsm_engine_chebyfilt).
+static std::vector<FiltSectionD> make_filt_sections() {
+  std::vector<FiltSectionD> secs(2 * llsm_cheby::kRows);
+  for(int r = 0; r < llsm_cheby::kRows; r ++)
+    for(int hp = 0; hp < 2; hp ++) {
+      llsm_cheby::Section s = llsm_cheby::make_section_row(r, hp != 0);
+      FiltSectionD& d = secs[2 * r + hp];
+      std::memcpy(d.b, s.b, sizeof(d.b)); std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.zi, s.zi, sizeof(d.zi));
+      llsm_cheby::block_tables(s.a, IIR_SEG, 6, & d.H[0][0], & d.M[0][0]);
+    }
+  return secs;
+}
 
 extern "C" llsm_gpu_batch* llsm_gpu_create_batch(llsm_gpu_context* ctx,
   const llsm_aoptions* options, FP_TYPE fs, int n_utt, const int* nx, const int* nfrm) {
@@ -563,20 +576,14 @@ extern "C" llsm_gpu_batch* llsm_gpu_create_batch(llsm_gpu_context* ctx,
     b -> sin_halo = (int)std::floor((b -> nwin_sin + 1) / std::max((double)thop * fs, 1.0));
     bad |= upload_vec(b -> sin_units, units);
   }
-  // filter sections: index 2*row + highpass
-  std::vector<FiltSectionD> secs(2 * llsm_cheby::kRows);
-  for(int r = 0; r < llsm_cheby::kRows; r ++)
-    for(int hp = 0; hp < 2; hp ++) {
-      llsm_cheby::Section s = llsm_cheby::make_section_row(r, hp != 0);
-      FiltSectionD& d = secs[2 * r + hp];
-      std::memcpy(d.b, s.b, sizeof(d.b)); std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.zi, s.zi, sizeof(d.zi));
-      llsm_cheby::block_tables(s.a, IIR_SEG, 6, & d.H[0][0], & d.M[0][0]);
-    }
-  bad |= upload_vec(b -> sections, secs);
+  bad |= upload_vec(b -> sections, make_filt_sections());
   if(bad) { llsm_gpu_delete_batch(b); return nullptr; }
   return b;
 }
 
+// Every DevBuf of the batch frees its own block when `delete b` destroys it; the pool's rule (a block enters the cache only
+// after the streams that used it are idle) is kept by the two waits that come first.  What is left to free by hand is what no
+// DevBuf holds: the caller-visible arrays, the page-locked blob staging and the edit event.
 extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   if(! b) return;
   hipSetDevice(b -> ctx -> device);
@@ -585,28 +592,8 @@ extern "C" void llsm_gpu_delete_batch(llsm_gpu_batch* b) {
   for(int k = 0; k < 11; k ++) if(b -> pblock) b -> arr[kParamIds[k]] = nullptr;        // pieces of pblock, not allocations
   llsm_dev_free(b -> pblock); b -> pblock = nullptr;
   for(int a = 0; a < LLSM_GPU_NARRAYS; a ++) llsm_dev_free(b -> arr[a]);
-  b -> d_nx.release(); b -> d_nfrm.release(); b -> d_ny.release(); b -> d_x_off.release();
-  b -> d_frm_off.release(); b -> d_y_off.release(); b -> d_frm_utt.release(); b -> d_pairs.release(); b -> d_hblocks.release();
-  b -> packed.release(); b -> ce.release(); b -> mid.release(); b -> iir_tmp.release(); b -> iir_edge[0].release(); b -> iir_edge[1].release(); b -> iir_seg[0].release(); b -> iir_seg[1].release();
-  b -> env.release(); b -> psd_log.release(); b -> pbuf.release(); b -> spgm_fix.release(); b -> spgm_fix_count.release();
-  b -> colored.release(); b -> env_cplx.release(); b -> env_hits.release(); b -> env_over.release(); b -> nf_units.release(); b -> sin_units.release(); b -> exu_units.release(); b -> yexc.release(); b -> nframes.release();
-  b -> live.release(); b -> win_sin.release(); b -> win_psd.release(); b -> win_env.release();
-  b -> win_filt.release(); b -> nfft_u.release(); b -> sections.release(); b -> jobs_ana.release(); b -> jobs_syn.release();
-  b -> l1_model_power.release(); b -> l1_model_param.release(); b -> l1_model_inv_t.release(); b -> l1_model_cumlog_t.release(); b -> l1_rd_raw.release(); b -> l1_cont.release();
-  b -> l1_f0_hm.release(); b -> l1_pulse_buf.release(); b -> l1_mixw.release(); b -> l1_hm_frames.release(); b -> l1_zero.release(); b -> l1_src_ampl.release();
   if(b -> blob_stage) { (void)hipHostFree(b -> blob_stage); b -> blob_stage = nullptr; }
-  b -> l1_prev.release(); b -> l1_next.release(); b -> l1_blk_off.release(); b -> l1_select.release();
-  b -> l1_jobs.release(); b -> l1_pulses.release(); b -> l1_segs.release(); b -> l1_blk_jobs.release();
-  b -> l1_proj.release(); b -> l1_alpha.release(); b -> l1_alpha_key.release();
-  b -> mod_theta.release(); b -> mod_ratio.release(); b -> mod_map.release();
   if(b -> mod_ev) { (void)hipEventDestroy(b -> mod_ev); b -> mod_ev = nullptr; }
-  b -> coder_mel.release();
-  b -> blob_widths.release(); b -> blob_tab.release(); b -> blob_dev.release();
-  b -> f0_uss.release(); b -> f0_raw.release(); b -> f0_cmndf.release(); b -> f0_cand.release(); b -> f0_bp.release();
-  for(auto& sc : b -> align) sc.release();
-  b -> sel_lists.release(); b -> sel_p7.release(); b -> sel_p8.release(); b -> sel_bp.release(); b -> sel_out.release();
-  b -> selc_lists.release(); b -> selc_near.release(); b -> selc_p10.release(); b -> selc_p11.release(); b -> selc_bp.release();
-  b -> selc_out.release();
   delete b;
 }
 
@@ -1163,6 +1150,83 @@ static void harm_pp_sizes(const llsm_gpu_batch* b, float fmin, int* lds_n, int* 
   *lds_n = std::min(n, LLSM_LDS_FFT_MAX);
 }
 
+// Harmonic stage of the analysis (llsm_refine_f0 + llsm_harmonic_analysis, dsputils.c:72-94, 175-228), for
+// llsm_gpu_batch_analyze and the per-frame API alike: F0 refinement if the options or `refine_only` ask for it, then NHAR,
+// AMPL and PHSE by peak picking (HMPP) or by k_harm_speech (HMCZT); refine_only stops after the refinement.  *pp_lds_n /
+// *pp_nmax: the transform sizes HMPP ran with (0 otherwise), which the envelope peak picking of the analysis takes again.
+static int harmonic_stage(llsm_gpu_batch* b, const BatchDev& d, int refine_only, int* pp_lds_n, int* pp_nmax) {
+  llsm_gpu_context* c = b -> ctx;
+  LaunchCtx* P = & c -> lc;
+  const bool hmpp = b -> opt.hm_method == LLSM_AOPTION_HMPP;
+  // lowest F0 of the batch (sizes the LDS of the peak-picking FFT)
+  // (unknown -- the F0 row was written through its device pointer --: the largest provision there is)
+  float fmin = b -> min_f0 > 0 ? b -> min_f0 : 1.0f;
+  fmin *= 0.9f;                                       // refinement may lower F0 by < 10 %
+  if(hmpp && ! refine_only && hmpp_window_too_long(b)) return -1;      // (refused before the F0 row is touched)
+  if(b -> opt.f0_refine || refine_only) {
+    RUN(launch_refine_f0(P, d));
+    note_refined_f0(b);
+  }
+  *pp_lds_n = *pp_nmax = 0;
+  if(refine_only) return 0;
+  if(hmpp) {
+    // one FFT size per utterance (llsm_get_fftsize, dsputils.c:318-326), decided on the device
+    // after F0 refinement; LDS is provisioned for the largest size the batch can need
+    harm_pp_sizes(b, fmin, pp_lds_n, pp_nmax);
+    if(b -> nfft_u.alloc(b -> lay.n_utt)) return -1;
+    RUN(launch_utt_fftsize(P, d, *pp_nmax, b -> nfft_u.p));
+    if(run_harm_pp(c, P, d, b, d.x, 0, 1, b -> lay.maxnhar, *pp_lds_n, *pp_nmax, d.nhar, d.ampl, d.phse)) return -1;
+  } else {
+    RUN(launch_harm_speech(P, d, fmin));
+  }
+  return 0;
+}
+
+// The second stream of ONE analysis call (the context's aux stream and its two events, created on first use).  fork()
+// makes it wait for everything enqueued on the first stream so far and says whether launches may go to lc(); a HIP failure
+// there is cleared and leaves the branch unusable for the rest of the call, whose launches then all stay on the first
+// stream.  record() marks the end of what the branch holds; join() makes the first stream wait for that mark (recording it
+// if nobody has).  Once work sits on the second stream, EVERY way out of the call joins it: an early return would
+// otherwise leave it reading env / psd_log and writing the PSD rows while the caller tears the batch down (llsm_dev_free is
+// a caching pool: no implicit synchronisation) -- ADVICE r3.  The destructor does that for the returns that skip join().
+class AuxBranch {
+  llsm_gpu_context* c; LaunchCtx ctx;
+  bool on, pending = false, recorded = false;           // pending: the second stream holds work the first does not wait for yet
+ public:
+  AuxBranch(llsm_gpu_context* ctx_, bool overlap) : c(ctx_), ctx(ctx_ -> lc), on(overlap) {}
+  AuxBranch(const AuxBranch&) = delete; AuxBranch& operator=(const AuxBranch&) = delete;
+  bool usable() const { return on; }
+  LaunchCtx* lc() { return & ctx; }
+  bool fork() {
+    if(! on) return false;
+    if(! c -> aux) {
+      if(hipStreamCreateWithFlags(& c -> aux, hipStreamNonBlocking) != hipSuccess ||
+         hipEventCreateWithFlags(& c -> ev_fork, hipEventDisableTiming) != hipSuccess ||
+         hipEventCreateWithFlags(& c -> ev_join, hipEventDisableTiming) != hipSuccess) c -> aux = nullptr;
+    }
+    if(! c -> aux || hipEventRecord(c -> ev_fork, c -> stream) != hipSuccess || hipStreamWaitEvent(c -> aux, c -> ev_fork, 0) != hipSuccess) {
+      (void)hipGetLastError();
+      return on = false;
+    }
+    ctx.stream = c -> aux; pending = true; recorded = false;
+    return true;
+  }
+  int record() { HIP_OK(hipEventRecord(c -> ev_join, c -> aux)); recorded = true; return 0; }
+  int join() {
+    if(! pending) return 0;
+    if(! recorded && record()) return -1;
+    HIP_OK(hipStreamWaitEvent(c -> stream, c -> ev_join, 0));
+    pending = false;
+    return 0;
+  }
+  ~AuxBranch() {
+    if(! pending) return;
+    // the join event may not have been recorded (the failure was the launch or the record itself): drain the stream
+    (void)hipStreamSynchronize(c -> aux);
+    (void)hipGetLastError();
+  }
+};
+
 extern "C" int llsm_gpu_batch_analyze(llsm_gpu_batch* b) {
   if(! b) { llsm_set_error("llsm_gpu_batch_analyze: no batch"); return -1; }
   llsm_gpu_context* c = b -> ctx;
@@ -1222,26 +1286,8 @@ extern "C" int llsm_gpu_batch_analyze(llsm_gpu_batch* b) {
   }
   BatchDev d = batch_dev(b, b -> fs);
   LaunchCtx* P = & c -> lc;
-  // lowest F0 of the batch (sizes the LDS of the peak-picking FFT)
-  // (unknown -- the F0 row was written through its device pointer --: the largest provision there is)
-  float fmin = b -> min_f0 > 0 ? b -> min_f0 : 1.0f;
-  fmin *= 0.9f;                                       // refinement may lower F0 by < 10 %
-  if(hmpp && hmpp_window_too_long(b)) return -1;      // (refused before the F0 row is touched)
-  if(b -> opt.f0_refine) {
-    RUN(launch_refine_f0(P, d));
-    note_refined_f0(b);
-  }
   int pp_lds_n = 0, pp_nmax = 0;
-  if(hmpp) {
-    // one FFT size per utterance (llsm_get_fftsize, dsputils.c:318-326), decided on the device
-    // after F0 refinement; LDS is provisioned for the largest size the batch can need
-    harm_pp_sizes(b, fmin, & pp_lds_n, & pp_nmax);
-    if(b -> nfft_u.alloc(L.n_utt)) return -1;
-    RUN(launch_utt_fftsize(P, d, pp_nmax, b -> nfft_u.p));
-    if(run_harm_pp(c, P, d, b, d.x, 0, 1, L.maxnhar, pp_lds_n, pp_nmax, d.nhar, d.ampl, d.phse)) return -1;
-  } else {
-    RUN(launch_harm_speech(P, d, fmin));
-  }
+  if(harmonic_stage(b, d, 0, & pp_lds_n, & pp_nmax)) return -1;
   RUN(launch_synth_ola(P, d, b -> sin_units.p, b -> n_sin_units, b -> sin_halo, b -> nwin_sin, b -> win_sin.p,
     std::min(L.maxnhar, 2048), b -> d_x_off.p, b -> d_nx.p, d.x, xres, 0, nullptr));   // x_res = x - harmonic part
   {
@@ -1251,105 +1297,44 @@ extern "C" int llsm_gpu_batch_analyze(llsm_gpu_batch* b) {
     if(b -> spgm_fix.alloc(npairs) || b -> spgm_fix_count.alloc(1)) return -1;
     HIP_OK(hipMemsetAsync(b -> spgm_fix_count.p, 0, sizeof(int), c -> stream));
   }
-  // Second stream (not while profiling -- the per-kernel events assume one stream -- and not with llsm_gpu_analysis_overlap(0)):
+  // Second stream (AuxBranch; off with llsm_gpu_analysis_overlap(0), on while profiling: the events go to the stream of the launch):
   //  * the FIX launch of the spectrogram envelope (a few dozen wavefronts, 0.05 ms of mostly launch and one pair's latency)
   //    runs beside the residual PSD frames, which do not read the envelope rows;
   //  * the smoother needs the two planes and nothing below needs its rows: it runs beside the band filter and the envelope
   //    analysis (measured in one process, tools/ab_overlap.py: 4.11 -> 4.08 ms per analysis step -- the dispatcher
   //    interleaves the launches only at their edges: two Kalman wavefronts hold a SIMD's registers).
-  // Once work sits on the second stream, EVERY way out of this function joins it: the early returns of RUN / HIP_OK
-  // below would otherwise leave it reading env / psd_log and writing the PSD rows while the caller tears the
-  // batch down (llsm_dev_free is a caching pool: no implicit synchronisation) -- ADVICE r3.
-  struct AuxJoin {
-    llsm_gpu_context* c; bool armed = false, joined = false;
-    ~AuxJoin() {
-      if(! armed || joined) return;
-      // the join event may not have been recorded (the failure was the launch or the record itself): drain the stream
-      (void)hipStreamSynchronize(c -> aux);
-      (void)hipGetLastError();
-    }
-  } aux_join{c};
-  bool use_aux = g_overlap.load() > 0;
-  if(use_aux && ! c -> aux) {
-    if(hipStreamCreateWithFlags(& c -> aux, hipStreamNonBlocking) != hipSuccess ||
-       hipEventCreateWithFlags(& c -> ev_fork, hipEventDisableTiming) != hipSuccess ||
-       hipEventCreateWithFlags(& c -> ev_join, hipEventDisableTiming) != hipSuccess) { c -> aux = nullptr; (void)hipGetLastError(); }
-  }
-  if(! c -> aux) use_aux = false;
-  LaunchCtx Pa = *P; Pa.stream = c -> aux;
-  RUN(launch_spgm_env(P, d, b -> nwin_psd, b -> nfft_spgm, ilog2(b -> nfft_spgm), b -> nfft_psd,
-    b -> norm_base, c -> tw, c -> tw_nmax, b -> env.p, b -> spgm_fix.p, b -> spgm_fix_count.p, use_aux ? 1 : 3));
-  bool fix_on_aux = false;
-  if(use_aux) {
-    if(hipEventRecord(c -> ev_fork, c -> stream) == hipSuccess && hipStreamWaitEvent(c -> aux, c -> ev_fork, 0) == hipSuccess) {
-      aux_join.armed = true;
-      RUN(launch_spgm_env(& Pa, d, b -> nwin_psd, b -> nfft_spgm, ilog2(b -> nfft_spgm), b -> nfft_psd,
-        b -> norm_base, c -> tw, c -> tw_nmax, b -> env.p, b -> spgm_fix.p, b -> spgm_fix_count.p, 2));
-      fix_on_aux = true;
-    } else {
-      (void)hipGetLastError();
-      RUN(launch_spgm_env(P, d, b -> nwin_psd, b -> nfft_spgm, ilog2(b -> nfft_spgm), b -> nfft_psd,
-        b -> norm_base, c -> tw, c -> tw_nmax, b -> env.p, b -> spgm_fix.p, b -> spgm_fix_count.p, 2));
-      use_aux = false;
-    }
-  }
+  AuxBranch aux(c, g_overlap.load() > 0);
+  auto spgm_env = [&](LaunchCtx* Q, int which) -> int {
+    RUN(launch_spgm_env(Q, d, b -> nwin_psd, b -> nfft_spgm, ilog2(b -> nfft_spgm), b -> nfft_psd,
+      b -> norm_base, c -> tw, c -> tw_nmax, b -> env.p, b -> spgm_fix.p, b -> spgm_fix_count.p, which));
+    return 0;
+  };
+  if(spgm_env(P, aux.usable() ? 1 : 3)) return -1;
+  if(aux.usable() && spgm_env(aux.fork() ? aux.lc() : P, 2)) return -1;
   if(b -> nfft_psd > LLSM_LDS_FFT_MAX && llsm_engine_big_fft(c, b -> nfft_psd, (size_t)llsm_big_fft_grid((size_t)b -> nfft_psd) * b -> nfft_psd)) return -1;
   RUN(launch_psd_frames(P, d, xres, b -> nwin_psd, b -> win_psd.p, b -> inv_wpow, b -> nfft_psd,
     ilog2(b -> nfft_psd), c -> tw, c -> tw_nmax, b -> psd_log.p));
-  bool forked = false;
-  if(use_aux) {
-    // (the smoother follows the FIX launch on the second stream and waits there for the PSD frames of the first)
-    if(hipEventRecord(c -> ev_fork, c -> stream) == hipSuccess && hipStreamWaitEvent(c -> aux, c -> ev_fork, 0) == hipSuccess) {
-      aux_join.armed = true;
-      RUN(launch_kalman(& Pa, d, b -> env.p, b -> psd_log.p, b -> pbuf.p, (int)nspec));
-      HIP_OK(hipEventRecord(c -> ev_join, c -> aux));
-      forked = true;
-    } else (void)hipGetLastError();
+  if(aux.fork()) {                                      // the smoother follows the FIX launch there and waits for the PSD frames of the first stream
+    RUN(launch_kalman(aux.lc(), d, b -> env.p, b -> psd_log.p, b -> pbuf.p, (int)nspec));
+    if(aux.record()) return -1;
+  } else {                                              // it stays on the first stream, which must see the FIX launch's rows
+    if(aux.join()) return -1;
+    RUN(launch_kalman(P, d, b -> env.p, b -> psd_log.p, b -> pbuf.p, (int)nspec));
   }
-  if(! forked && fix_on_aux) {                          // the smoother stays on the first stream: it must see the FIX launch's rows
-    HIP_OK(hipEventRecord(c -> ev_join, c -> aux));
-    HIP_OK(hipStreamWaitEvent(c -> stream, c -> ev_join, 0));
-    aux_join.joined = true;
-  }
-  if(! forked) RUN(launch_kalman(P, d, b -> env.p, b -> psd_log.p, b -> pbuf.p, (int)nspec));
   RUN(launch_filtfilt(P, b -> jobs_ana.p, b -> njobs_ana, b -> sections.p));
   b -> ce_filled = true;
   RUN(launch_harm_env(P, d, b -> ce.p, X));          // edc for every frame (+ CZT envelopes)
   if(hmpp && L.maxnhar_e > 0)                         // HMPP: envelopes by peak picking instead
     if(run_harm_pp(c, P, d, b, b -> ce.p, X, L.nchannel, L.maxnhar_e, pp_lds_n, pp_nmax, d.nhar_e, d.eenv_ampl, d.eenv_phse)) return -1;
-  if(forked) {
-    HIP_OK(hipStreamWaitEvent(c -> stream, c -> ev_join, 0));               // everything later on the stream sees the smoother's rows
-    aux_join.joined = true;
-  }
-  return 0;
+  return aux.join();                                    // everything later on the stream sees the smoother's rows
 }
 
-// Harmonic stage of the analysis alone (llsm_refine_f0 + llsm_harmonic_analysis, dsputils.c:72-94, 175-228):
-// outputs F0 (refined), NHAR, AMPL, PHSE.  Used by the per-frame API (frameapi.cpp).
+// Harmonic stage of the analysis alone: outputs F0 (refined), NHAR, AMPL, PHSE.  Used by the per-frame API (frameapi.cpp).
 int llsm_engine_batch_harmonics(llsm_gpu_batch* b, int refine_only) {
-  llsm_gpu_context* c = b -> ctx;
-  hipSetDevice(c -> device);
-  const llsm_gpu_layout& L = b -> lay;
-  if(L.total_frames == 0 || L.total_samples == 0) return 0;
-  const bool hmpp = b -> opt.hm_method == LLSM_AOPTION_HMPP;
-  BatchDev d = batch_dev(b, b -> fs);
-  LaunchCtx* P = & c -> lc;
-  float fmin = b -> min_f0 > 0 ? b -> min_f0 : 1.0f;
-  fmin *= 0.9f;
-  if(hmpp && ! refine_only && hmpp_window_too_long(b)) return -1;
-  if(b -> opt.f0_refine || refine_only) {
-    RUN(launch_refine_f0(P, d));
-    note_refined_f0(b);
-  }
-  if(refine_only) return 0;
-  if(hmpp) {
-    int pp_lds_n = 0, pp_nmax = 0;
-    harm_pp_sizes(b, fmin, & pp_lds_n, & pp_nmax);
-    if(b -> nfft_u.alloc(L.n_utt)) return -1;
-    RUN(launch_utt_fftsize(P, d, pp_nmax, b -> nfft_u.p));
-    if(run_harm_pp(c, P, d, b, d.x, 0, 1, L.maxnhar, pp_lds_n, pp_nmax, d.nhar, d.ampl, d.phse)) return -1;
-  } else RUN(launch_harm_speech(P, d, fmin));
-  return 0;
+  hipSetDevice(b -> ctx -> device);
+  if(b -> lay.total_frames == 0 || b -> lay.total_samples == 0) return 0;
+  int pp_lds_n = 0, pp_nmax = 0;
+  return harmonic_stage(b, batch_dev(b, b -> fs), refine_only, & pp_lds_n, & pp_nmax);
 }
 
 // chebyfilt (dsputils.c:51-70) of one device signal: zero-phase low / high / band-pass, optionally squared.
@@ -1358,55 +1343,31 @@ int llsm_engine_chebyfilt(llsm_gpu_context* c, const float* d_src, int n, float 
   hipSetDevice(c -> device);
   if(n <= 1) { if(n == 1) HIP_OK(hipMemcpyAsync(d_dst, d_src, sizeof(float), hipMemcpyDeviceToDevice, c -> stream)); return 0; }
   if(! c -> sections) {
-    std::vector<FiltSectionD> secs(2 * llsm_cheby::kRows);
-    for(int r = 0; r < llsm_cheby::kRows; r ++)
-      for(int hp = 0; hp < 2; hp ++) {
-        llsm_cheby::Section s = llsm_cheby::make_section_row(r, hp != 0);
-        FiltSectionD& d = secs[2 * r + hp];
-        std::memcpy(d.b, s.b, sizeof(d.b)); std::memcpy(d.a, s.a, sizeof(d.a)); std::memcpy(d.zi, s.zi, sizeof(d.zi));
-        llsm_cheby::block_tables(s.a, IIR_SEG, 6, & d.H[0][0], & d.M[0][0]);
-      }
+    const std::vector<FiltSectionD> secs = make_filt_sections();
     HIP_OK(hipMalloc((void**)& c -> sections, secs.size() * sizeof(FiltSectionD)));
     HIP_OK(hipMemcpy(c -> sections, secs.data(), secs.size() * sizeof(FiltSectionD), hipMemcpyHostToDevice));
   }
   if(c1 < 0) c1 = 0;
   if(c2 > 0.5f) c2 = 0.5f;
   FiltJob j; std::memset(& j, 0, sizeof(j));
-  float *mid = nullptr, *tmp = nullptr; FiltJob* dj = nullptr;
-  HIP_OK(hipMalloc((void**)& mid, sizeof(float) * (size_t)n));
-  if(hipMalloc((void**)& tmp, sizeof(float) * ((size_t)n + 32)) != hipSuccess || hipMalloc((void**)& dj, sizeof(FiltJob)) != hipSuccess) {
-    hipFree(mid); hipFree(tmp); llsm_set_error("chebyfilt: out of memory"); return -1;
-  }
-  j.src = d_src; j.dst = d_dst; j.mid = mid; j.tmp = tmp; j.n = n; j.square = square; j.pad = g_hconv.filtfilt_pad;
+  DevBuf<float> mid, tmp; DevBuf<FiltJob> dj;          // freed on return: every way out below waits for the stream first
+  if(mid.alloc((size_t)n) || tmp.alloc((size_t)n + 32) || dj.alloc(1)) { llsm_set_error("chebyfilt: out of memory"); return -1; }
+  j.src = d_src; j.dst = d_dst; j.mid = mid.p; j.tmp = tmp.p; j.n = n; j.square = square; j.pad = g_hconv.filtfilt_pad;
   if(c1 != 0 && c2 < 0.5f) { j.sec0 = 2 * llsm_cheby::row_of(c1) + 1; j.sec1 = 2 * llsm_cheby::row_of(c2); }
   else if(c1 == 0) { j.sec0 = 2 * llsm_cheby::row_of(c2); j.sec1 = -1; }
   else { j.sec0 = 2 * llsm_cheby::row_of(c1) + 1; j.sec1 = -1; }
-  int rc = hipMemcpy(dj, & j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess;
-  if(! rc) rc = launch_filtfilt(& c -> lc, dj, 1, c -> sections);
+  int rc = hipMemcpy(dj.p, & j, sizeof(j), hipMemcpyHostToDevice) != hipSuccess;
+  if(! rc) rc = launch_filtfilt(& c -> lc, dj.p, 1, c -> sections);
   if(hipStreamSynchronize(c -> stream) != hipSuccess) rc = -1;
-  hipFree(mid); hipFree(tmp); hipFree(dj);
   if(rc) { llsm_set_error("chebyfilt: launch failed"); return -1; }
   return 0;
 }
 
-extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions* so,
-  unsigned long long seed, int use_injected_white) {
-  if(! b || ! so) { llsm_set_error("llsm_gpu_batch_synthesize: no batch / options"); return -1; }
+// What the synthesis of a batch needs once per sampling rate: the window lengths and the noise-filter transform, the two Hann
+// windows, the envelope overlap-add plan and the work units of the fused noise filter and of the persistent excitation.
+static int synthesis_plan(llsm_gpu_batch* b, float fs) {
   llsm_gpu_context* c = b -> ctx;
-  hipSetDevice(c -> device);
-  if(so -> use_l1 && b -> l1_nspec == 0) {
-    llsm_set_error("use_l1: the batch carries no layer-1 members (llsm_gpu_batch_enable_layer1 / _tolayer1)");
-    return -1;
-  }
-  if(so -> fs != b -> fs) {
-    llsm_set_error("llsm_soptions.fs must equal the sampling rate the batch was created with");
-    return -1;
-  }
-  if(follow_conventions(b)) return -1;
-  const llsm_gpu_layout& L = b -> lay;
-  if(L.total_frames == 0 || L.total_out == 0) return 0;
-  const float fs = so -> fs, thop = b -> opt.thop;
-  const size_t F = L.total_frames, Y = L.total_out, nch = L.nchannel;
+  const float thop = b -> opt.thop;
   if(b -> syn_fs != fs) {
     b -> nwin_env = lp::nwin_env(thop, fs);
     b -> nwin_filt = lp::nwin_filt(thop, fs);
@@ -1470,25 +1431,70 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
     b -> wsym_filt = hann_sym(b -> nwin_filt);
     b -> syn_fs = fs; b -> njobs_syn = 0;
   }
-  if(so -> use_l1 && llsm_l1_prefetch_rows(b, so)) return -1;
-  const size_t tplsz = (size_t)L.n_utt * nch * L.ntemplate_ext;
+  return 0;
+}
+
+// Template stage of the synthesis, and all of llsm_engine_template_batch: the scratch of the band filter, its jobs (built
+// again when the scratch has moved), Gaussian templates unless the caller injected its own, and the filter over them.
+static int template_stage(llsm_gpu_batch* b, const BatchDev& d, float fs, bool make_white, unsigned long long seed) {
+  const llsm_gpu_layout& L = b -> lay;
+  LaunchCtx* P = & b -> ctx -> lc;
+  const size_t tplsz = (size_t)L.n_utt * L.nchannel * L.ntemplate_ext;
   if(b -> colored.alloc(tplsz) || b -> mid.alloc(tplsz) ||
-     b -> iir_tmp.alloc((size_t)L.n_utt * nch * (L.ntemplate_ext + 32)) ||
-     b -> env_cplx.alloc(F * nch * std::max(L.maxnhar_e, 1)) || b -> yexc.alloc(Y)) return -1;
+     b -> iir_tmp.alloc((size_t)L.n_utt * L.nchannel * (L.ntemplate_ext + 32))) return -1;
   float* white = (float*)b -> arr[LLSM_GPU_WHITE];
-  {
-    const void* key[3] = {b -> colored.p, b -> mid.p, b -> iir_tmp.p};
-    if(b -> njobs_syn == 0 || std::memcmp(key, b -> key_syn, sizeof(key))) {
-      if(build_jobs(b, 1, fs, nullptr, white)) return -1;
-      std::memcpy(b -> key_syn, key, sizeof(key));
-    }
+  const void* key[3] = {b -> colored.p, b -> mid.p, b -> iir_tmp.p};
+  if(b -> njobs_syn == 0 || std::memcmp(key, b -> key_syn, sizeof(key))) {
+    if(build_jobs(b, 1, fs, nullptr, white)) return -1;
+    std::memcpy(b -> key_syn, key, sizeof(key));
   }
-  BatchDev d = batch_dev(b, fs);
-  LaunchCtx* P = & c -> lc;
-  float* ysin = (float*)b -> arr[LLSM_GPU_YSIN];
-  if(! use_injected_white) RUN(launch_white(P, d, white, L.ntemplate_ext, b -> d_ny.p, seed));
+  if(make_white) RUN(launch_white(P, d, white, L.ntemplate_ext, b -> d_ny.p, seed));
   RUN(launch_filtfilt(P, b -> jobs_syn.p, b -> njobs_syn, b -> sections.p));
   b -> colored_filled = true;
+  return 0;
+}
+
+// The noise part when the fused kernel does not serve (transforms beyond its 2048 points, or $LLSM_GPU_NOISE_OLA=0): the
+// shaped frames go to HBM and the mix gathers them into y_noise and writes y = ysin + y_noise.
+static int noise_unfused(llsm_gpu_batch* b, const BatchDev& d, float fs, const float* ysin) {
+  llsm_gpu_context* c = b -> ctx;
+  LaunchCtx* P = & c -> lc;
+  const size_t F = b -> lay.total_frames;
+  if(b -> nframes.alloc(F * b -> nfft_filt) || b -> live.alloc(F)) return -1;
+  if(b -> nfft_filt > LLSM_LDS_FFT_MAX &&
+     llsm_engine_big_fft(c, b -> nfft_filt, (size_t)llsm_big_fft_grid((size_t)b -> nfft_filt + b -> nfft_filt / 2 + 1) * (size_t)(b -> nfft_filt + b -> nfft_filt / 2 + 1))) return -1;
+  RUN(launch_noise_filter(P, d, b -> yexc.p, b -> d_y_off.p, b -> d_ny.p, b -> fnyq, fs,
+    b -> nwin_filt, b -> win_filt.p, b -> inv_wsqr, b -> nfft_filt, ilog2(b -> nfft_filt),
+    c -> tw, c -> tw_nmax, b -> nframes.p, b -> live.p, 0));
+  RUN(launch_ola_noise_mix(P, d, b -> nframes.p, b -> live.p, b -> nfft_filt,
+    b -> d_y_off.p, b -> d_ny.p, b -> max_ny, fs, ysin, (float*)b -> arr[LLSM_GPU_YNOISE], (float*)b -> arr[LLSM_GPU_Y]));
+  return 0;
+}
+
+extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions* so,
+  unsigned long long seed, int use_injected_white) {
+  if(! b || ! so) { llsm_set_error("llsm_gpu_batch_synthesize: no batch / options"); return -1; }
+  llsm_gpu_context* c = b -> ctx;
+  hipSetDevice(c -> device);
+  if(so -> use_l1 && b -> l1_nspec == 0) {
+    llsm_set_error("use_l1: the batch carries no layer-1 members (llsm_gpu_batch_enable_layer1 / _tolayer1)");
+    return -1;
+  }
+  if(so -> fs != b -> fs) {
+    llsm_set_error("llsm_soptions.fs must equal the sampling rate the batch was created with");
+    return -1;
+  }
+  if(follow_conventions(b)) return -1;
+  const llsm_gpu_layout& L = b -> lay;
+  if(L.total_frames == 0 || L.total_out == 0) return 0;
+  const float fs = so -> fs;
+  const size_t F = L.total_frames, Y = L.total_out, nch = L.nchannel;
+  if(synthesis_plan(b, fs)) return -1;
+  if(so -> use_l1 && llsm_l1_prefetch_rows(b, so)) return -1;
+  BatchDev d = batch_dev(b, fs);
+  LaunchCtx* P = & c -> lc;
+  if(template_stage(b, d, fs, ! use_injected_white, seed)) return -1;
+  if(b -> env_cplx.alloc(F * nch * std::max(L.maxnhar_e, 1)) || b -> yexc.alloc(Y)) return -1;
   // noise excitation: persistent units (k_excite_units) where the geometry allows and $LLSM_GPU_EXCITE4 is unset; set,
   // it selects the per-sample kernel after k_env_params
   const char* e4 = std::getenv("LLSM_GPU_EXCITE4");   // (read per call: tests switch it)
@@ -1498,50 +1504,34 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
     b -> nwin_env, b -> win_env.p, b -> nch_active, b -> d_y_off.p, b -> d_ny.p, b -> max_ny, fs,
     b -> yexc.p, b -> exu_units.p, b -> n_exu_units));
   // b -> fnyq: the PSD rows' axis (conf FNYQ; analysis fs / 2, layer0.c:481).  Transforms up to 2048 points: filter and overlap-add
-  // in one kernel (the shaped frames stay on chip); larger ones: frames to HBM, gathered by the mix.
-  float* ynoise = (float*)b -> arr[LLSM_GPU_YNOISE];
+  // in one kernel (the shaped frames stay on chip); larger ones: frames to HBM, gathered by the mix (noise_unfused).
+  float *ysin = (float*)b -> arr[LLSM_GPU_YSIN], *ynoise = (float*)b -> arr[LLSM_GPU_YNOISE], *yout = (float*)b -> arr[LLSM_GPU_Y];
   static const bool fused_ok = [] { const char* e = std::getenv("LLSM_GPU_NOISE_OLA"); return !(e && e[0] == '0'); }();
-  int fused = -2;
-  if(fused_ok)
-    fused = launch_noise_filter_ola(P, d, b -> nf_units.p, b -> n_nf_units, b -> nf_halo, b -> yexc.p,
+  bool have_fused_kernel = false;
+  if(fused_ok) {
+    const int rc = launch_noise_filter_ola(P, d, b -> nf_units.p, b -> n_nf_units, b -> nf_halo, b -> yexc.p,
       b -> d_y_off.p, b -> d_ny.p, b -> fnyq, fs, b -> nwin_filt, b -> win_filt.p, b -> wsym_filt, b -> inv_wsqr,
       ilog2(b -> nfft_filt), ynoise);
-  if(fused != 0 && fused != -2) {
-    llsm_set_error(std::string("launch_noise_filter_ola failed: ") + hipGetErrorString((hipError_t)fused));
-    return -1;
+    if(rc != 0 && rc != -2) {                           // -2: the fused kernel has no instantiation for this transform
+      llsm_set_error(std::string("launch_noise_filter_ola failed: ") + hipGetErrorString((hipError_t)rc));
+      return -1;
+    }
+    have_fused_kernel = rc == 0;
   }
-  float* yout = (float*)b -> arr[LLSM_GPU_Y];
   if(so -> use_l1) {
     // layer0.c:148-287: the harmonic part is the HM <-> pulse-by-pulse cross-fade state machine (l1.cpp);
-    // the noise part first (fallback path: frames to HBM, gathered against a silent harmonic part)
-    if(fused == -2) {
-      if(b -> nframes.alloc(F * b -> nfft_filt) || b -> live.alloc(F)) return -1;
-      if(b -> nfft_filt > LLSM_LDS_FFT_MAX &&
-         llsm_engine_big_fft(c, b -> nfft_filt, (size_t)llsm_big_fft_grid((size_t)b -> nfft_filt + b -> nfft_filt / 2 + 1) * (size_t)(b -> nfft_filt + b -> nfft_filt / 2 + 1))) return -1;
+    // the noise part first (unfused: gathered against a silent harmonic part)
+    if(! have_fused_kernel) {
       HIP_OK(hipMemsetAsync(ysin, 0, Y * sizeof(float), c -> stream));
-      RUN(launch_noise_filter(P, d, b -> yexc.p, b -> d_y_off.p, b -> d_ny.p, b -> fnyq, fs,
-        b -> nwin_filt, b -> win_filt.p, b -> inv_wsqr, b -> nfft_filt, ilog2(b -> nfft_filt),
-        c -> tw, c -> tw_nmax, b -> nframes.p, b -> live.p, 0));
-      RUN(launch_ola_noise_mix(P, d, b -> nframes.p, b -> live.p, b -> nfft_filt,
-        b -> d_y_off.p, b -> d_ny.p, b -> max_ny, fs, ysin, ynoise, yout));
+      if(noise_unfused(b, d, fs, ysin)) return -1;
     }
     return llsm_l1_synthesize_harmonics(b, so, ynoise, ysin, yout);
   }
   // harmonic part last: its overlap-add flush also writes y = y_sin + y_noise when y_noise is in place
   RUN(launch_synth_ola(P, d, b -> sin_units.p, b -> n_sin_units, b -> sin_halo, b -> nwin_sin, b -> win_sin.p,
-    std::min(L.maxnhar, 2048), b -> d_y_off.p, b -> d_ny.p, fused == 0 ? ynoise : nullptr, ysin, 1,
-    fused == 0 ? yout : nullptr));
-  if(fused == -2) {
-    if(b -> nframes.alloc(F * b -> nfft_filt) || b -> live.alloc(F)) return -1;
-    if(b -> nfft_filt > LLSM_LDS_FFT_MAX &&
-       llsm_engine_big_fft(c, b -> nfft_filt, (size_t)llsm_big_fft_grid((size_t)b -> nfft_filt + b -> nfft_filt / 2 + 1) * (size_t)(b -> nfft_filt + b -> nfft_filt / 2 + 1))) return -1;
-    RUN(launch_noise_filter(P, d, b -> yexc.p, b -> d_y_off.p, b -> d_ny.p, b -> fnyq, fs,
-      b -> nwin_filt, b -> win_filt.p, b -> inv_wsqr, b -> nfft_filt, ilog2(b -> nfft_filt),
-      c -> tw, c -> tw_nmax, b -> nframes.p, b -> live.p, 0));
-    RUN(launch_ola_noise_mix(P, d, b -> nframes.p, b -> live.p, b -> nfft_filt,
-      b -> d_y_off.p, b -> d_ny.p, b -> max_ny, fs, ysin, ynoise, yout));
-  }
-  return 0;
+    std::min(L.maxnhar, 2048), b -> d_y_off.p, b -> d_ny.p, have_fused_kernel ? ynoise : nullptr, ysin, 1,
+    have_fused_kernel ? yout : nullptr));
+  return have_fused_kernel ? 0 : noise_unfused(b, d, fs, ysin);
 }
 
 // ---- internal helpers for rt.cpp (declared in engine.h) --------------------
@@ -1554,18 +1544,7 @@ llsm_gpu_batch* llsm_engine_template_batch(llsm_gpu_context* ctx, const llsm_aop
   llsm_gpu_batch* b = llsm_gpu_create_batch(ctx, opt, fs, S, z.data(), z.data());
   if(! b) return nullptr;
   for(int u = 0; u < S; u ++) b -> ny[u] = len;
-  const llsm_gpu_layout& L = b -> lay;
-  const size_t tplsz = (size_t)S * L.nchannel * L.ntemplate_ext;
-  bool bad = upload_vec(b -> d_ny, b -> ny) || b -> colored.alloc(tplsz) || b -> mid.alloc(tplsz) ||
-    b -> iir_tmp.alloc((size_t)S * L.nchannel * (L.ntemplate_ext + 32));
-  float* white = (float*)b -> arr[LLSM_GPU_WHITE];
-  if(! bad) bad = build_jobs(b, 1, fs, nullptr, white) != 0;
-  if(! bad) {
-    BatchDev d = batch_dev(b, fs);
-    bad = launch_white(& ctx -> lc, d, white, L.ntemplate_ext, b -> d_ny.p, seed) != 0 ||
-          launch_filtfilt(& ctx -> lc, b -> jobs_syn.p, b -> njobs_syn, b -> sections.p) != 0;
-  }
-  if(bad) { llsm_gpu_delete_batch(b); return nullptr; }
+  if(upload_vec(b -> d_ny, b -> ny) || template_stage(b, batch_dev(b, fs), fs, true, seed)) { llsm_gpu_delete_batch(b); return nullptr; }
   return b;
 }
 const float* llsm_engine_batch_colored(llsm_gpu_batch* b) { return b -> colored.p; }

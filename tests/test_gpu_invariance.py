@@ -204,6 +204,31 @@ def test_fanout_block_size_does_not_change_long_utterances():
         L.llsm_gpu_set_fanout(-1, -1, -1)
 
 
+@pytest.mark.parametrize("hm_method", [llsm.HMCZT, llsm.HMPP], ids=["hmczt", "hmpp"])
+def test_second_stream_does_not_change_the_analysis(ctx, hm_method):
+    """A6: llsm_gpu_analysis_overlap(0) keeps every launch of the analysis on one stream, (1) forks the FIX launch of the
+    spectrogram envelope and the smoother onto the second and joins them: the same kernels on the same inputs, so every
+    analysed array is the same bit for bit.  A fork or join in the wrong place shows as stale or differing PSD rows."""
+    L = llsm.load()
+    utts = [make_speechlike(71, nx=6615), make_speechlike(72, nx=4410)]      # 0.15 s and 0.1 s: 30 and 20 frames
+    xs, f0s = [x for x, _ in utts], [f.astype(np.float32) for _, f in utts]
+    ao = llsm.make_aoptions(f0_refine=1, hm_method=hm_method)
+    prev = L.llsm_gpu_analysis_overlap(-1)
+    got = {}
+    try:
+        for on in (0, 1):
+            L.llsm_gpu_analysis_overlap(on)
+            b, g, xres = gpu_analyze(ctx, ao, FS, xs, f0s)
+            b.close()
+            got[on] = dict(g); got[on]["xres"] = xres
+    finally:
+        L.llsm_gpu_analysis_overlap(prev)
+    assert set(got[0]) == set(llsm.Batch.PARAM_IDS) | {"xres"}
+    assert np.abs(got[0][llsm.A_AMPL]).max() > 0 and np.ptp(got[0][llsm.A_PSD]) > 0 and np.abs(got[0][llsm.A_EDC]).max() > 0
+    assert not np.array_equal(got[0][llsm.A_F0], np.concatenate(f0s))        # (the refinement ran)
+    _assert_same(got[1], got[0], "second stream on against off")
+
+
 # envelope plane at the edge points of the cancelling frame against the float64 oracle's resampled envelope (natural-log
 # units).  The register-resident path with its list-and-redo launch meets it on WF_REFERENCE_CASE (seed 123208, frame 43:
 # 1.0e-5 at both points on an MI355X); the LDS kernel without exact edge bins was 1.7e-3 .. 3.0e-2 off on the pinned cases.

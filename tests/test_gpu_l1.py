@@ -1011,3 +1011,40 @@ def test_alpha_cache_follows_rewritten_rows(ctx, o64, speech):
         for u, v, name in zip(got, ref, ("y", "ampl", "phse", "nhar")):
             assert np.array_equal(u, v), (what, name, float(np.abs(u.astype(np.float64) - v).max()))
     assert not np.array_equal(again[0], first[0])
+
+
+# hop 0.009 s at 96 kHz = 864 samples: nextpow2(2 x 864 x 1.2 + 32) = 4096 points, beyond the 2048 of the fused noise
+# filter + overlap-add (hop > 840 samples leaves it), so both branches of the synthesis take the unfused path there
+@pytest.mark.parametrize("fs,thop", [(FS, 0.005), (96000.0, 0.009)], ids=["fused", "unfused_4096"])
+def test_noise_part_does_not_depend_on_use_l1(ctx, speech, fs, thop):
+    """The same rows, templates and seed give the same y_noise, bit for bit, whether the harmonic part is the layer-0
+    overlap-add or the layer-1 state machine: neither k_noise_filter_ola nor k_ola_noise_mix reads y_sin when it forms
+    y_noise (the mix only adds it into y), so only the order of the launches around the noise part differs."""
+    x, f0, ao0, pr, q = speech
+    sl = slice(30, 70)                                           # 40 frames: voiced, then the unvoiced middle
+    n = sl.stop - sl.start
+    ao = llsm.make_aoptions(f0_refine=0, thop=thop)
+    rows = {a: np.ascontiguousarray(v[sl]) for a, v in params_to_gpu_rows(pr).items()}
+    qq = q32(q); qq.has_hm[:] = 0
+    qq.pbpsyn[:] = (np.arange(pr.nfrm) % 20 > 10).astype(np.int32)
+    l1 = {a: np.ascontiguousarray(v[sl]) for a, v in l1_rows(qq).items()}
+    assert np.count_nonzero(rows[llsm.A_F0]) >= 20 and 0 < l1[llsm.A_PBPSYN].sum() < n
+
+    def ynoise(use_l1):
+        b = llsm.Batch(ctx, ao, fs, [0], [n])
+        try:
+            b.upload_params(rows); b.enable_layer1(2048)
+            for aid, a in l1.items():
+                b.upload(aid, a)
+            b.L.llsm_gpu_batch_set_maxnhar_conf(b.h, ao.maxnhar)
+            b.synthesize(llsm.make_soptions(fs, use_l1=use_l1), seed=5); ctx.sync()
+            return b.download(llsm.A_YNOISE), b.download(llsm.A_YSIN)
+        finally:
+            b.close()
+
+    (yn0, ys0), (yn1, ys1) = ynoise(0), ynoise(1)
+    assert np.sqrt(np.mean(yn0 ** 2)) > 1e-4 and np.abs(ys0).max() > 0 and np.abs(ys1).max() > 0
+    assert not np.array_equal(ys0, ys1)                          # (the harmonic parts do differ: pulses against harmonics)
+    if not np.array_equal(yn0, yn1):
+        d = np.abs(yn0.astype(np.float64) - yn1)
+        raise AssertionError(f"y_noise differs in {np.count_nonzero(d)} of {d.size} samples, max |diff| {d.max():.3g}")
