@@ -29,6 +29,7 @@
 
 #include "batch.h"
 #include "lfmodel.h"
+#include "model_internal.h"
 #include "plan.h"
 
 namespace lp = llsm_plan;
@@ -589,8 +590,6 @@ struct L1Host {
 // layer-0 rows a layer-1 conversion needs: f0, nhar, ampl, phse
 struct HmHost { std::vector<float> f0, ampl, phse; std::vector<int> nhar; };
 
-int chunk_nfrm_(llsm_chunk* c) { int* n = (int*)llsm_container_get(c -> conf, LLSM_CONF_NFRM); return n ? *n : -1; }
-
 // a parameter-only batch of one utterance holding the HM rows of `frames`
 llsm_gpu_batch* hm_batch(llsm_container** frames, int nfrm, llsm_container* conf, int maxnhar, float fnyq, float thop,
   float lip_radius, HmHost& h) {
@@ -729,7 +728,7 @@ static void frames_tolayer0(llsm_container** frames, int n, llsm_container* conf
 extern "C" void llsm_frame_tolayer0(llsm_container* dst, llsm_container* conf) { frames_tolayer0(& dst, 1, conf); }
 
 extern "C" void llsm_chunk_tolayer0(llsm_chunk* dst) {
-  const int nfrm = chunk_nfrm_(dst);
+  const int nfrm = llsm_chunk_nfrm(dst);
   if(nfrm > 0) frames_tolayer0(dst -> frames, nfrm, dst -> conf);
 }
 
@@ -742,7 +741,7 @@ int llsm_l1_prepare_batch(llsm_gpu_batch* b, llsm_chunk** src, int n_utt, const 
   llsm_flat_l1 v = o.view();
   for(int u = 0; u < n_utt; u ++) {
     if(llsm_chunk_to_flat_l1(src[u], & v, fo[u])) return -1;
-    const int nf = chunk_nfrm_(src[u]);
+    const int nf = llsm_chunk_nfrm(src[u]);
     for(int i = 0; i < nf; i ++) {
       llsm_pbpeffect* ef = (llsm_pbpeffect*)llsm_container_get(src[u] -> frames[i], LLSM_FRAME_PBPEFF);
       if(ef) llsm_gpu_batch_set_pbpeffect(b, fo[u] + i, ef -> modifier, ef -> info, src[u] -> frames[i]);
@@ -764,7 +763,7 @@ int llsm_l1_writeback_hm(llsm_gpu_batch* b, llsm_chunk** src, int n_utt, const i
   std::vector<float> ampl(F * mh), phse(F * mh);
   if(llsm_gpu_batch_download(b, LLSM_GPU_AMPL, ampl.data(), ampl.size() * 4) || llsm_gpu_batch_download(b, LLSM_GPU_PHSE, phse.data(), phse.size() * 4)) return -1;
   for(int u = 0; u < n_utt; u ++) {
-    const int nf = chunk_nfrm_(src[u]);
+    const int nf = llsm_chunk_nfrm(src[u]);
     for(int i = 0; i < nf; i ++) {
       const size_t g = (size_t)fo[u] + i;
       if(! has[g] || b -> l1_had_hm[g]) continue;

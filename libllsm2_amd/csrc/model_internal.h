@@ -7,6 +7,11 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* LLSM_CONF_NFRM of a chunk; -1 when its conf has none */
+static inline int llsm_chunk_nfrm(llsm_chunk* c) {
+  int* n = (int*)llsm_container_get(c -> conf, LLSM_CONF_NFRM);
+  return n ? *n : -1;
+}
 /* realloc for a member array of a frame that may live in a frame slab (model.cpp): never hands slab memory to the
  * allocator; keep_bytes of the old contents are carried over */
 void* llsm_model_regrow(void* p, size_t keep_bytes, size_t new_bytes);
