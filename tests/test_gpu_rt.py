@@ -6,11 +6,38 @@ import numpy as np
 import pytest
 
 import libllsm2_amd as llsm
+import rt_reference
 from conftest import FS, make_speechlike
-from gpu_common import oracle_analyze, rel_rms, report
+from gpu_common import CONVENTION_NAMES, oracle_analyze, rel_rms, report
 from verify_utils import assert_reference_acceptance
 
 pytestmark = pytest.mark.gpu
+
+
+def synced(o32):
+    """the float32 build of the oracle is a library of its own: give it the product's conventions (gpu_common.oracle32_metrics)"""
+    L = llsm.load()
+    for name in CONVENTION_NAMES:
+        o32.set_convention(name, L.llsm_gpu_get_convention(name.encode()))
+    return o32
+
+
+def assert_rt_samples(o32, fs, p32, seed, yp, yap, yp_o, yap_o, where):
+    """The stream sample by sample against the float64 oracle's (yp_o, yap_o), under the bounds of
+    tests/test_gpu_rt_samples.py (rt_reference.rt_violations).  p32: the float32-rounded rows both sides synthesised.  The
+    float32 oracle's own ysin_local on the stream is consulted only where the plain 60 is exceeded."""
+    sched = rt_reference.rt_schedule(p32.nfrm, p32.thop, fs)
+    m = rt_reference.rt_metrics(p32, sched, yp, yp_o, yap, yap_o)
+    y32 = 0.0
+    if m["ysin_local"] > rt_reference.YSIN_LOCAL:
+        o32 = synced(o32)
+        yp32, yap32, _ = o32.rt_run(o32.soptions(fs), p32.astype(np.float32), seed=seed)
+        y32 = rt_reference.rt_metrics(p32, sched, yp32, yp_o, yap32, yap_o)["ysin_local"]
+        m["ysin_local_f32_oracle"] = y32
+    print("[rt samples] %s: %s" % (where, {k: m[k] for k in ("ysin_local", "ysin_local_at", "ysin_nonzero_uncovered", "ynoise_local", "ynoise_local_at")}))
+    bad = rt_reference.rt_violations(m, y32)
+    assert not bad, (where, bad)
+    return m
 
 
 def chunk_from_oracle(L, ao, pr, fs):
@@ -51,7 +78,7 @@ def rt_run(L, so, ch, nfrm, capacity=4096):
 
 
 @pytest.mark.parametrize("thop", [0.005, 128 / 44100.0])
-def test_rt_matches_oracle_rt(o64, thop):
+def test_rt_matches_oracle_rt(o64, o32, thop):
     L = llsm.load()
     x, _ = make_speechlike(3, nx=26000)
     nfrm = int(len(x) / FS / thop)
@@ -74,6 +101,7 @@ def test_rt_matches_oracle_rt(o64, thop):
              p_abs_max=float(np.abs(yp - yp_o).max()), ap_abs_max=float(np.abs(yap - yap_o).max()))
     report(f"rt_thop{int(round(thop * FS))}", m)
     assert m["p_rel_rms"] <= 1e-4 and m["ap_rel_rms"] <= 1e-4, m
+    assert_rt_samples(o32, FS, p32, seed, yp, yap, yp_o, yap_o, "rt_thop%d" % int(round(thop * FS)))
 
 
 def test_rt_vs_offline_and_threaded(o64):
@@ -146,14 +174,14 @@ def test_rt_create_rejects_bad_conf():
     L.llsm_delete_container(conf)
 
 
-def test_rt_group_equals_single_streams(o64):
+def test_rt_group_equals_single_streams(o64, o32):
     """BASELINE.json config 4 shape: a group of lock-stepped streams fed one hop per call and
     drained with 256-sample pulls gives, per stream, exactly what a single-stream buffer with
     the same seed gives (stream s uses seed + s)."""
     L = llsm.load()
     S = 5
     thop = 0.005
-    chunks, nfrm = [], None
+    chunks, rows, nfrm = [], [], None
     ao = llsm.make_aoptions(f0_refine=0, thop=thop)
     for s in range(S):
         x, _ = make_speechlike(20 + s, nx=15000)
@@ -165,6 +193,7 @@ def test_rt_group_equals_single_streams(o64):
             f0[:] = 0                                            # an all-unvoiced stream
         pr, _ = oracle_analyze(o64, ao, FS, x, f0)
         chunks.append(chunk_from_oracle(L, ao, pr, FS)); nfrm = n
+        rows.append(pr.astype(np.float32).astype(np.float64))
     so = llsm.make_soptions(FS)
     seed = 900
     # reference: each stream alone
@@ -213,6 +242,11 @@ def test_rt_group_equals_single_streams(o64):
         # the noise filter packs two streams into one complex FFT, so a stream's rounding
         # depends on its pair partner: equal to float32 rounding, not bit-for-bit
         assert rel_rms(yap, singles[s][1]) < 2e-6, s
+        # ... and the oracle run of seed + s is the arbiter of both, sample by sample
+        yp_o, yap_o, lat_o = o64.rt_run(o64.soptions(FS), rows[s], seed=seed + s)
+        assert lat_o == lat and len(yp_o) == len(yp)
+        assert_rt_samples(o32, FS, rows[s], seed + s, yp, yap, yp_o, yap_o, "rt_group stream %d" % s)
+        assert_rt_samples(o32, FS, rows[s], seed + s, singles[s][0], singles[s][1], yp_o, yap_o, "rt_group stream %d alone" % s)
     for ch in chunks:
         L.llsm_delete_chunk(ch)
 
@@ -257,7 +291,7 @@ def test_rt_large_group_packed_by_helper_threads(o64):
 
 
 @pytest.mark.parametrize("seed", range(8))
-def test_rt_random_configurations(o64, seed):
+def test_rt_random_configurations(o64, o32, seed):
     """Seeded fuzz of llsmrt over sampling rate, hop (integer and fractional), band plan and harmonic limits: the
     streaming output must match the oracle's restatement of llsmrt.c sample for sample (same latency, same length)."""
     from test_gpu_configs import _fuzz_case
@@ -283,6 +317,7 @@ def test_rt_random_configurations(o64, seed):
     report("rt_fuzz_%02d" % seed, m)
     assert lat == lato and len(yp) == len(ypo), (lat, lato, len(yp), len(ypo))
     assert m["p_rel_rms"] <= 1e-5 and m["ap_rel_rms"] <= 1e-5, m
+    assert_rt_samples(o32, fs, p32, seed_rng, yp, yap, ypo, yapo, "rt_fuzz_%02d" % seed)
 
 
 def _group_run(L, so, chunks, nfrm, seed):
