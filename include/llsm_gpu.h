@@ -368,6 +368,62 @@ int llsm_gpu_batch_splice(llsm_gpu_batch* dst, const llsm_gpu_batch* src, const 
 enum { LLSM_GPU_WARP_PSD = 1 };
 int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0_ratio, const FP_TYPE* formant_ratio, int flags);
 
+/* ---- smoothing of parameter tracks around joins: a triangular weighted mean along the frames of a layer-1 batch, in place,
+ * of F0, RD, VTMAGN, PSD and EDC -- the tracks that step where llsm_gpu_batch_splice renders an index list of
+ * llsm_gpu_batch_select that hops between recordings.  No phase row is touched and nothing is averaged in a logarithmic
+ * domain.  Asynchronous on the context's stream; a refused call returns -1, sets llsm_gpu_last_error() (the message starts
+ * with "llsm_gpu_batch_smooth:" and names the frame at fault) and writes and launches nothing.
+ *
+ * radius  host, total_frames ints in the batch's flat frame order: the reach of the mean of every frame, 0: not touched.
+ * flags   an OR of LLSM_GPU_SMOOTH_*: the tracks that are smoothed.
+ *
+ * The rules, for frame g = frm_off[u] + i of an utterance u of n frames, with R = radius[g].  Every value read below is
+ * the value the rows held BEFORE the call: the call works on a snapshot, never on a value it has just written.
+ *  S1. R == 0: the frame is not touched, every row bit for bit, AMPL, PHSE, NHAR and HAS_HM included.
+ *  S2. Frame j is voiced when F0[j] != 0.  The window starts as [max(0, i - R), min(n - 1, i + R)], frames of utterance u
+ *      only: it never crosses into a neighbouring utterance of the flat arrays.  It is then shrunk from both ends to the
+ *      largest interval around i in which every frame has frame i's voicing: a track is never averaged across a voicing
+ *      change.  The result is [lo, hi], lo <= i <= hi.
+ *  S3. lo == hi: the frame is not touched, as in S1.
+ *  S4. The weights are w_j = R + 1 - |j - i| (integers >= 1) and W is their sum over j = lo ... hi.  For a track x,
+ *          S(x) = (float)( (sum over j = lo ... hi of (double)w_j * (double)x_j) / (double)W ):
+ *      the sum is float64, starts from 0.0 and runs over j ascending with one addition per term; every product is exact in
+ *      float64, so contraction cannot change a bit; the division and the conversion to float32 are correctly rounded.  The
+ *      order of the additions is part of the contract.
+ *  S5. Voiced frame: F0, RD and every bin of VTMAGN become S(.) of their tracks where LLSM_GPU_SMOOTH_F0, _RD and _VTMAGN
+ *      are set; there is no floor on VTMAGN.  If any of these three flags is set, NHAR = 0 and HAS_HM = 0, so that
+ *      llsm_gpu_batch_tolayer0(b, 1) rebuilds the harmonics; the AMPL and PHSE rows are not written.  Every point of PSD
+ *      and every channel of EDC become S(.) where LLSM_GPU_SMOOTH_PSD and _EDC are set.
+ *  S6. Unvoiced frame: PSD and EDC as in S5 where flagged; nothing else changes.
+ *  S7. Never written: VSPHSE, NVSPHSE, PSDRES, HAS_PSDRES, EENV_AMPL, EENV_PHSE, NHAR_E, PBPSYN, per-frame effects and the
+ *      waveforms.
+ *  S8. An output frame depends on its own radius and on the at most 65 frames of its own utterance in its window, and on
+ *      nothing else in the batch: not on its place in the batch, on other radii or on earlier calls.
+ *  S9. The batch's lowest-F0 bound stays as it is: a weighted mean of voiced F0 values, rounded monotonically, is never
+ *      below their minimum.
+ * Refused, every check before anything changes: a NULL batch or a NULL radius; a batch without layer 1; flag bits outside
+ * LLSM_GPU_SMOOTH_ALL; a radius below 0 or above LLSM_GPU_SMOOTH_MAX_RADIUS; scratch that cannot be allocated.
+ * Returns 0 without a launch: flags == 0, a batch without frames, a radius that is all zeros.
+ *
+ * llsm_gpu_join_radii  host only: the radius array from the utt_a / pos_a lists of a splice map (llsm_gpu_splice_map,
+ *   llsm_gpu_batch_select).  nfrm holds the n_utt frame counts of the destination, utt_a and pos_a one entry per
+ *   destination frame in flat order; utt_a NULL: every frame's source is its own utterance, as in the splice map.  In a
+ *   destination utterance at flat offset o a join lies between frames i - 1 and i (1 <= i < n) unless
+ *   utt_a[o + i] == utt_a[o + i - 1] and pos_a[o + i] == pos_a[o + i - 1] + 1 in float32 (the natural continuation of rule
+ *   S3 of llsm_gpu_batch_select).  The distance of frame i to a join at i_j is i - i_j for i >= i_j and i_j - 1 - i below
+ *   it, and radius[o + i] = max(0, reach - d) with d the least distance to a join of the utterance: the two frames at a
+ *   join get reach and the radius falls by one per frame to 0; an utterance without joins gets zeros.  Returns the number
+ *   of joins, or -1 with a message ("llsm_gpu_join_radii: ...") for a NULL nfrm, pos_a or radius, a negative count, or a
+ *   reach outside [0, LLSM_GPU_SMOOTH_MAX_RADIUS]; radius is then untouched.
+ * Known limit: the mean is linear in the rows' own units (VTMAGN in dB, F0 in Hz), and the window is cut, not faded, at a
+ * voicing change. */
+enum { LLSM_GPU_SMOOTH_F0 = 1, LLSM_GPU_SMOOTH_RD = 2, LLSM_GPU_SMOOTH_VTMAGN = 4,
+       LLSM_GPU_SMOOTH_PSD = 8, LLSM_GPU_SMOOTH_EDC = 16, LLSM_GPU_SMOOTH_ALL = 31 };
+enum { LLSM_GPU_SMOOTH_MAX_RADIUS = 32 };
+int llsm_gpu_batch_smooth(llsm_gpu_batch* b, const int* radius, int flags);
+int llsm_gpu_join_radii(int n_utt, const int* nfrm, const int* utt_a, const FP_TYPE* pos_a,
+                        int reach, int* radius);   /* host only */
+
 /* ---- F0 estimation: LLSM_GPU_X -> LLSM_GPU_F0 on the device, a YIN-style estimator (difference function, cumulative mean
  * normalised difference "CMNDF", first dip below a threshold, parabolic fit, median of five).  It is the estimator of
  * tests/golden/make_f0_track.py on the batch's frame grid and decides every frame alone; llsm_gpu_batch_track_f0 below

@@ -151,7 +151,7 @@ llsm_chunk_blob_size llsm_chunk_to_blob llsm_blob_view llsm_blob_to_chunk llsm_b
 llsm_create_rtsynth_group llsm_delete_rtsynth_group llsm_rtsynth_group_getlatency
 llsm_rtsynth_group_numoutput llsm_rtsynth_group_feed llsm_rtsynth_group_feed_many llsm_rtsynth_group_fetch llsm_rtsynth_group_fetch_all llsm_gpu_rt_graph llsm_gpu_rt_graph_hops llsm_gpu_rt_fused llsm_gpu_rt_direct llsm_gpu_rt_pipeline llsm_gpu_analysis_overlap llsm_slab_stats llsm_slab_trim llsm_delete_chunks llsm_gpu_release_cached_batches llsm_gpu_device_numa_node llsm_gpu_bind_thread_to_device llsm_gpu_batch_packed_words llsm_gpu_batch_download_packed llsm_gpu_batch_upload_packed llsm_gpu_batch_download_outputs llsm_gpu_batch_download_packed_block llsm_gpu_batch_upload_packed_block llsm_gpu_batch_transfer_many llsm_gpu_batch_params_layout llsm_gpu_batch_transfer_params llsm_gpu_shared_f0_tiles llsm_gpu_synth_tables llsm_gpu_pbp_real_ifft llsm_frame_compute_snr
 llsm_gpu_batch_phasesync_rps llsm_gpu_batch_phasepropagate llsm_gpu_batch_retime llsm_gpu_retime_uniform_positions
-llsm_gpu_batch_pitch_formant llsm_gpu_batch_splice
+llsm_gpu_batch_pitch_formant llsm_gpu_batch_splice llsm_gpu_batch_smooth llsm_gpu_join_radii
 llsm_gpu_batch_enable_coder llsm_gpu_batch_coder_dimension llsm_gpu_batch_encode llsm_gpu_batch_decode
 llsm_blob_bytes llsm_gpu_batch_blob_sizes llsm_gpu_batch_download_blobs llsm_gpu_batch_download_blob_block
 llsm_gpu_f0_default_options llsm_gpu_f0_plan llsm_gpu_batch_estimate_f0
@@ -224,6 +224,12 @@ def load():
     L.llsm_gpu_retime_uniform_positions.restype = None
     L.llsm_gpu_batch_pitch_formant.argtypes = [vp, P_fp, P_fp, C.c_int]
     L.llsm_gpu_batch_splice.argtypes = [vp, vp, C.POINTER(SpliceMap)]
+    try:                                                 # (as below: an experiment build of an earlier commit lacks the smoothing)
+        L.llsm_gpu_batch_smooth.argtypes = [vp, P_int, C.c_int]
+        L.llsm_gpu_join_radii.argtypes = [C.c_int, P_int, P_int, P_fp, C.c_int, P_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
     L.llsm_gpu_f0_default_options.argtypes = [C.POINTER(F0Options)]
     L.llsm_gpu_f0_default_options.restype = None
     L.llsm_gpu_f0_plan.argtypes = [C.POINTER(F0Options), fp, P_int, P_int, P_int, P_int]
@@ -587,6 +593,43 @@ def per_frame_ratio(value, nfrm):
                      % (v.shape, len(nfrm), F))
 
 
+# LLSM_GPU_SMOOTH_* (llsm_gpu_batch_smooth)
+SMOOTH_F0, SMOOTH_RD, SMOOTH_VTMAGN, SMOOTH_PSD, SMOOTH_EDC, SMOOTH_ALL = 1, 2, 4, 8, 16, 31
+SMOOTH_MAX_RADIUS = 32
+
+
+def per_frame_radius(value, total_frames):
+    """a smooth radius as total_frames int32 values: a scalar is every frame's, total_frames values are taken as they
+    are; any other shape is a ValueError"""
+    F = int(total_frames)
+    v = np.asarray(value)
+    if v.dtype.kind not in "iu" and not np.array_equal(v, np.floor(v)):
+        raise ValueError("radius holds values that are not integers")
+    if v.ndim == 0:
+        return np.full(F, int(v), np.int32)
+    if v.shape == (F,):
+        return np.ascontiguousarray(v, np.int32)
+    raise ValueError("radius of shape %s: expected a scalar or %d frame values" % (v.shape, F))
+
+
+def join_radii(nfrm, pos_a, utt_a=None, reach=8):
+    """(radius, n_joins): the int32 radii Batch.smooth takes, from the lists Batch.splice renders
+    (llsm_gpu_join_radii): reach on the two frames at every join, falling by one per frame to 0; nfrm: the frame counts
+    of the destination's utterances, pos_a and utt_a (None: every frame's own utterance) one entry per frame"""
+    n = np.ascontiguousarray(nfrm, np.int32)
+    F = int(n.astype(np.int64).sum()) if (n >= 0).all() else 0
+    p = np.ascontiguousarray(pos_a, np.float32)
+    u = None if utt_a is None else np.ascontiguousarray(utt_a, np.int32)
+    if (n >= 0).all() and (p.shape != (F,) or (u is not None and u.shape != (F,))):
+        raise ValueError("pos_a / utt_a: expected %d frame values" % F)
+    radius = np.zeros(F, np.int32)
+    k = load().llsm_gpu_join_radii(len(n), n.ctypes.data_as(P_int), None if u is None else u.ctypes.data_as(P_int),
+                                   p.ctypes.data_as(P_fp), int(reach), radius.ctypes.data_as(P_int))
+    if k < 0:
+        raise LlsmError("join_radii: " + load().llsm_gpu_last_error().decode())
+    return radius, int(k)
+
+
 def make_soptions(fs, **kw):
     o = SOptions()
     o.fs, o.use_iczt, o.use_l1, o.iczt_param_a, o.iczt_param_b = fs, 1, 0, 0.275, 2.26
@@ -776,6 +819,12 @@ class Batch:
         _check(self.L.llsm_gpu_batch_pitch_formant(self.h, None if r is None else r.ctypes.data_as(P_fp),
                                                    None if a is None else a.ctypes.data_as(P_fp),
                                                    WARP_PSD if warp_psd else 0), "pitch_formant")
+
+    def smooth(self, radius, flags=SMOOTH_ALL):
+        """triangular means of F0, RD, VTMAGN, PSD and EDC (flags: an OR of SMOOTH_*) along the frames, in place, from a
+        snapshot of the rows (llsm_gpu_batch_smooth); radius: a scalar or total_frames ints (join_radii), 0: untouched"""
+        r = per_frame_radius(radius, self.layout.total_frames)
+        _check(self.L.llsm_gpu_batch_smooth(self.h, r.ctypes.data_as(P_int), int(flags)), "smooth")
 
     # ---- F0 estimation (llsm_gpu.h): LLSM_GPU_X -> LLSM_GPU_F0 on the device
     def estimate_f0(self, **options):

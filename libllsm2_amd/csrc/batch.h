@@ -190,8 +190,9 @@ struct llsm_gpu_batch {
   // edits (modify.cpp): per-frame phase shifts of phasepropagate; the ratios of the last llsm_gpu_batch_pitch_formant
   // ([2][F]: F0, formant) and the resolved map (kernels.h SpliceMap) of the last llsm_gpu_batch_retime ([2 or 3][F] words) or
   // llsm_gpu_batch_splice ([2 or 5][F] words) into this batch, staged in page-locked memory that mod_ev says the copies
-  // have left
-  DevBuf<float> mod_theta, mod_ratio; DevBuf<int> mod_map;
+  // have left; llsm_gpu_batch_smooth stages [tiles | radii of the listed frames] the same way, and mod_smooth holds its
+  // result rows, one per listed frame, followed by their marks (kernels.h SmoothJob)
+  DevBuf<float> mod_theta, mod_ratio, mod_smooth; DevBuf<int> mod_map;
   PinVec<int> mod_stage; hipEvent_t mod_ev = nullptr;
   // frame coder (batch_coder.cpp): the orders of LLSM_GPU_CODE (0: not enabled) and the mel axis, built once per batch
   int coder_os = 0, coder_ob = 0; float coder_mel_floor = 0, coder_mel_ceil = 0;

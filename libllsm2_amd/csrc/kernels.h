@@ -297,6 +297,18 @@ int launch_splice(LaunchCtx* P, const ModRows& src, const ModRows& dst, const Sp
 // ratios (NULL: 1), warp_psd the PSD warp; LDS: 16 (nspec + npsd) bytes per workgroup
 int launch_pitch_formant(LaunchCtx* P, const ModRows& r, int g_lo, int g_hi, const float* rho, const float* alpha,
   int warp_psd);
+// llsm_gpu_batch_smooth.  A tile is up to kSmoothTile frames g0 ... g0 + cnt - 1 of one utterance (flat frames u0 ... u1),
+// every one with a radius > 0; its frames are entries slot ... slot + cnt - 1 of the compact list: `radius` holds their
+// radii, `rows` one result row [VTMAGN | PSD | EDC | F0, RD] (smooth_row_width floats) each, and `mark` what the store does
+// with each (0: S3, left alone; 1: unvoiced; 2: voiced).  launch_smooth_rows reads the batch and writes rows and mark only;
+// launch_smooth_store, behind it on the same stream, writes the batch.  flags: LLSM_GPU_SMOOTH_*.
+const int kSmoothTile = 16, kSmoothMaxRadius = 32;
+enum { SM_F0 = 1, SM_RD = 2, SM_VTMAGN = 4, SM_PSD = 8, SM_EDC = 16 };   // LLSM_GPU_SMOOTH_* (modify.cpp asserts it)
+struct SmoothTile { int g0, cnt, u0, u1, slot; };
+struct SmoothJob { const SmoothTile* tiles; int ntiles; const int* radius; float* rows; int* mark; int flags; };
+inline int smooth_row_width(const ModRows& r) { return r.nspec + r.npsd + r.nchannel + 2; }
+int launch_smooth_rows(LaunchCtx* P, const ModRows& r, const SmoothJob& job);
+int launch_smooth_store(LaunchCtx* P, const ModRows& r, const SmoothJob& job);
 
 // ---- frame coder of a device-resident batch (batch_coder.cpp): launch_coder_encode / launch_coder_decode above on the batch's
 // rows, then the members the host decoder leaves at their llsm_create_frame values (coder_kernels.hip)

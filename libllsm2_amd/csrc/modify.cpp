@@ -11,6 +11,9 @@
 //                                    and their kernel (k_splice)
 //   llsm_gpu_batch_pitch_formant     F0 and formant ratios per frame on a layer-1 batch, the edit of the reference's
 //                                    pitch-shift recipe (rules: llsm_gpu.h)
+//   llsm_gpu_batch_smooth            triangular means of F0, RD, VTMAGN, PSD and EDC along the frames around joins, from a
+//                                    snapshot of the rows (rules: llsm_gpu.h)
+//   llsm_gpu_join_radii              the radii smooth takes, from the index lists splice renders
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -278,4 +281,98 @@ extern "C" int llsm_gpu_batch_pitch_formant(llsm_gpu_batch* b, const FP_TYPE* f0
   HIP_OK(hipEventRecord(b -> mod_ev, st));
   const int rc = launch_pitch_formant(& b -> ctx -> lc, mod_rows(b), g_lo, g_hi, dr, da, flags & LLSM_GPU_WARP_PSD);
   return rc ? launch_failed("llsm_gpu_batch_pitch_formant", rc) : 0;
+}
+
+static_assert(kSmoothMaxRadius == LLSM_GPU_SMOOTH_MAX_RADIUS, "the kernels' reach is the header's");
+static_assert(SM_F0 == LLSM_GPU_SMOOTH_F0 && SM_RD == LLSM_GPU_SMOOTH_RD && SM_VTMAGN == LLSM_GPU_SMOOTH_VTMAGN &&
+  SM_PSD == LLSM_GPU_SMOOTH_PSD && SM_EDC == LLSM_GPU_SMOOTH_EDC, "the kernels' flag bits are the header's");
+
+extern "C" int llsm_gpu_batch_smooth(llsm_gpu_batch* b, const int* radius, int flags) {
+  const char* fn = "llsm_gpu_batch_smooth";
+  if(! b) return refuse(fn, "NULL batch");
+  if(! radius) return refuse(fn, "NULL radius");
+  if(b -> l1_nspec == 0) return refuse(fn, "the batch has no layer 1 (llsm_gpu_batch_tolayer1)");
+  if(flags & ~LLSM_GPU_SMOOTH_ALL) return refuse(fn, "unknown flag bits " + std::to_string(flags & ~LLSM_GPU_SMOOTH_ALL));
+  const int F = b -> lay.total_frames;
+  size_t listed = 0;
+  for(int g = 0; g < F; g ++) {
+    if(radius[g] < 0 || radius[g] > LLSM_GPU_SMOOTH_MAX_RADIUS)
+      return refuse(fn, "radius of frame " + std::to_string(g) + " (" + std::to_string(radius[g]) + ") is outside [0, " +
+        std::to_string(LLSM_GPU_SMOOTH_MAX_RADIUS) + "]");
+    listed += radius[g] > 0;
+  }
+  if(flags == 0 || listed == 0) return 0;                          // nothing changes
+  // the listed frames (radius > 0) cut into tiles: runs of consecutive frames of one utterance, kSmoothTile at the most;
+  // staged in page-locked memory as [tiles | radii of the listed frames]
+  const size_t tile_words = sizeof(SmoothTile) / sizeof(int);
+  if(b -> mod_ev) HIP_OK(hipEventSynchronize(b -> mod_ev));         // the previous call's copy has left the stage
+  if(! b -> mod_stage.resize((tile_words + 1) * listed + 1)) return -1;
+  SmoothTile* ht = (SmoothTile*)b -> mod_stage.data();
+  int* hr = b -> mod_stage.data() + tile_words * listed;           // (at most one tile per listed frame)
+  int ntiles = 0, slot = 0;
+  for(int u = 0; u < b -> lay.n_utt; u ++) {
+    const int u0 = b -> frm_off[u], u1 = u0 + b -> nfrm[u] - 1;
+    for(int g = u0; g <= u1; g ++) {
+      if(radius[g] == 0) continue;
+      const bool grow = ntiles > 0 && ht[ntiles - 1].u0 == u0 && ht[ntiles - 1].g0 + ht[ntiles - 1].cnt == g &&
+        ht[ntiles - 1].cnt < kSmoothTile;
+      if(grow) ht[ntiles - 1].cnt ++;
+      else ht[ntiles ++] = SmoothTile{g, 1, u0, u1, slot};
+      hr[slot ++] = radius[g];
+    }
+  }
+  // the tiles move up against the radii: one block, one copy
+  const size_t words = tile_words * (size_t)ntiles + listed;
+  std::memmove(b -> mod_stage.data() + tile_words * (size_t)ntiles, hr, listed * sizeof(int));
+  hipSetDevice(b -> ctx -> device);
+  hipStream_t st = b -> ctx -> stream;
+  const ModRows rows = mod_rows(b);
+  // a failed allocation is a refusal: nothing has changed yet
+  if(b -> mod_smooth.alloc(listed * ((size_t)smooth_row_width(rows) + 1))) return -1;
+  if(b -> mod_map.alloc(words)) return -1;
+  HIP_OK(hipMemcpyAsync(b -> mod_map.p, b -> mod_stage.data(), words * sizeof(int), hipMemcpyHostToDevice, st));
+  if(! b -> mod_ev) HIP_OK(hipEventCreateWithFlags(& b -> mod_ev, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(b -> mod_ev, st));
+  SmoothJob job;
+  job.tiles = (const SmoothTile*)b -> mod_map.p; job.ntiles = ntiles;
+  job.radius = b -> mod_map.p + tile_words * (size_t)ntiles;
+  job.rows = b -> mod_smooth.p; job.mark = (int*)(b -> mod_smooth.p + listed * (size_t)smooth_row_width(rows));
+  job.flags = flags;
+  // accepted: from here on the batch changes.  The lowest-F0 bound stays (rule S9).
+  int rc = launch_smooth_rows(& b -> ctx -> lc, rows, job);
+  if(! rc) rc = launch_smooth_store(& b -> ctx -> lc, rows, job);
+  return rc ? launch_failed(fn, rc) : 0;
+}
+
+extern "C" int llsm_gpu_join_radii(int n_utt, const int* nfrm, const int* utt_a, const FP_TYPE* pos_a, int reach,
+  int* radius) {
+  const char* fn = "llsm_gpu_join_radii";
+  if(! nfrm || ! pos_a || ! radius) return refuse(fn, ! nfrm ? "NULL nfrm" : (! pos_a ? "NULL pos_a" : "NULL radius"));
+  if(n_utt < 0) return refuse(fn, "n_utt = " + std::to_string(n_utt) + " is negative");
+  for(int u = 0; u < n_utt; u ++)
+    if(nfrm[u] < 0) return refuse(fn, "nfrm[" + std::to_string(u) + "] = " + std::to_string(nfrm[u]) + " is negative");
+  if(reach < 0 || reach > LLSM_GPU_SMOOTH_MAX_RADIUS)
+    return refuse(fn, "reach = " + std::to_string(reach) + " is outside [0, " + std::to_string(LLSM_GPU_SMOOTH_MAX_RADIUS) + "]");
+  int joins = 0;
+  for(int u = 0, o = 0; u < n_utt; o += nfrm[u], u ++) {
+    const int n = nfrm[u];
+    auto join_at = [&](int i) {                                    // between frames i - 1 and i, 1 <= i < n
+      const float next = pos_a[o + i - 1] + 1.0f;                  // (float32, one rounding)
+      return !((! utt_a || utt_a[o + i] == utt_a[o + i - 1]) && pos_a[o + i] == next);
+    };
+    // distance to the last join at or below i, then to the first join above it
+    int d = reach;
+    for(int i = 0; i < n; i ++) {
+      if(i >= 1 && join_at(i)) { d = 0; joins ++; }
+      radius[o + i] = reach - d;
+      if(d < reach) d ++;
+    }
+    d = reach;
+    for(int i = n - 1; i >= 1; i --) {
+      if(join_at(i)) d = 0;                                         // frame i - 1 is at distance 0
+      if(reach - d > radius[o + i - 1]) radius[o + i - 1] = reach - d;
+      if(d < reach) d ++;
+    }
+  }
+  return joins;
 }

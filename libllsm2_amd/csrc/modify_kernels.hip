@@ -12,6 +12,12 @@
 //                   themselves P of two frames of any utterance of another batch (retime: one side, the frame's own
 //                   utterance); four consecutive output frames per 256-thread workgroup, 16-byte stores, 16-byte loads at
 //                   the source's own alignment, only the frames' scalars in LDS
+//   k_smooth_rows   llsm_gpu_batch_smooth, first half: the triangular float64 means of F0, RD, VTMAGN, PSD and EDC of a tile
+//                   of up to 16 consecutive frames into scratch rows; a thread owns a column, walks the tile's source frames
+//                   once in ascending order and adds each value into the register accumulators of the outputs whose window
+//                   holds the frame
+//   k_smooth_store  second half, behind it on the stream: the scratch rows back into the batch, 16-byte stores where the
+//                   span allows, NHAR = HAS_HM = 0 on smoothed voiced frames
 //
 // No `#pragma clang fp contract(fast)` here: the phase kernels reproduce the host's float64 arithmetic bit for bit and the
 // blends are x_a + (x_b - x_a) r without contraction (the library is built with -ffp-contract=off).
@@ -351,6 +357,176 @@ __global__ __launch_bounds__(kPfThreads) void k_pitch_formant(ModRows r, int g_l
   __syncthreads();
   if(do_vt) pf_write(gv, lv, ns, nf, s_warpvt, s_vt, s_alpha, s_comp, tid);
   if(do_psd) pf_write(gp, lp_, np, nf, s_psd, nullptr, s_alpha, s_comp, tid);
+}
+
+// ---- llsm_gpu_batch_smooth (rules S1 - S9 of llsm_gpu.h)
+namespace {
+const int kSmThreads = 256;
+const int kSmReach = kSmoothTile + 2 * kSmoothMaxRadius;  // frames whose voicing the windows of one tile may ask for
+
+// one frame of a tile as its threads share it: the window [lo, hi] of rule S2 and R + 1 in one word -- lo and hi counted
+// from the first frame of the tile's reach, bits 0 - 7 and 8 - 15, R + 1 in bits 16 - 23 --, the sum of the weights and the
+// mark the store goes by (0: rule S3 or no frame, 1: unvoiced, 2: voiced)
+struct SmFrame { int win, wsum, mark; };
+const int kSmNoWindow = 0xff;                             // lo = 255 > hi = 0: holds no frame
+DEV int sm_reach0(const SmoothTile& t) { return max(t.u0, t.g0 - kSmoothMaxRadius); }
+
+// The frames of tile t planned from the F0 row: the F0 values within the tile's reach come into LDS once, then thread f
+// shrinks the window of frame f to its voicing run.  Entries f >= t.cnt get no window.
+DEV void sm_plan(const ModRows& r, const SmoothTile& t, const int* __restrict__ radius, float* s_f0, SmFrame* s_frm, int tid) {
+  const int b0 = sm_reach0(t), b1 = min(t.u1, t.g0 + t.cnt - 1 + kSmoothMaxRadius);
+  for(int q = tid; q <= b1 - b0; q += kSmThreads) s_f0[q] = r.f0[b0 + q];       // (at most kSmReach values)
+  __syncthreads();
+  if(tid < kSmoothTile) {
+    SmFrame F = {kSmNoWindow, 1, 0};
+    if(tid < t.cnt) {
+      const int g = t.g0 + tid, R = radius[t.slot + tid];
+      const bool v = s_f0[g - b0] != 0.0f;
+      const int wlo = max(t.u0, g - R), whi = min(t.u1, g + R);
+      int lo = g, hi = g;
+      while(lo > wlo && (s_f0[lo - 1 - b0] != 0.0f) == v) lo --;
+      while(hi < whi && (s_f0[hi + 1 - b0] != 0.0f) == v) hi ++;
+      int wsum = 0;
+      for(int j = lo; j <= hi; j ++) wsum += R + 1 - abs(j - g);
+      F.win = (lo - b0) | (hi - b0) << 8 | (R + 1) << 16; F.wsum = wsum; F.mark = lo == hi ? 0 : (v ? 2 : 1);
+    }
+    s_frm[tid] = F;
+  }
+  __syncthreads();
+}
+
+// One track of the tile: `width` columns, element k of frame j of the reach (flat frame b0 + j) at x[j * stride + k], results
+// into column k of the scratch rows at `out` (row_w floats apart).  want: the least mark that takes part (2: a track of
+// voiced frames only).  c0: the tile's first frame, counted from b0.
+// A thread owns column k: it walks the source frames from the tile's smallest lo to its largest hi once, ascending, loads
+// x_j[k] once and adds w x into the float64 accumulator of every output whose window holds j -- so every output's additions
+// come in ascending j (rule S4).  The windows are wave-uniform (one scalar register each), the accumulators registers
+// indexed by the unrolled loops alone.
+DEV void sm_track(const float* __restrict__ x, int stride, int width, int want, const SmFrame* s_frm, int c0,
+  float* __restrict__ out, int row_w, int tid) {
+  int win[kSmoothTile];
+  int jmin = 0x7fffffff, jmax = -1;
+#pragma unroll
+  for(int f = 0; f < kSmoothTile; f ++) {
+    win[f] = __builtin_amdgcn_readfirstlane(s_frm[f].mark >= want ? s_frm[f].win : kSmNoWindow);
+    const int lo = win[f] & 0xff, hi = win[f] >> 8 & 0xff;
+    if(lo <= hi) { jmin = min(jmin, lo); jmax = max(jmax, hi); }
+  }
+  if(jmax < 0) return;                                    // no frame of the tile takes part in this track
+  const int lane = tid & 63;
+  for(int k0 = tid - lane; k0 < width; k0 += kSmThreads) {
+    const int k = k0 + lane;
+    const bool live = k < width;
+    double acc[kSmoothTile];
+#pragma unroll
+    for(int f = 0; f < kSmoothTile; f ++) acc[f] = 0.0;
+    for(int j = jmin; j <= jmax; j ++) {
+      const double xv = live ? (double)x[(size_t)j * stride + k] : 0.0;
+#pragma unroll
+      for(int f = 0; f < kSmoothTile; f ++) {
+        int w = win[f];
+        asm volatile("" : "+s"(w));                       // unpacked here, every time: hoisted out of the loop the three
+                                                          // fields of sixteen windows spilled scalar registers
+        if(j >= (w & 0xff) && j <= (w >> 8 & 0xff)) acc[f] = acc[f] + (double)((w >> 16) - abs(j - (c0 + f))) * xv;
+      }
+    }
+    if(live) {
+#pragma unroll
+      for(int f = 0; f < kSmoothTile; f ++) {
+        int w = win[f];
+        asm volatile("" : "+s"(w));                       // (as above: sixteen conditions kept as lane masks spilled too)
+        if((w & 0xff) <= (w >> 8 & 0xff)) out[(size_t)f * row_w + k] = (float)(acc[f] / (double)s_frm[f].wsum);
+      }
+    }
+  }
+}
+
+// The span of one track (W floats per frame) of a tile's nf frames, from the scratch rows at `sc` (row_w floats apart) back
+// into the batch's row at d; frames with ok[f] == 0 are left alone.  d starts wherever its frame index leaves it: single
+// floats up to the first 16-byte boundary, then float4 where all four elements belong to frames that are written, single
+// floats elsewhere and behind the last float4.
+DEV void sm_span(float* __restrict__ d, const float* __restrict__ sc, int W, int row_w, int nf, const int* ok, int tid) {
+  const int n = nf * W;
+  const int head = min(n, (int)((4 - (((size_t)d >> 2) & 3)) & 3)), n4 = (n - head) >> 2;
+  auto one = [&](int e) { const int f = e / W; if(ok[f]) d[e] = sc[(size_t)f * row_w + (e - f * W)]; };
+  if(tid < head) one(tid);
+  for(int q = tid; q < n4; q += kSmThreads) {
+    const int e = head + 4 * q, f1 = (e + 3) / W;
+    int f = e / W, k = e - f * W;
+    bool all = true;
+    for(int ff = f; ff <= f1; ff ++) all = all && ok[ff];
+    if(all) {
+      float o[4];
+      for(int j = 0; j < 4; j ++) { o[j] = sc[(size_t)f * row_w + k]; if(++ k == W) { k = 0; f ++; } }
+      *(float4*)(d + e) = make_float4(o[0], o[1], o[2], o[3]);
+    } else for(int j = 0; j < 4; j ++) one(e + j);
+  }
+  for(int e = head + (n4 << 2) + tid; e < n; e += kSmThreads) one(e);
+}
+}  // namespace
+
+// One workgroup per tile (blockIdx.x) and track (blockIdx.y: bit y of the flags; a track that is not flagged ends at once).
+// Reads the batch, writes job.rows and job.mark only: the store runs behind it on the stream, so every mean is formed from
+// the rows as they were before the call.  Every workgroup of a tile plans the same windows and writes the same marks.
+__global__ __launch_bounds__(kSmThreads) void k_smooth_rows(ModRows r, SmoothJob job) {
+  __shared__ float s_f0[kSmReach];
+  __shared__ SmFrame s_frm[kSmoothTile];
+  const int track = 1 << blockIdx.y;
+  if(!(job.flags & track)) return;
+  const SmoothTile t = job.tiles[blockIdx.x];
+  const int tid = threadIdx.x;
+  sm_plan(r, t, job.radius, s_f0, s_frm, tid);
+  if(tid < t.cnt) job.mark[t.slot + tid] = s_frm[tid].mark;
+  const int ns = r.nspec, np = r.npsd, nch = r.nchannel, row_w = ns + np + nch + 2;
+  const float* x; int width, col;
+  switch(track) {
+    case SM_F0: x = r.f0; width = 1; col = ns + np + nch; break;
+    case SM_RD: x = r.rd; width = 1; col = ns + np + nch + 1; break;
+    case SM_VTMAGN: x = r.vtmagn; width = ns; col = 0; break;
+    case SM_PSD: x = r.psd; width = np; col = ns; break;
+    default: x = r.edc; width = nch; col = ns + np; break;
+  }
+  const int b0 = sm_reach0(t);
+  sm_track(x + (size_t)b0 * width, width, width, track & (SM_PSD | SM_EDC) ? 1 : 2, s_frm, t.g0 - b0,
+    job.rows + (size_t)t.slot * row_w + col, row_w, tid);
+}
+
+// One workgroup per tile, the same tiles.  Unflagged tracks and frames of mark 0 (rule S3) are skipped; a voiced frame with
+// any of its three tracks smoothed loses its harmonic model (rule S5).
+__global__ __launch_bounds__(kSmThreads) void k_smooth_store(ModRows r, SmoothJob job) {
+  __shared__ int s_v[kSmoothTile], s_n[kSmoothTile];
+  const SmoothTile t = job.tiles[blockIdx.x];
+  const int tid = threadIdx.x;
+  if(tid < kSmoothTile) {
+    const int m = tid < t.cnt ? job.mark[t.slot + tid] : 0;
+    s_v[tid] = m == 2; s_n[tid] = m != 0;
+  }
+  __syncthreads();
+  const int ns = r.nspec, np = r.npsd, nch = r.nchannel, row_w = ns + np + nch + 2;
+  const float* sc = job.rows + (size_t)t.slot * row_w;
+  const size_t G0 = (size_t)t.g0;
+  if(job.flags & SM_VTMAGN) sm_span(r.vtmagn + G0 * ns, sc, ns, row_w, t.cnt, s_v, tid);
+  if(job.flags & SM_PSD) sm_span(r.psd + G0 * np, sc + ns, np, row_w, t.cnt, s_n, tid);
+  if(job.flags & SM_EDC) sm_span(r.edc + G0 * nch, sc + ns + np, nch, row_w, t.cnt, s_n, tid);
+  if(tid < t.cnt && s_v[tid]) {
+    const float* row = sc + (size_t)tid * row_w + ns + np + nch;
+    const size_t g = G0 + tid;
+    if(job.flags & SM_F0) r.f0[g] = row[0];
+    if(job.flags & SM_RD) r.rd[g] = row[1];
+    if(job.flags & (SM_F0 | SM_RD | SM_VTMAGN)) { r.nhar[g] = 0; r.has_hm[g] = 0; }
+  }
+}
+
+int launch_smooth_rows(LaunchCtx* P, const ModRows& r, const SmoothJob& job) {
+  if(job.ntiles <= 0) return 0;
+  LAUNCH("k_smooth_rows", k_smooth_rows, dim3(job.ntiles, 5), dim3(kSmThreads), 0, r, job);
+  return 0;
+}
+
+int launch_smooth_store(LaunchCtx* P, const ModRows& r, const SmoothJob& job) {
+  if(job.ntiles <= 0) return 0;
+  LAUNCH("k_smooth_store", k_smooth_store, dim3(job.ntiles), dim3(kSmThreads), 0, r, job);
+  return 0;
 }
 
 int launch_phase_shift(LaunchCtx* P, const ModRows& r, const float* theta, int layer1_based) {
