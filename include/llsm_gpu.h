@@ -180,6 +180,9 @@ void llsm_gpu_sum_outputs(FP_TYPE* y, const FP_TYPE* y_sin, const FP_TYPE* y_noi
  * call), laid out as plane 9 around that call's centre lines: pair after pair in list order, each [na][2 band + 1] row-major,
  * entry q of row i column c_i - band + q with c_i = center[pos0 + i], +infinity where that column lies outside [p_i, q_i].
  * Refused until such a call has run; no other call writes it, and that call writes none of planes 6, 9, 12 and 13.
+ * which = 15: the noise excitation of the last llsm_gpu_batch_synthesize, [total_out] laid out as LLSM_GPU_YNOISE (utterance
+ * after utterance at the batch's output offsets): the signal the noise filter of that call read.  Refused until a synthesis
+ * has formed it; no other call writes it.
  * Each plane has its own length.  2 and 3 are refused (-1, with a message) until llsm_gpu_batch_analyze /
  * llsm_gpu_batch_synthesize has run the band filter on this batch.  The later stages of those calls only read the two
  * buffers and no other call writes them, so the planes stay valid until the next analyze / synthesize of the batch.
@@ -1179,7 +1182,16 @@ void llsm_gpu_set_default_seed(unsigned long long seed);
  * is a single low- or high-pass); 2 whether i samples run fused (i >= 4 M');
  * 3 the halo of a time segment; 4 the number of time segments; 5 and 6 the
  * range [lo, hi) the main job or its segments write ([M, i - M) when fused);
- * 100 + s the first sample segment s writes.  -1: no such quantity. */
+ * 100 + s the first sample segment s writes.
+ * 17 the kernel that filters the noise of an offline synthesis at hop thop
+ * and rate fs with PSD rows of j points, under the Hann convention in force:
+ * i != 0 the fused filter + overlap-add is wanted (the default), i == 0 it is
+ * not ($LLSM_GPU_NOISE_OLA=0).  100 + 10 ALIAS + TQ: k_noise_filter_ola<LOGN,
+ * ALIAS, TQ>; 1 k_noise_filter_wf<LOGN>; 2 k_noise_filter on the LDS; 3 on
+ * global scratch (the last three followed by k_ola_noise_mix).
+ * 18 frames per unit of the fused noise filter for an utterance of j frames
+ * in a batch of i frames, under $LLSM_GPU_NOISE_UNIT as it stands.
+ * -1: no such quantity. */
 int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE thop,
   FP_TYPE fs, FP_TYPE rel_winsize);
 

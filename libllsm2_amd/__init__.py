@@ -852,7 +852,8 @@ class Batch:
         of the last select_chain with this batch as the target; 12: the distance planes of the last align_slope with this
         batch as a, pair after pair, each na x nb; 13: the band planes of the last align_band_slope with this batch as a,
         laid out as plane 9; 14: the band planes of the last align_around with this batch as a, laid out as plane 9 around
-        that call's centre lines)"""
+        that call's centre lines; 15: the noise excitation of the last synthesize, total_out samples laid out as
+        A_YNOISE, what that call's noise filter read)"""
         n = self.L.llsm_gpu_batch_debug_plane(self.h, int(which), None, 0)
         if n < 0:
             raise LlsmError("debug_plane: " + self.L.llsm_gpu_last_error().decode())

@@ -155,7 +155,7 @@ struct llsm_gpu_batch {
   DevBuf<float> win_sin, win_psd, win_env, win_filt;
   DevBuf<FiltSectionD> sections; DevBuf<FiltJob> jobs_ana, jobs_syn;
   int njobs_ana = 0, njobs_syn = 0, nch_active = 0;
-  bool ce_filled = false, colored_filled = false;   // the band filter of analyze / synthesize has been launched on this batch (llsm_gpu_batch_debug_plane 2 / 3)
+  bool ce_filled = false, colored_filled = false, yexc_filled = false;   // the band filter of analyze / synthesize has been launched on this batch (llsm_gpu_batch_debug_plane 2 / 3); a synthesis has written yexc (plane 15)
   const void* key_ana[3] = {nullptr, nullptr, nullptr};   // scratch pointers the job tables embed
   const void* key_syn[3] = {nullptr, nullptr, nullptr};
   float inv_wpow = 0, norm_base = 0, norm_base_blackman = 0;

@@ -129,6 +129,7 @@ extern "C" int llsm_gpu_get_convention(const char* name) {
 #define NF_UNIT_DIV 2048
 #endif
 static int sin_unit_frames(long long F, int nf, int nwin, int maxnhar);
+static int nf_unit_frames(long long F, int nf);
 static int excite_unit_start(int ny, int S, int k);
 static int virtual_devices(void);
 static std::atomic<int> g_overlap([] { const char* e = std::getenv("LLSM_GPU_OVERLAP"); return (e && e[0] == '0') ? 0 : 1; }());
@@ -620,22 +621,24 @@ extern "C" int llsm_gpu_batch_set_fnyq(llsm_gpu_batch* b, FP_TYPE fnyq) {
 // successful llsm_gpu_batch_align_slope with this batch as a, pair after pair, each [na][nb]; only such a call writes it.
 // 13: the band planes of the last successful llsm_gpu_batch_align_band_slope with this batch as a, laid out as plane 9; only
 // such a call writes it.  14: the band planes of the last successful llsm_gpu_batch_align_around with this batch as a, laid
-// out as plane 9 around that call's centre lines; only such a call writes it.
+// out as plane 9 around that call's centre lines; only such a call writes it.  15: the noise excitation of the last
+// synthesis (yexc), [total_out], laid out as LLSM_GPU_YNOISE: what the noise filter of that call read; only
+// llsm_gpu_batch_synthesize writes it.
 // dst == NULL: only the size.  Returns the number of floats of the plane, -1 without one.
 extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, float* dst, long long cap) {
-  if(! b || which < 0 || which > 14) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
+  if(! b || which < 0 || which > 15) { llsm_set_error("llsm_gpu_batch_debug_plane: bad arguments"); return -1; }
   int mode = -1;                                                      // of the alignment call whose plane `which` is
   for(int m = 0; m < ALIGN_CALLS; m ++) if(kAlignCalls[m].plane == which) mode = m;
   DevBuf<float>& src = mode >= 0 ? b -> align[mode].plane :
                       which == 0 ? b -> env : which == 1 ? b -> psd_log : which == 2 ? b -> ce : which == 3 ? b -> colored :
                       which == 4 ? b -> f0_cmndf : which == 5 ? b -> f0_cand : which == 7 ? b -> sel_p7 : which == 8 ? b -> sel_p8 :
-                      which == 10 ? b -> selc_p10 : b -> selc_p11;
+                      which == 10 ? b -> selc_p10 : which == 15 ? b -> yexc : b -> selc_p11;
   const long long n = mode >= 0 ? b -> align[mode].cells :
                       which <= 1 ? (long long)b -> lay.total_frames * (b -> nfft_psd / 2 + 1) :
                       which == 2 ? (long long)b -> lay.nchannel * b -> lay.total_samples :
                       which == 3 ? (long long)b -> lay.n_utt * b -> lay.nchannel * b -> lay.ntemplate_ext :
                       which == 4 ? (long long)b -> lay.total_frames * b -> f0_cm_cols :
-                      which == 5 ? (long long)b -> lay.total_frames * 24 : which >= 10 ? b -> selc_frames * (which == 10 ? 32 : 256) :
+                      which == 5 ? (long long)b -> lay.total_frames * 24 : which == 15 ? (long long)b -> lay.total_out : which >= 10 ? b -> selc_frames * (which == 10 ? 32 : 256) :
                       b -> sel_frames * (which == 7 ? 16 : 64);
   if(which == 4 && b -> f0_cm_cols == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_estimate_f0 with keep_cmndf has run on this batch"); return -1; }
   if(which == 5 && ! b -> f0_cand_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_track_f0 has run on this batch"); return -1; }
@@ -644,6 +647,7 @@ extern "C" long long llsm_gpu_batch_debug_plane(llsm_gpu_batch* b, int which, fl
   if((which == 10 || which == 11) && b -> selc_frames == 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no llsm_gpu_batch_select_chain has run on this batch"); return -1; }
   if(which == 2 && ! b -> ce_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has filtered the bands of this batch"); return -1; }
   if(which == 3 && ! b -> colored_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no synthesis has filtered the templates of this batch"); return -1; }
+  if(which == 15 && ! b -> yexc_filled) { llsm_set_error("llsm_gpu_batch_debug_plane: no synthesis has formed the noise excitation of this batch"); return -1; }
   if(! src.p || n <= 0) { llsm_set_error("llsm_gpu_batch_debug_plane: no analysis has run on this batch"); return -1; }
   if(dst) {
     if(cap < n) { llsm_set_error("llsm_gpu_batch_debug_plane: destination too small"); return -1; }
@@ -1393,14 +1397,9 @@ static int synthesis_plan(llsm_gpu_batch* b, float fs) {
       // work units of k_noise_filter_ola: frames [i0, i1) of one utterance, i0 even; unit length so
       // that the batch gives about one unit per resident wavefront (2 / SIMD), never below 4 frames;
       // halo = frames before i0 whose N-sample output window still reaches sample start(i0)
-      const long long Ftot = b -> lay.total_frames;
-      int C = (int)((Ftot + NF_UNIT_DIV - 1) / NF_UNIT_DIV);
-      C = std::max(4, (C + 1) & ~1);
-      if(const char* e = std::getenv("LLSM_GPU_NOISE_UNIT")) C = std::max(2, std::atoi(e) & ~1);   // tuning override
       std::vector<int4> units;
       for(int u = 0; u < b -> lay.n_utt; u ++) {
-        const int nf = b -> nfrm[u], nu = (nf + C - 1) / C;   // equal (even-sized) units within the utterance
-        const int sz = nu > 0 ? (((nf + nu - 1) / nu) + 1) & ~1 : 2;
+        const int nf = b -> nfrm[u], sz = nf_unit_frames(b -> lay.total_frames, nf);
         for(int i0 = 0; i0 < nf; i0 += sz) units.push_back(make_int4(u, i0, std::min(i0 + sz, nf), 0));
       }
       b -> n_nf_units = (int)units.size();
@@ -1503,10 +1502,12 @@ extern "C" int llsm_gpu_batch_synthesize(llsm_gpu_batch* b, const llsm_soptions*
   RUN(launch_excite_env(P, d, b -> colored.p, L.ntemplate_ext, b -> env_hits.p, by_units ? nullptr : b -> env_cplx.p,
     b -> nwin_env, b -> win_env.p, b -> nch_active, b -> d_y_off.p, b -> d_ny.p, b -> max_ny, fs,
     b -> yexc.p, b -> exu_units.p, b -> n_exu_units));
+  b -> yexc_filled = true;
   // b -> fnyq: the PSD rows' axis (conf FNYQ; analysis fs / 2, layer0.c:481).  Transforms up to 2048 points: filter and overlap-add
   // in one kernel (the shaped frames stay on chip); larger ones: frames to HBM, gathered by the mix (noise_unfused).
   float *ysin = (float*)b -> arr[LLSM_GPU_YSIN], *ynoise = (float*)b -> arr[LLSM_GPU_YNOISE], *yout = (float*)b -> arr[LLSM_GPU_Y];
-  static const bool fused_ok = [] { const char* e = std::getenv("LLSM_GPU_NOISE_OLA"); return !(e && e[0] == '0'); }();
+  const char* eo = std::getenv("LLSM_GPU_NOISE_OLA");   // (read per call: tests switch it)
+  const bool fused_ok = !(eo && eo[0] == '0');
   bool have_fused_kernel = false;
   if(fused_ok) {
     const int rc = launch_noise_filter_ola(P, d, b -> nf_units.p, b -> n_nf_units, b -> nf_halo, b -> yexc.p,
@@ -1593,6 +1594,17 @@ static int excite_unit_start(int ny, int S, int k) {
   return k >= 0 && s0 < ny ? (int)s0 : -1;
 }
 
+// frames per unit of k_noise_filter_ola for an utterance of nf frames in a batch of F frames: about one unit per resident
+// wavefront (2 / SIMD) over the batch, never below 4 frames ($LLSM_GPU_NOISE_UNIT overrides, from 2 up), equal even-sized
+// units within the utterance.  llsm_gpu_plan_index case 18 exports it.
+static int nf_unit_frames(long long F, int nf) {
+  int C = (int)((F + NF_UNIT_DIV - 1) / NF_UNIT_DIV);
+  C = std::max(4, (C + 1) & ~1);
+  if(const char* e = std::getenv("LLSM_GPU_NOISE_UNIT")) C = std::max(2, std::atoi(e) & ~1);   // tuning override
+  const int nu = (nf + C - 1) / C;
+  return nu > 0 ? (((nf + nu - 1) / nu) + 1) & ~1 : 2;
+}
+
 // frames per unit of k_synth_ola for an utterance of nf frames in a batch of F frames (about 8 wavefronts / SIMD over
 // the batch, never below 4 frames).  llsm_gpu_plan_index case 14 exports it.
 static int sin_unit_frames(long long F, int nf, int nwin, int maxnhar) {
@@ -1627,6 +1639,11 @@ extern "C" int llsm_gpu_plan_index(int which, int i, int j, FP_TYPE f0, FP_TYPE 
     case 14: return sin_unit_frames(i, i, lp::nwin_sin(thop, fs), j);
     case 15: return excite_unit_start(i, excite_unit_samples(), j);
     case 16: return filt_plan_query(i, j, f0, thop, fs);
+    case 18: return nf_unit_frames(i, j);
+    case 17: {                                         // the noise filter's route at this hop and rate (kernels.h NF_ROUTE_*)
+      const int nwin = lp::nwin_filt(thop, fs);
+      return noise_filter_route(ilog2(lp::nextpow2(nwin * 1.2 + 32)), j, hann_sym(nwin), i != 0);
+    }
   }
   return -1;
 }

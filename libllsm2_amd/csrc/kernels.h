@@ -152,6 +152,12 @@ int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int
   const int4* units = nullptr, int nunits = 0);
 bool excite_units_ok(const BatchDev& d, int nwin_env, float fs_syn);   // the geometry k_excite_units takes
 int excite_unit_samples();                            // output samples per unit of k_excite_units
+// Which kernel filters the noise of a 2^logN-point transform with target rows of npsd points (llsm_gpu_plan_index case 17;
+// both launchers below decide by it, so the value is the kernel that runs).  fused: the caller wants filter and overlap-add
+// in one kernel.  Fused: 100 + 10 ALIAS + TQ of k_noise_filter_ola<LOGN, ALIAS, TQ>; otherwise -- fused not wanted, or no
+// fused instantiation at this size -- k_noise_filter_wf<LOGN>, or k_noise_filter on the LDS or on global scratch.
+enum { NF_ROUTE_WF = 1, NF_ROUTE_LDS = 2, NF_ROUTE_SCRATCH = 3, NF_ROUTE_FUSED = 100 };
+int noise_filter_route(int logN, int npsd, int wsym, bool fused);
 int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
   const int* out_off, const int* out_len, float fnyq_conf, float fs_syn, int nwin,
   const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax,

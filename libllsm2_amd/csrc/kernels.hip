@@ -2657,6 +2657,16 @@ DEV float block_max(float v, float* red, int tid) {
   return m;
 }
 
+// Two frames share one inverse transform (Ya + j Yb), whose float32 rounding error is that of the LOUDER one, spread over
+// all N samples of both: next to a frame 60 dB up, a frame is off by 1000 x 2^-24 of its own level over the hop its
+// partner does not reach (tests/test_gpu_noise_filter.py measured 824).  So each frame's gain carries 2^-nf_level_exp(peak
+// of its PSD row: the level up to what its PSDRES row adds, which the exponent leaves aside -- a few dB, and only the
+// conditioning depends on it): both spectra enter the transform at the order of 1, and the factor comes off
+// with the 1 / N behind it.  Powers of two: a frame's own arithmetic is unchanged, and a pair at equal exponents keeps its bits.
+DEV int nf_level_exp(float pk_db) {
+  return __builtin_amdgcn_readfirstlane((int)rintf(fminf(fmaxf(pk_db, -400.0f), 400.0f) * 0.16609640f));   // log2(10) / 20
+}
+
 // One frame pair (gg[0], gg[1] >= nframes: absent) by NT threads; X / tw / P: LDS (N, N/2, N/2 + 1 float2), red: NT / 64 floats.
 // Every thread of the workgroup must call it (barriers inside).
 // lds_frames != NULL (rt): frame e of the pair is lds_frames + e * nwin instead of yexc + g * nwin.
@@ -2678,8 +2688,8 @@ DEV int noise_filter_pair(const int (&gg)[2], int tid, float2* X, const float2* 
   const int nspec = N / 2 + 1;
   const int nfade = 16;
   const float fn_syn = fs / 2.0f;
-  const float invN = 1.0f / (float)N;
   bool alive[2]; const float* xs[2]; int nxu[2], base[2];
+  int lev[2] = {0, 0};                               // nf_level_exp of the frames of an offline synthesis (llsmrt: 0)
 #pragma unroll
   for(int e = 0; e < 2; e ++) {
     const int g = gg[e];
@@ -2701,6 +2711,7 @@ DEV int noise_filter_pair(const int (&gg)[2], int tid, float2* X, const float2* 
     if(! pk_ready) pk = block_max<NT>(pk, red, tid);   // (uniform control flow: every thread gets here)
     if(g >= nframes) continue;
     alive[e] = !(pk < -100.0f);
+    if(alive[e] && nframes_out && ! rt) lev[e] = nf_level_exp(pk);   // (llsmrt keeps its bits in all its launch modes)
     if(lane == 0 && nframes_out) live[g] = alive[e] ? 1 : 0;
     if(rt) { xs[e] = lds_frames ? lds_frames + (size_t)e * nwin : yexc + (size_t)g * nwin; nxu[e] = nwin; base[e] = 0; }
     else {
@@ -2773,8 +2784,8 @@ DEV int noise_filter_pair(const int (&gg)[2], int tid, float2* X, const float2* 
       } else {
         ta = target_db(prow0, rrow0, hr0, npsd, fq, fnyq_conf); tb = target_db(prow1, rrow1, hr1, npsd, fq, fnyq_conf);
       }
-      const float Ha = expf(ta * (2.3025851f / 20.0f)) / sqrtf(ea * 44100.0f / fs + 1e-8f);
-      const float Hb = expf(tb * (2.3025851f / 20.0f)) / sqrtf(eb * 44100.0f / fs + 1e-8f);
+      const float Ha = ldexpf(expf(ta * (2.3025851f / 20.0f)) / sqrtf(ea * 44100.0f / fs + 1e-8f), -lev[0]);
+      const float Hb = ldexpf(expf(tb * (2.3025851f / 20.0f)) / sqrtf(eb * 44100.0f / fs + 1e-8f), -lev[1]);
       unpack_pair(X, N, logN, k, & A, & B);
       A.x *= Ha; A.y *= Ha; B.x *= Hb; B.y *= Hb;
       if(k == 0) { A.y = 0; B.y = 0; }              // real signals: DC bin is real
@@ -2797,7 +2808,7 @@ DEV int noise_filter_pair(const int (&gg)[2], int tid, float2* X, const float2* 
     if(! alive[e]) continue;
     float* out = nframes_out + (size_t)gg[e] * N;
     for(int t = lane; t < N; t += NT) {
-      float v = (e == 0 ? X[t].x : X[t].y) * invN;
+      float v = ldexpf(e == 0 ? X[t].x : X[t].y, lev[e] - logN);   // x 2^lev / N
       if(t < nfade) v *= (float)t / (float)nfade;
       if(t >= N - nfade) v *= 1.0f - (float)(N - 1 - t) / (float)nfade;
       out[t] = v;
@@ -2865,7 +2876,6 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : NF_WPE)) void k_noise_filte
   WfTw<LOGN> tw; wf_init(tw, lane);
   const int nfade = 16;
   const float fn_syn = fs / 2.0f;
-  const float invN = 1.0f / (float)N;
   // the analysis window is the same for every frame pair this wavefront walks: load it once
   const int shift = N / 2 - nwin / 2;                // x_re[j - nwin/2 + nfft/2]
   float* Wl = (float*)(Tdb + npsd);                  // ... and kept in LDS (16 registers fewer: no spills)
@@ -2927,6 +2937,7 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : NF_WPE)) void k_noise_filte
     const bool alive[2] = {!(pk0 < -100.0f), cur.valid[1] && !(pk1 < -100.0f)};
     if(lane == 0) { live[gg[0]] = alive[0] ? 1 : 0; if(cur.valid[1]) live[gg[1]] = alive[1] ? 1 : 0; }
     if(! alive[0] && ! alive[1]) { __syncthreads(); continue; }
+    const int lev[2] = {alive[0] && ! rt ? nf_level_exp(pk0) : 0, alive[1] && ! rt ? nf_level_exp(pk1) : 0};   // (llsmrt keeps its bits)
 #pragma unroll
     for(int m = 0; m < P; m ++) {
       const float w = Wl[lane + WAVE * m];
@@ -2977,8 +2988,8 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : NF_WPE)) void k_noise_filte
       }
       // 10^(t/20) / sqrt(e 44100/fs + 1e-8): hardware exp2 / rsq (1 ulp), the argument scaling
       // costs |t| 7e-9 relative -- inside the stated 1e-4 synthesis tolerance by three orders
-      const float ha = __expf(ta * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(ea, esc, 1e-8f));
-      const float hb = __expf(tb * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(eb, esc, 1e-8f));
+      const float ha = ldexpf(__expf(ta * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(ea, esc, 1e-8f)), -lev[0]);
+      const float hb = ldexpf(__expf(tb * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(eb, esc, 1e-8f)), -lev[1]);
       float ar = xr[m] * ha, ai = xi[m] * ha, br = mr[m] * hb, bi = mi[m] * hb;
       if(m == 0 && lane == 0) { ai = 0.0f; bi = 0.0f; }           // real signals: DC bin is real
       if(m == H - 1) { nyq_r = __shfl(ar, WAVE - 1, WAVE); nyq_i = __shfl(br, WAVE - 1, WAVE); }
@@ -2998,7 +3009,7 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : NF_WPE)) void k_noise_filte
 #pragma unroll
       for(int m = 0; m < P; m ++) {
         const int t = lane + WAVE * m;
-        float v = (e == 0 ? xr[m] : xi[m]) * invN;
+        float v = ldexpf(e == 0 ? xr[m] : xi[m], lev[e] - LOGN);   // x 2^lev / N
         if(m == 0 && t < nfade) v *= (float)t / (float)nfade;
         if(m == P - 1 && t >= N - nfade) v *= 1.0f - (float)(N - 1 - t) / (float)nfade;
         out[t] = v;
@@ -3034,7 +3045,8 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : NF_WPE)) void k_noise_filte
 template <int LOGN, int MH>                          // MH = 3: the 7-tap smoother (default convention); 0: general (mavg_h <= 3)
 DEV void nf_gain_loop(float (&xr)[(1 << LOGN) / WAVE], float (&xi)[(1 << LOGN) / WAVE],
   float (&mr)[(1 << LOGN) / WAVE / 2 + 1], float (&mi)[(1 << LOGN) / WAVE / 2 + 1],
-  const float2* Pw, const float2* Tdb, int npsd, float cpos, float esc, int mavg_h, int lane, float& nyq_r, float& nyq_i) {
+  const float2* Pw, const float2* Tdb, int npsd, float cpos, float esc, int mavg_h, int lane, float& nyq_r, float& nyq_i,
+  int leva, int levb) {                              // nf_level_exp of the two frames
   constexpr int N = 1 << LOGN, P = N / WAVE, H = P / 2, nspec = N / 2 + 1;
   int lv = lane;                                     // opaque per pair: the per-bin grid positions and
   asm volatile("" : "+v"(lv));                       // weights are recomputed, not hoisted (and spilled)
@@ -3070,8 +3082,8 @@ DEV void nf_gain_loop(float (&xr)[(1 << LOGN) / WAVE], float (&xi)[(1 << LOGN) /
     }
     // 10^(t/20) / sqrt(e 44100/fs + 1e-8): hardware exp2 / rsq (1 ulp), the argument scaling
     // costs |t| 7e-9 relative -- inside the stated 1e-4 synthesis tolerance by three orders
-    const float ha = __expf(ta * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(ea, esc, 1e-8f));
-    const float hb = __expf(tb * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(eb, esc, 1e-8f));
+    const float ha = ldexpf(__expf(ta * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(ea, esc, 1e-8f)), -leva);
+    const float hb = ldexpf(__expf(tb * (2.3025851f / 20.0f)) * __frsqrt_rn(fmaf(eb, esc, 1e-8f)), -levb);
     float ar = xr[m] * ha, ai = xi[m] * ha, br = mr[m] * hb, bi = mi[m] * hb;
     if(m == 0 && lane == 0) { ai = 0.0f; bi = 0.0f; }           // real signals: DC bin is real
     if(m == H - 1) { nyq_r = __shfl(ar, WAVE - 1, WAVE); nyq_i = __shfl(br, WAVE - 1, WAVE); }
@@ -3101,7 +3113,6 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : (ALIAS ? NF_OLA_WPE : NF_WP
   WfTw<LOGN> tw; wf_init(tw, lane);
   const int nfade = 16;
   const float fn_syn = fs / 2.0f;
-  const float invN = 1.0f / (float)N;
   const int shift = N / 2 - nwin / 2;                // x_re[j - nwin/2 + nfft/2]
   // analysis window, sample lane + 64 m of the padded frame.  Two wavefronts per SIMD: in registers.  ALIAS (three): its
   // first half in LDS behind the ring -- win[j] == win[wsym - j] exactly (engine.cpp make_hann mirrors the table) --, 1 KB
@@ -3227,6 +3238,7 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : (ALIAS ? NF_OLA_WPE : NF_WP
     pk0 = wave_max(pk0); pk1 = wave_max(pk1);
     const bool alive[2] = {!(pk0 < -100.0f), valid1 && !(pk1 < -100.0f)};
     if(! alive[0] && ! alive[1]) { stage(j + 2, hr_nxt); continue; }
+    const int lev[2] = {alive[0] ? nf_level_exp(pk0) : 0, alive[1] ? nf_level_exp(pk1) : 0};
     {
       int js = lane - shift;                         // opaque: the table positions are recomputed per pair, not kept
       asm volatile("" : "+v"(js));
@@ -3260,8 +3272,8 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : (ALIAS ? NF_OLA_WPE : NF_WP
     __syncthreads();
     float nyq_r = 0.0f, nyq_i = 0.0f;
 #if !(NF_ABL & 4)
-    if(mavg_h == 3) nf_gain_loop<LOGN, 3>(xr, xi, mr, mi, Pw, Tdb, npsd, cpos, esc, mavg_h, lane, nyq_r, nyq_i);
-    else nf_gain_loop<LOGN, 0>(xr, xi, mr, mi, Pw, Tdb, npsd, cpos, esc, mavg_h, lane, nyq_r, nyq_i);
+    if(mavg_h == 3) nf_gain_loop<LOGN, 3>(xr, xi, mr, mi, Pw, Tdb, npsd, cpos, esc, mavg_h, lane, nyq_r, nyq_i, lev[0], lev[1]);
+    else nf_gain_loop<LOGN, 0>(xr, xi, mr, mi, Pw, Tdb, npsd, cpos, esc, mavg_h, lane, nyq_r, nyq_i, lev[0], lev[1]);
 #endif
     __syncthreads();
     if(lane == 0) { xr[H] = nyq_r; xi[H] = nyq_i; }
@@ -3292,7 +3304,7 @@ __global__ __launch_bounds__(WAVE, (LOGN >= 11 ? 1 : (ALIAS ? NF_OLA_WPE : NF_WP
 #pragma unroll
       for(int m = 0; m < P; m ++) {
         const int t = lo_ + WAVE * m;
-        float v = (e == 0 ? xr[m] : xi[m]) * invN;
+        float v = ldexpf(e == 0 ? xr[m] : xi[m], lev[e] - LOGN);   // x 2^lev / N
         if(m == 0 && t < nfade) v *= (float)t / (float)nfade;
         if(m == P - 1 && t >= N - nfade) v *= 1.0f - (float)(N - 1 - t) / (float)nfade;
         acc[m] += v;
@@ -4319,6 +4331,20 @@ int launch_excite_env(LaunchCtx* P, const BatchDev& d, const float* colored, int
   });
 }
 
+// The route of the noise filter (kernels.h NF_ROUTE_*): the one decision both launchers below follow.
+int noise_filter_route(int logN, int npsd, int wsym, bool fused) {
+  const int wf = with_wf(logN, 0, [&](auto ln) {
+    constexpr int LN = ln;
+    if(! fused) return (int)NF_ROUTE_WF;
+    // target rows inside the exchange buffer when they fit there and in NF_TQ registers per lane
+    if(wsym > 0 && npsd <= NF_TQ * WAVE && (1 << (LN - 1)) + 7 + npsd <= wf_lds_elems<LN>())
+      return NF_ROUTE_FUSED + 10 + (npsd <= 2 * WAVE ? 2 : NF_TQ);
+    return NF_ROUTE_FUSED + 1;
+  });
+  if(wf) return wf;                                   // 4096 and up: the LDS kernel (register budget)
+  return (1 << logN) > LLSM_LDS_FFT_MAX ? NF_ROUTE_SCRATCH : NF_ROUTE_LDS;
+}
+
 int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
   const int* out_off, const int* out_len, float fnyq_conf, float fs_syn, int nwin,
   const float* win, float inv_wsqr, int N, int logN, const float2* tw, int tw_nmax,
@@ -4326,13 +4352,13 @@ int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
   if(d.nframes == 0) return 0;
   const int np = rt ? (d.nframes + 1) / 2 : npairs_of(d);
   const auto pairs = rt ? nullptr : d.pairs;
-  const int rc = with_wf(logN, NO_WF, [&](auto ln) {         // 4096 and up: the LDS kernel (register budget)
+  const int route = noise_filter_route(logN, d.npsd, 0, false);
+  if(route == NF_ROUTE_WF) return with_wf(logN, -1, [&](auto ln) {
     LAUNCH("k_noise_filter_wf", (k_noise_filter_wf<ln>), dim3(fft_grid(np) * (NF_WPE / 2)), dim3(WAVE),
       sizeof(float2) * (wf_lds_elems<ln>() + d.npsd) + (sizeof(float) << ln), yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes,
       d.psd, d.psdres, d.has_psdres, d.npsd, fnyq_conf, d.thop, fs_syn, nwin, win, inv_wsqr, nframes_out, live, rt, pairs, np);
     return 0;
   });
-  if(rc != NO_WF) return rc;
   auto lds_form = [&](int grid, size_t lds, const float2* t, int t_nmax, float2* scratch) {
     LAUNCH("k_noise_filter", k_noise_filter, dim3(grid), dim3(WAVE), lds,
       yexc, out_off, out_len, d.frm_utt, d.frm_off, d.nframes, d.psd, d.psdres, d.has_psdres,
@@ -4340,7 +4366,7 @@ int launch_noise_filter(LaunchCtx* P, const BatchDev& d, const float* yexc,
       nframes_out, live, rt, pairs, np, scratch);
     return 0;
   };
-  if(N > LLSM_LDS_FFT_MAX) {                          // beyond the LDS: global scratch + the big twiddle table (engine.cpp)
+  if(route == NF_ROUTE_SCRATCH) {                     // beyond the LDS: global scratch + the big twiddle table (engine.cpp)
     const int grid = std::min(fft_grid(np), llsm_big_fft_grid((size_t)N + N / 2 + 1));
     if(! P -> tw_big || N > P -> tw_big_nmax || P -> big_scratch_elems < (size_t)grid * (N + N / 2 + 1)) return -1;
     return lds_form(grid, 64, P -> tw_big, P -> tw_big_nmax, P -> big_scratch);
@@ -4356,6 +4382,8 @@ int launch_noise_filter_ola(LaunchCtx* P, const BatchDev& d, const int4* units, 
   const float* yexc, const int* out_off, const int* out_len, float fnyq_conf, float fs_syn, int nwin,
   const float* win, int wsym, float inv_wsqr, int logN, float* ynoise) {
   if(nunits == 0) return 0;
+  const int route = noise_filter_route(logN, d.npsd, wsym, true);
+  if(route < NF_ROUTE_FUSED) return -2;
   return with_wf(logN, -2, [&](auto ln) {
     constexpr int LN = ln;
     auto go = [&](auto alias, auto tq, size_t lds) {
@@ -4365,10 +4393,10 @@ int launch_noise_filter_ola(LaunchCtx* P, const BatchDev& d, const int4* units, 
       return 0;
     };
     const size_t lds = sizeof(float2) * wf_lds_elems<LN>() + (sizeof(float) << LN);
-    // target rows inside the exchange buffer when they fit there and in NF_TQ registers per lane
-    if(wsym > 0 && d.npsd <= NF_TQ * WAVE && (1 << (LN - 1)) + 7 + d.npsd <= wf_lds_elems<LN>()) {
-      const size_t lds_alias = lds + sizeof(float) * (wsym / 2 + 1);
-      return d.npsd <= 2 * WAVE ? go(std::true_type{}, int_c<2>{}, lds_alias) : go(std::true_type{}, int_c<NF_TQ>{}, lds_alias);
+    const size_t lds_alias = lds + sizeof(float) * (wsym / 2 + 1);
+    switch(route) {
+      case NF_ROUTE_FUSED + 12: return go(std::true_type{}, int_c<2>{}, lds_alias);
+      case NF_ROUTE_FUSED + 10 + NF_TQ: return go(std::true_type{}, int_c<NF_TQ>{}, lds_alias);
     }
     return go(std::false_type{}, int_c<1>{}, lds + sizeof(float2) * d.npsd);
   });

@@ -573,8 +573,10 @@ static void synthesize_noise_excitation(const o_soptions* opt, const o_params* p
   free(xn); free(env);
 }
 
-/* layer0.c:557-634 */
-static void filter_noise(const o_params* p, fp fs, const fp* x, int nx, fp* y) {
+/* layer0.c:557-634.  has_psdres: per frame, whether its PSDRES row is added back (NULL: p -> psdres decides for every
+ * frame, as the reference's container does).  frame_rms (may be NULL): per frame the RMS over the nfft samples of the
+ * frame as it is overlap-added (after the inverse transform's 1 / nfft and the fades), 0 for a frame the -100 dB gate drops */
+void o_filter_noise(const o_params* p, fp fs, const fp* x, int nx, const int* has_psdres, fp* y, fp* frame_rms) {
   const int nfade = 16;
   float thop = (float)p -> thop;
   int nwin = o_idx_nwin_filt(thop, (float)fs);
@@ -599,6 +601,7 @@ static void filter_noise(const o_params* p, fp fs, const fp* x, int nx, fp* y) {
     const fp* npsdv = p -> psd + (size_t)i * npsd;
     fp peak = npsdv[0];
     for(int j = 1; j < npsd; j ++) if(npsdv[j] > peak) peak = npsdv[j];
+    if(frame_rms) frame_rms[i] = 0;
     if(peak < -100) continue;
     int center = o_idx_center(i, thop, (float)fs);
     o_fetch_frame(x, nx, center, nwin, xfrm);
@@ -608,7 +611,7 @@ static void filter_noise(const o_params* p, fp fs, const fp* x, int nx, fp* y) {
     for(int j = 0; j < nspec; j ++) psd[j] = (x_re[j] * x_re[j] + x_im[j] * x_im[j]) / wsqr;
     o_moving_avg(psd, nspec, o_conv_mavg_half(), envs);
     for(int j = 0; j < npsd; j ++) src_psd[j] = npsdv[j];
-    if(p -> psdres)
+    if(p -> psdres && (! has_psdres || has_psdres[i]))
       for(int j = 0; j < npsd; j ++)
         src_psd[j] += (fp)(p -> psdres[(size_t)i * npsd + j] - LOG2IN(LOGRESBIAS));
     o_spectrum_from_envelope(src_axis, src_psd, npsd, nspec - 1, (fp)(fs / 2.0), H);
@@ -626,6 +629,11 @@ static void filter_noise(const o_params* p, fp fs, const fp* x, int nx, fp* y) {
       x_re[j] *= (fp)j / nfade;
       x_re[nfft - j - 1] *= (fp)(1.0 - (fp)j / nfade);
     }
+    if(frame_rms) {
+      fp e = 0;
+      for(int j = 0; j < nfft; j ++) e += x_re[j] * x_re[j];
+      frame_rms[i] = (fp)sqrt((double)(e / nfft));
+    }
     for(int j = 0; j < nfft; j ++) {
       int idx = center + j - nfft / 2;
       if(idx >= 0 && idx < nx) y[idx] += x_re[j];
@@ -633,6 +641,11 @@ static void filter_noise(const o_params* p, fp fs, const fp* x, int nx, fp* y) {
   }
   free(w); free(psd); free(envs); free(H); free(x_re); free(x_im);
   free(xfrm); free(src_axis); free(src_psd);
+}
+
+/* the noise excitation of o_synthesize on its own (tests/noise_filter_reference.py) */
+void o_noise_excitation(const o_soptions* opt, const o_params* p, int ny, unsigned long long seed, const fp* white, fp* y) {
+  synthesize_noise_excitation(opt, p, opt -> fs, ny, seed, white, y);
 }
 
 /* layer0.c:636-664 (use_l1 == 0 path) */
@@ -643,7 +656,7 @@ int o_synthesize(const o_soptions* opt, const o_params* p,
   synthesize_harmonics_l0(opt, p, fs, ny, y_sin);
   fp* y_exc = malloc(sizeof(fp) * ny);
   synthesize_noise_excitation(opt, p, fs, ny, seed, white, y_exc);
-  filter_noise(p, fs, y_exc, ny, y_noise);
+  o_filter_noise(p, fs, y_exc, ny, NULL, y_noise, NULL);
   for(int i = 0; i < ny; i ++) y[i] = y_sin[i] + y_noise[i];
   free(y_exc);
   return ny;
@@ -659,7 +672,7 @@ int o_synthesize_l1(const o_soptions* opt, o_params* p, o_l1params* q, int maxnh
   o_synthesize_harmonics_l1(opt, p, q, maxnhar_conf, effect, effect_info, y_sin, ny);
   fp* y_exc = malloc(sizeof(fp) * ny);
   synthesize_noise_excitation(opt, p, fs, ny, seed, white, y_exc);
-  filter_noise(p, fs, y_exc, ny, y_noise);
+  o_filter_noise(p, fs, y_exc, ny, NULL, y_noise, NULL);
   for(int i = 0; i < ny; i ++) y[i] = y_sin[i] + y_noise[i];
   free(y_exc);
   return ny;

@@ -153,6 +153,9 @@ int o_analyze(const o_aoptions* opt, const fp* x, int nx, fp fs, fp* f0,
  * [nchannel][min(20000,ny)+128] injected Gaussian templates, else seeded RNG. */
 int o_synthesize(const o_soptions* opt, const o_params* p,
   unsigned long long seed, const fp* white, fp* y, fp* y_sin, fp* y_noise);
+/* the two stages of the noise part on their own: o_synthesize calls both */
+void o_noise_excitation(const o_soptions* opt, const o_params* p, int ny, unsigned long long seed, const fp* white, fp* y);
+void o_filter_noise(const o_params* p, fp fs, const fp* x, int nx, const int* has_psdres, fp* y, fp* frame_rms);
 void o_chunk_phasepropagate(o_params* p, int sign);
 void o_chunk_phasesync_rps(o_params* p);
 

@@ -337,6 +337,27 @@ class Oracle:
         self.lib.o_set_czt_mode(C.c_int(0))
         return y, ys, yn
 
+    def noise_excitation(self, sopt, pr, seed=0, white=None):
+        """the noise excitation of synthesize() on its own (o_noise_excitation), ny samples"""
+        cp = self.cparams(pr)
+        ny = self.ny(pr.nfrm, pr.thop, float(sopt.fs))
+        y = np.zeros(ny, self.dtype)
+        w = self.arr(white) if white is not None else None
+        self.lib.o_noise_excitation(C.byref(sopt), C.byref(cp), C.c_int(ny), C.c_ulonglong(seed), self.p(w), self.p(y))
+        return y
+
+    def filter_noise(self, pr, fs, x, has_psdres=None):
+        """the noise filter of synthesize() on the excitation x (o_filter_noise) -> (y_noise, frame_rms[nfrm]);
+        has_psdres: per-frame flags, None = every frame adds its PSDRES row"""
+        cp = self.cparams(pr)
+        x = self.arr(x)
+        y = np.zeros(len(x), self.dtype); rms = np.zeros(pr.nfrm, self.dtype)
+        h = None if has_psdres is None else np.ascontiguousarray(has_psdres, np.int32)
+        assert h is None or len(h) == pr.nfrm
+        self.lib.o_filter_noise(C.byref(cp), self.f(fs), self.p(x), C.c_int(len(x)),
+                                self.pi(h) if h is not None else None, self.p(y), self.p(rms))
+        return y, rms
+
     def phasepropagate(self, pr, sign):
         cp = self.cparams(pr); self.lib.o_chunk_phasepropagate(C.byref(cp), C.c_int(sign))
 
