@@ -731,9 +731,10 @@ int  llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo, int* hi);
  * and nothing else, which holds them to takes recorded against a click -- two freely spoken renditions of five minutes
  * drift apart by seconds, and the band that holds the drift passes the cap or costs what the whole matrix would.  Here the
  * caller gives the column c_i around which row i is searched, so that alignment can go from coarse to fine: align a
- * decimated copy of the pair with llsm_gpu_batch_align_slope (every 16th vector of LLSM_GPU_CODE uploaded to a small batch,
- * or llsm_gpu_batch_retime + llsm_gpu_batch_encode), turn its pos into a line with llsm_gpu_align_center_line, and search the
- * fine pair within a few times the decimation of it.  center is a host array of sum_p na(p) columns, pair after pair in
+ * coarse copy of the pair with llsm_gpu_batch_align_slope (the pooled vectors of llsm_gpu_batch_pool_code uploaded to a small
+ * batch, or llsm_gpu_batch_retime + llsm_gpu_batch_encode), turn its pos into a line with llsm_gpu_align_center_line, and
+ * search the fine pair within a few times the pooling factor of it.  llsm_gpu_batch_align_pyramid below runs exactly these
+ * steps in one call, with the pooled vectors kept on the device, and picks a connected band itself.  center is a host array of sum_p na(p) columns, pair after pair in
  * list order (the layout of pos); band one half-width per pair; slope chooses the moves: 0 those of
  * llsm_gpu_batch_align_band, 1 those of llsm_gpu_batch_align_band_slope.  The contract is that of llsm_gpu_batch_align_band --
  * the same pos and cost, the same options and llsm_gpu_align_check, synchronous, a refused call returns -1 with a message that
@@ -790,7 +791,8 @@ int  llsm_gpu_align_band_slope_rows(int na, int nb, int band, int* lo, int* hi);
  * in the words of llsm_gpu_batch_align_slope, (6) a line that is not valid (the message names the pair, the row and the
  * value), (7) a band that is not connected (the message names the pair and llsm_gpu_align_around_min of it), and (8) a sum of
  * na x (2 band + 1) above 2^28 cells (the message names the total).  n_pairs == 0 returns 0.
- * Known limits: one wavefront walks a pair; the coarse pass is the caller's -- no call runs both; under a line that climbs
+ * Known limits: one wavefront walks a pair; the coarse pass is the caller's here -- llsm_gpu_batch_align_pyramid below runs
+ * both; under a line that climbs
  * by whole bands per row the distance tiles of a strip of 64 rows cover far more cells than the band holds. */
 int  llsm_gpu_batch_align_around(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
        const int* center /* sum_p na(p) columns, pair after pair in list order: the layout of pos */,
@@ -800,6 +802,75 @@ int  llsm_gpu_batch_align_around(llsm_gpu_batch* a, const llsm_gpu_batch* b, int
 int  llsm_gpu_align_around_rows(int na, int nb, const int* center, int band, int slope, int* lo, int* hi);  /* host only */
 int  llsm_gpu_align_around_min(int na, int nb, const int* center, int slope);                               /* host only */
 int  llsm_gpu_align_center_line(int na_c, int nb_c, const FP_TYPE* pos_c, int na, int nb, int* center);     /* host only */
+
+/* ---- pooled coder vectors: the mean of every `factor` consecutive rows of LLSM_GPU_CODE of an utterance, computed on the
+ * device -- the input of a coarse alignment.  A mean and not every factor-th row: a decimated track aliases (a plosive of
+ * two frames is there or not by the phase of the grid), the mean of a group is a low-pass before the decimation and sees
+ * every frame.
+ *  P1. For an utterance of n frames and a factor f in [1, 64] there are nc = (n + f - 1) / f coarse frames
+ *      (llsm_gpu_pool_frames: nc, or -1 with a message for nfrm < 1 or a factor outside the range; host only).  Coarse frame k
+ *      pools the frames j = k f ... min(n, (k + 1) f) - 1, m of them -- the last group of an utterance may be short.  For
+ *      every column c of LLSM_GPU_CODE, the voicing column 0 included: s = 0.0f; for j ascending: s = s + CODE[j][c];
+ *      out[k][c] = s / (float)m.  float32, one rounding per operation, the division correctly rounded; the order of the
+ *      additions is part of the rule.  Pooled column 0 is the voiced share of the group, which rule D1's > 0.5f reads as a
+ *      majority vote.  factor == 1 copies the rows, except that -0.0f becomes +0.0f.  A NaN or an infinity in a group
+ *      spreads to its mean in that column and no further.
+ * llsm_gpu_batch_pool_code pools the n utterances named in utts (repeats allowed, any order) and writes them to the host
+ * array dst one after another in list order, each [nc][dim] row-major.  Synchronous.  It reads LLSM_GPU_CODE and writes no
+ * array and no scratch of the batch.  Refused with -1, a message that starts with "llsm_gpu_batch_pool_code:", nothing
+ * launched and dst untouched: a NULL batch; a coder that is not enabled; a factor outside [1, 64]; n < 0; with n > 0 a NULL
+ * list or dst, an index outside the batch, an utterance without frames, and a total above 2^28 coarse frames.  n == 0
+ * returns 0. */
+int  llsm_gpu_pool_frames(int nfrm, int factor);                       /* host only */
+int  llsm_gpu_batch_pool_code(const llsm_gpu_batch* b, int factor, int n, const int* utts, FP_TYPE* dst);
+
+/* ---- coarse-to-fine alignment in one call: the recipe above llsm_gpu_batch_align_around -- pool, align the coarse pair,
+ * turn its positions into a line, pick a band, search the fine pair around the line -- for every pair of a list, with the
+ * pooled vectors formed and kept on the device: LLSM_GPU_CODE does not cross the link, no throw-away batch is made, and
+ * the band is chosen so that it is connected.  pos and cost are those of llsm_gpu_batch_align_around under the line and the
+ * band the call made; center_out (sum_p na(p) columns, the layout of pos; may be NULL) receives the lines and band_out
+ * (n_pairs; may be NULL) the bands.  Synchronous.  A refused call returns -1 with a message that starts with
+ * "llsm_gpu_batch_align_pyramid:" and leaves pos, cost, center_out and band_out untouched.  LLSM_GPU_CODE of both batches is
+ * read and no array of either written; a == b is allowed, and an utterance may appear in any number of pairs.  A pair's
+ * result depends on its own two utterances, factor, margin, slope and the options only.  Scratch: two sets of its own on a,
+ * one per pass, the pooled vectors among them; planes 6, 9, 12, 13 and 14 and the scratch of the five calls above stay as
+ * they were, and the two sets have no plane number in llsm_gpu_batch_debug_plane.
+ *
+ * The rules, per pair of na x nb frames.
+ *  Y1. Both utterances are pooled by P1 to nca x ncb vectors.
+ *  Y2. The pooled pair is aligned with opt unchanged: slope = 0 by rules D1 - D3 of llsm_gpu_batch_align, slope = 1 by rules
+ *      L1 - L4 of llsm_gpu_batch_align_slope.  This gives pos_c[0 .. nca).
+ *  Y3. center = llsm_gpu_align_center_line(nca, ncb, pos_c, na, nb): that function, not a restatement of it.
+ *  Y4. band = max(min(margin x factor, nb - 1), llsm_gpu_align_around_min(na, nb, center, slope)), the product taken in 64
+ *      bits: margin is the half-width in coarse frames, and the band is always connected.
+ *  Y5. Rules A1 - A3 of llsm_gpu_batch_align_around with this line, this band and slope.
+ * It follows, and tests/test_gpu_align_pyramid.py holds it to the bit, that the call gives what llsm_gpu_batch_pool_code,
+ * llsm_gpu_batch_align or _slope on batches that hold the pooled vectors, llsm_gpu_align_center_line,
+ * llsm_gpu_align_around_min and llsm_gpu_batch_align_around give when run by hand; that with margin x factor >= nb - 1 pos
+ * and cost are those of llsm_gpu_batch_align (slope = 0) or llsm_gpu_batch_align_slope (slope = 1) on the fine pair; and that
+ * for finite features cost is never below the cost of that full call.  A 1 x 1 coarse pair (both utterances no longer than
+ * factor) gives an all-zero line, which llsm_gpu_align_around_min answers with nb - 1: the whole matrix.
+ *
+ * Refused, each check over all pairs before the next, before anything is allocated, copied or launched: (1) everything
+ * llsm_gpu_batch_align refuses short of its cap, by the same code and in the same order (n_pairs == 0 returns 0 here, as it
+ * does there); (2) a factor outside [2, 64], a negative margin, a slope that is neither 0 nor 1; (3) under slope = 1 a fine
+ * pair that is not admissible under L1, in the words of llsm_gpu_batch_align_slope, or a coarse pair that is not (the message
+ * names the pair, both sizes and the factor: 64 x 127 frames pool to 1 x 2 at factor 64 -- a smaller factor is the remedy);
+ * (4) a sum of nca x ncb above 2^28 cells.  The cap of the fine pass, a sum of na x (2 band + 1) above 2^28 cells, is known
+ * only after the coarse pass: it is refused then, in the words of llsm_gpu_batch_align_around, with pos, cost, center_out and
+ * band_out untouched -- but the call's own coarse scratch and pooled vectors have been written by then (nothing a caller can
+ * observe: they have no plane).
+ * Known limits: one wavefront walks a pair in either pass; two levels only; an utterance that appears in k pairs is pooled
+ * k times; the lines and the bands are made on the host between the passes, na steps per pair (times log2 nb under
+ * slope = 1, whose least band is found by bisection). */
+int  llsm_gpu_batch_align_pyramid(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       int factor   /* 2 .. 64 */,
+       int margin   /* >= 0, half-width of the fine band in COARSE frames */,
+       int slope    /* 0 or 1, as llsm_gpu_batch_align_around */,
+       const llsm_gpu_align_options* opt /* NULL: defaults */,
+       FP_TYPE* pos, FP_TYPE* cost /* may be NULL */,
+       int* center_out /* sum_p na(p), layout of pos; may be NULL */,
+       int* band_out   /* n_pairs; may be NULL */);
 
 /* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
  * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere

@@ -161,6 +161,7 @@ llsm_gpu_batch_align_band llsm_gpu_align_band_min llsm_gpu_align_band_rows
 llsm_gpu_batch_align_slope llsm_gpu_align_slope_rows
 llsm_gpu_batch_align_band_slope llsm_gpu_align_band_slope_min llsm_gpu_align_band_slope_rows
 llsm_gpu_batch_align_around llsm_gpu_align_around_rows llsm_gpu_align_around_min llsm_gpu_align_center_line
+llsm_gpu_pool_frames llsm_gpu_batch_pool_code llsm_gpu_batch_align_pyramid
 llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select llsm_gpu_batch_select_chain
 """.split()
 
@@ -275,6 +276,14 @@ def load():
         L.llsm_gpu_align_around_rows.argtypes = [C.c_int, C.c_int, P_int, C.c_int, C.c_int, P_int, P_int]
         L.llsm_gpu_align_around_min.argtypes = [C.c_int, C.c_int, P_int, C.c_int]
         L.llsm_gpu_align_center_line.argtypes = [C.c_int, C.c_int, P_fp, C.c_int, C.c_int, P_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the pooling and the pyramid)
+        L.llsm_gpu_pool_frames.argtypes = [C.c_int, C.c_int]
+        L.llsm_gpu_batch_pool_code.argtypes = [vp, C.c_int, C.c_int, P_int, P_fp]
+        L.llsm_gpu_batch_align_pyramid.argtypes = [vp, vp, C.c_int, P_int, P_int, C.c_int, C.c_int, C.c_int, C.POINTER(AlignOptions),
+                                                   P_fp, P_fp, P_int, P_int]
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -549,6 +558,15 @@ def align_center_line(pos_c, nb_c, na, nb):
     _check(load().llsm_gpu_align_center_line(len(pc), int(nb_c), pc.ctypes.data_as(P_fp), int(na), int(nb),
                                              c.ctypes.data_as(P_int)), "align_center_line")
     return c
+
+
+def pool_frames(nfrm, factor):
+    """the coarse frames of an utterance of nfrm frames pooled by `factor`, ceil(nfrm / factor) (llsm_gpu_pool_frames, rule P1
+    of llsm_gpu_batch_pool_code); nfrm < 1 and a factor outside [1, 64] are refused"""
+    r = load().llsm_gpu_pool_frames(int(nfrm), int(factor))
+    if r < 0:
+        raise LlsmError("pool_frames: " + load().llsm_gpu_last_error().decode())
+    return int(r)
 
 
 def make_select_options(**kw):
@@ -933,6 +951,45 @@ class Batch:
             raise ValueError("align_around: center has %d columns, the pairs have %d frames" % (len(c), need))
         return self._align(self.L.llsm_gpu_batch_align_around, "align_around", other, utt_a, utt_b, band, options,
                            before=(c.ctypes.data_as(P_int),), after=(int(slope),))
+
+    def _frames_of(self, utts):
+        """the frames of the listed utterances, 0 for an index outside (which is the library's to refuse)"""
+        u = np.ascontiguousarray(utts, np.int32).reshape(-1)
+        nfrm = np.diff(self.frm_off)
+        inside = (u >= 0) & (u < len(nfrm))
+        n = np.zeros(len(u), np.int64); n[inside] = nfrm[u[inside]]
+        return u, n
+
+    def pool_code(self, utts, factor):
+        """the coder vectors of the listed utterances (repeats allowed, any order) pooled by `factor`: the mean of every
+        `factor` consecutive rows of A_CODE, computed on the device (llsm_gpu_batch_pool_code, rule P1) -- the input of a
+        coarse alignment.  Returns a list with one float32 array [pool_frames(nfrm, factor)][coder_dimension] per entry"""
+        u, n = self._frames_of(utts)
+        f = int(factor)
+        nc = (n + f - 1) // f if 1 <= f <= 64 else np.zeros(len(u), np.int64)      # (a factor outside is the library's to refuse)
+        dim = self.coder_dimension
+        dst = np.zeros((int(nc.sum()), max(dim, 0)), np.float32)
+        _check(self.L.llsm_gpu_batch_pool_code(self.h, f, len(u), u.ctypes.data_as(P_int), dst.ctypes.data_as(P_fp)), "pool_code")
+        return np.split(dst, np.cumsum(nc)[:-1]) if len(u) else []
+
+    def align_pyramid(self, other, utt_a, utt_b, factor, margin, slope=False, **options):
+        """coarse-to-fine alignment in one call (llsm_gpu_batch_align_pyramid): both utterances of a pair pooled by `factor`
+        on the device, the pooled pair aligned (align, or align_slope with slope), its positions turned into a centre line
+        (align_center_line), and the fine pair searched within max(margin * factor, align_around_min) columns of it
+        (align_around).  Returns (pos, cost, center, band): what align_around returns, a list with the line of every pair
+        (int32) and the int32 array of the bands that were used"""
+        o = make_align_options(**options)
+        ua, na = self._frames_of(utt_a)
+        ub = np.ascontiguousarray(utt_b, np.int32).reshape(-1)
+        assert ua.shape == ub.shape, (ua.shape, ub.shape)
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        center = np.zeros(int(na.sum()), np.int32); band = np.zeros(len(ua), np.int32)
+        _check(self.L.llsm_gpu_batch_align_pyramid(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                                                   int(factor), int(margin), int(slope), C.byref(o), pos.ctypes.data_as(P_fp),
+                                                   cost.ctypes.data_as(P_fp), center.ctypes.data_as(P_int), band.ctypes.data_as(P_int)),
+               "align_pyramid")
+        cut = np.cumsum(na)[:-1]
+        return (np.split(pos, cut) if len(ua) else []), cost, (np.split(center, cut) if len(ua) else []), band
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders
     def select(self, bank, opt=None, **options):

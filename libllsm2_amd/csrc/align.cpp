@@ -24,8 +24,18 @@
 //                                    section 30: the kernels of the banded calls instantiated for ALIGN_GEO_LINE, which read
 //                                    the centre of a row from a table), with scratch of its own
 //
-// The five calls are one function, align_run, told apart by an AlignMode (band, slope, around: batch.h): the name in the
-// messages, the scratch set, the steps of a strip (strip_steps) and the kernel instantiations follow from it.  Every check
+//   llsm_gpu_pool_frames            host only: the coarse frames of an utterance under a pooling factor (rule P1)
+//   llsm_gpu_batch_pool_code        the means of every `factor` consecutive rows of LLSM_GPU_CODE of the listed utterances
+//                                    (rule P1, DESIGN.md section 34: k_pool_code) on the host
+//   llsm_gpu_batch_align_pyramid    coarse to fine in one call (rules Y1 - Y5): both sides pooled on the device, the pooled
+//                                    pairs through the full or the slope pass, llsm_gpu_align_center_line and
+//                                    llsm_gpu_align_around_min on the host, the fine pairs through the pass around the line,
+//                                    with two scratch sets of its own and no plane
+//
+// The five calls are one pass, align_pass behind align_head, told apart by an AlignMode (band, slope, around: batch.h): the
+// steps of a strip (strip_steps) and the kernel instantiations follow from it, and for the five calls (align_run) the name in
+// the messages and the scratch set do too.  A pass reads its two sides through AlignSide views and takes scratch set and name
+// from its AlignJob, so the pyramid runs it twice: on the pooled rows and on the batches' own.  Every check
 // runs before anything is allocated, copied or launched.  The scratch lives on batch a, grow-only, one set per call.
 // Wherever a function takes `line`, NULL stands for the straight diagonal of rule B1, computed.
 #include <hip/hip_runtime.h>
@@ -219,15 +229,37 @@ int strip_steps(int mode, const AlignPair& q, const int* line, int i0, const int
   return std::max(jhi - jlo, 0) + 1 + i1 - i0 + ((mode & ALIGN_SLOPE) && i1 + 1 < q.na ? 1 : 0);
 }
 
-// The five calls, told apart by `mode` (AlignMode: batch.h): the name the messages carry and the scratch set on a follow
-// from it.  With ALIGN_BAND the planes are band planes, else band is not read and the planes hold the whole matrix of every
-// pair.  The checks run in the order in which the calls have always made them.  ALIGN_AROUND comes with ALIGN_BAND, with the
-// centre lines of all pairs in `center` and with the caller's `slope` as `pattern`, which becomes the ALIGN_SLOPE bit once it
-// has been checked; that call makes its checks in the order of its header, each over all pairs before the next.
-int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, int mode, int pattern,
-  const int* center, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
-  const bool banded = mode & ALIGN_BAND, around = mode & ALIGN_AROUND;
-  const char* who = kAlignCalls[align_call(mode)].name;
+// One side of a call: the rows of LLSM_GPU_CODE of a batch and where its utterances lie in them -- or, in the coarse pass of
+// llsm_gpu_batch_align_pyramid, the pooled rows of a pair list and where each pair's lie.  code is a device pointer and is
+// not read on the host; the other two are host arrays of n_utt + 1 and n_utt entries.
+struct AlignSide { const float* code; const int* frm_off; const int* nfrm; int n_utt; };
+AlignSide side_of(const llsm_gpu_batch* b) {
+  return AlignSide{(const float*)b -> arr[LLSM_GPU_CODE], b -> frm_off.data(), b -> nfrm.data(), b -> lay.n_utt};
+}
+// What a pass runs on and for: the batch whose context, stream and scratch it uses, the two sides (dim columns a row), the
+// checked options, the scratch set it rewrites and the name its messages carry.
+struct AlignJob {
+  llsm_gpu_batch* owner; AlignSide a, b; int dim; llsm_gpu_align_options o; llsm_gpu_batch::AlignScratch* sc; const char* who;
+};
+
+std::string pair_of(int p) { return "pair " + std::to_string(p) + ": "; }   // (only a refusal pays for it)
+// empty, or why the utterances of pair p cannot be aligned
+std::string pair_fault(const AlignSide& a, const AlignSide& b, int p, int ua, int ub) {
+  if(ua < 0 || ua >= a.n_utt) return pair_of(p) + "utterance " + std::to_string(ua) + " is outside batch a";
+  if(ub < 0 || ub >= b.n_utt) return pair_of(p) + "utterance " + std::to_string(ub) + " is outside batch b";
+  if(a.nfrm[ua] <= 0 || b.nfrm[ub] <= 0) return pair_of(p) + "an utterance without frames";
+  return "";
+}
+// empty, or rule L1's refusal of pair p in the words of llsm_gpu_batch_align_slope
+std::string inadmissible(int p, int na, int nb) {
+  const std::string bound = slope_bound(na, nb);
+  return bound.empty() ? "" : pair_of(p) + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound;
+}
+
+// What every call refuses of its two batches and its options before it looks at a pair, in the order in which the calls
+// have always made these checks; o: the options, checked and resolved.
+int align_head(const llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const llsm_gpu_align_options* opt, const char* who,
+  llsm_gpu_align_options& o) {
   if(! a || ! b) return refuse("NULL batch", who);
   if(n_pairs < 0) return refuse("n_pairs < 0", who);
   if(a -> ctx != b -> ctx) return refuse("the batches belong to different contexts", who);
@@ -235,40 +267,40 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   if(a -> coder_os + a -> coder_ob != b -> coder_os + b -> coder_ob)
     return refuse("the coder dimensions differ: " + std::to_string(a -> coder_os + a -> coder_ob + 3) + " and " +
       std::to_string(b -> coder_os + b -> coder_ob + 3), who);
-  llsm_gpu_align_options o;
   if(opt) o = *opt; else llsm_gpu_align_default_options(& o);
-  if(check(& o, a -> coder_os, a -> coder_ob, who)) return -1;
+  return check(& o, a -> coder_os, a -> coder_ob, who);
+}
+
+// One pass over the pairs of a list, after align_head: the five calls and the two passes of llsm_gpu_batch_align_pyramid,
+// told apart by `mode` (AlignMode: batch.h) and by the job.  With ALIGN_BAND the planes are band planes, else band is not
+// read and the planes hold the whole matrix of every pair.  The checks run in the order in which the calls have always made
+// them.  ALIGN_AROUND comes with ALIGN_BAND, with the centre lines of all pairs in `center` and with the caller's `slope` as
+// `pattern`, which becomes the ALIGN_SLOPE bit once it has been checked; that call makes its checks in the order of its
+// header, each over all pairs before the next.
+int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_b, int mode, int pattern, const int* center,
+  const int* band, FP_TYPE* pos, FP_TYPE* cost) {
+  const bool banded = mode & ALIGN_BAND, around = mode & ALIGN_AROUND;
+  const char* who = J.who;
+  const AlignSide& a = J.a; const AlignSide& b = J.b;
+  const llsm_gpu_align_options& o = J.o;
   if(n_pairs == 0) return 0;
   if(! utt_a || ! utt_b) return refuse("NULL utterance list", who);
   if(banded && ! around && ! band) return refuse("NULL band", who);
   if(! pos) return refuse("NULL pos", who);
-  auto pair_of = [](int p) { return "pair " + std::to_string(p) + ": "; };   // (only a refusal pays for it)
-  // empty, or why the utterances of pair p cannot be aligned
-  auto pair_fault = [&](int p) -> std::string {
-    const int ua = utt_a[p], ub = utt_b[p];
-    if(ua < 0 || ua >= a -> lay.n_utt) return pair_of(p) + "utterance " + std::to_string(ua) + " is outside batch a";
-    if(ub < 0 || ub >= b -> lay.n_utt) return pair_of(p) + "utterance " + std::to_string(ub) + " is outside batch b";
-    if(a -> nfrm[ua] <= 0 || b -> nfrm[ub] <= 0) return pair_of(p) + "an utterance without frames";
-    return "";
-  };
-  auto inadmissible = [&](int p, int na, int nb) -> std::string {
-    const std::string bound = slope_bound(na, nb);
-    return bound.empty() ? "" : pair_of(p) + std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound;
-  };
   if(around) {                                                      // checks 1 - 6 of llsm_gpu_batch_align_around (7 and 8: below)
-    for(int p = 0; p < n_pairs; p ++) { const std::string why = pair_fault(p); if(! why.empty()) return refuse(why, who); }
+    for(int p = 0; p < n_pairs; p ++) { const std::string why = pair_fault(a, b, p, utt_a[p], utt_b[p]); if(! why.empty()) return refuse(why, who); }
     if(pattern != 0 && pattern != 1) return refuse("slope = " + std::to_string(pattern) + " is neither 0 nor 1", who);
     if(pattern) mode |= ALIGN_SLOPE;
     if(! band || ! center) return refuse("NULL band or center", who);
     for(int p = 0; p < n_pairs; p ++) if(band[p] < 0) return refuse(pair_of(p) + "band < 0", who);
     for(int p = 0; p < n_pairs && pattern; p ++) {
-      const std::string why = inadmissible(p, a -> nfrm[utt_a[p]], b -> nfrm[utt_b[p]]);
+      const std::string why = inadmissible(p, a.nfrm[utt_a[p]], b.nfrm[utt_b[p]]);
       if(! why.empty()) return refuse(why, who);
     }
     long long at = 0;
     for(int p = 0; p < n_pairs; p ++) {
-      const int na = a -> nfrm[utt_a[p]];
-      const std::string why = line_fault(na, b -> nfrm[utt_b[p]], center + at);
+      const int na = a.nfrm[utt_a[p]];
+      const std::string why = line_fault(na, b.nfrm[utt_b[p]], center + at);
       if(! why.empty()) return refuse(pair_of(p) + why, who);
       at += na;
     }
@@ -278,10 +310,10 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   // list fits 64 bits
   auto plane_cells = [&](int r) -> long long {
     const int ua = utt_a[r], ub = utt_b[r];
-    if(ua < 0 || ua >= a -> lay.n_utt) return 0;
-    const long long na = std::max(a -> nfrm[ua], 0);
+    if(ua < 0 || ua >= a.n_utt) return 0;
+    const long long na = std::max(a.nfrm[ua], 0);
     if(banded) return std::min(na * (2ll * std::max(band[r], 0) + 1), 1ll << 61);
-    return ub < 0 || ub >= b -> lay.n_utt ? 0 : na * std::max(b -> nfrm[ub], 0);
+    return ub < 0 || ub >= b.n_utt ? 0 : na * std::max(b.nfrm[ub], 0);
   };
   std::vector<int2> table, region;                                  // rule K1: the rows of the region of all pairs, and of one
   std::vector<AlignPair> pairs((size_t)n_pairs);
@@ -289,15 +321,14 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   bool over = false;                                                // around a line: the cap is passed, and refused after the last band
   for(int p = 0; p < n_pairs; p ++) {
     const int ua = utt_a[p], ub = utt_b[p], bd = banded ? band[p] : 0;
-    auto pair = [p] { return "pair " + std::to_string(p) + ": "; };   // (only a refusal pays for it)
-    const std::string fault = pair_fault(p);
+    const std::string fault = pair_fault(a, b, p, ua, ub);
     if(! fault.empty()) return refuse(fault, who);
-    const int na = a -> nfrm[ua], nb = b -> nfrm[ub];
+    const int na = a.nfrm[ua], nb = b.nfrm[ub];
     const int* line = around ? center + frames : nullptr;           // (frames: the rows of the pairs before this one)
-    if(bd < 0) return refuse(pair() + "band < 0", who);
+    if(bd < 0) return refuse(pair_of(p) + "band < 0", who);
     const int least = ! banded || slope ? 0 : around ? around_min(na, nb, line) : band_min(na, nb);
     if(bd < least)
-      return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
+      return refuse(pair_of(p) + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
         std::to_string(nb) + " frames: " + (around ? "llsm_gpu_align_around_min is " : "llsm_gpu_align_band_min is ") +
         std::to_string(least), who);
     if(slope) {
@@ -307,7 +338,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
     // (a pair of the shape and band of the pair before it shares that pair's rows of the table: equal takes are common)
     const bool as_before = bslope && ! around && p > 0 && na == pairs[p - 1].na && nb == pairs[p - 1].nb && bd == pairs[p - 1].band;
     if(bslope && ! as_before && ! band_slope_rows(na, nb, bd, region, line))
-      return refuse(pair() + "a band of " + std::to_string(bd) + " is not connected for the slope pattern on " + std::to_string(na) +
+      return refuse(pair_of(p) + "a band of " + std::to_string(bd) + " is not connected for the slope pattern on " + std::to_string(na) +
         " x " + std::to_string(nb) + " frames: " + (around ? "llsm_gpu_align_around_min is " + std::to_string(around_slope_min(na, nb, line))
         : "llsm_gpu_align_band_slope_min is " + std::to_string(band_slope_min(na, nb))), who);
     if(over) {                                                      // only the bands of the remaining pairs are still looked at
@@ -316,7 +347,7 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
       continue;
     }
     AlignPair& q = pairs[p];
-    q.a0 = a -> frm_off[ua]; q.na = na; q.b0 = b -> frm_off[ub]; q.nb = nb;
+    q.a0 = a.frm_off[ua]; q.na = na; q.b0 = b.frm_off[ub]; q.nb = nb;
     q.cell0 = (int)cells; q.row0 = (int)rows; q.pos0 = (int)frames; q.band = bd; q.mv0 = steps;
     q.pad = as_before ? pairs[p - 1].pad : (int)table.size();       // where the pair's rows of the region start
     if(bslope && ! as_before) table.insert(table.end(), region.begin(), region.end());
@@ -339,21 +370,21 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   }
   if(over)
     return refuse("the band planes hold " + std::to_string(cells) + " cells, more than 2^28 = " + std::to_string(kMaxCells), who);
-  // accepted: from here on this call's scratch on a changes (and the other call's, its plane among it, does not)
-  llsm_gpu_batch::AlignScratch& sc = a -> align[align_call(mode)];
+  // accepted: from here on this pass's scratch set changes (and those of the other calls, their planes among them, do not)
+  llsm_gpu_batch::AlignScratch& sc = *J.sc;
   std::vector<int4> tiles; tiles.reserve((size_t)n_tiles);
   for(int p = 0; p < n_pairs; p ++)                                 // the tiles of the matrix that meet the rows' columns, overhang included
     for(int i0 = 0, jlo, jhi; i0 < pairs[p].na; i0 += ALIGN_TILE) {
       strip_span(banded, pairs[p], around ? center + pairs[p].pos0 : nullptr, i0, jlo, jhi);
       for(int j0 = tile_floor(jlo); j0 <= jhi; j0 += ALIGN_TILE) tiles.push_back(make_int4(p, i0, j0, 0));
     }
-  hipSetDevice(a -> ctx -> device);
+  hipSetDevice(J.owner -> ctx -> device);
   const size_t n_out = (size_t)frames + (size_t)n_pairs;
   if(sc.plane.alloc((size_t)cells) || sc.row.alloc((size_t)rows) || sc.out.alloc(n_out) || sc.moves.alloc((size_t)steps) ||
      sc.pairs.alloc(pairs.size()) || sc.tiles.alloc(tiles.size()) || sc.region.alloc(table.size()) ||
      (around && sc.center.alloc((size_t)frames))) return -1;
   sc.cells = 0;                                                     // the planes are being rewritten
-  LaunchCtx* P = & a -> ctx -> lc;
+  LaunchCtx* P = & J.owner -> ctx -> lc;
   // (pageable sources: the copies have left the vectors when the calls return, and run in stream order)
   HIP_OK(hipMemcpyAsync(sc.pairs.p, pairs.data(), pairs.size() * sizeof(AlignPair), hipMemcpyHostToDevice, P -> stream));
   HIP_OK(hipMemcpyAsync(sc.tiles.p, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, P -> stream));
@@ -361,8 +392,8 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   if(around) HIP_OK(hipMemcpyAsync(sc.center.p, center, (size_t)frames * sizeof(int), hipMemcpyHostToDevice, P -> stream));
   const AlignGeo geo = around ? ALIGN_GEO_LINE : banded ? ALIGN_GEO_BAND : ALIGN_GEO_FULL;
   AlignDev d;
-  d.code_a = (const float*)a -> arr[LLSM_GPU_CODE]; d.code_b = (const float*)b -> arr[LLSM_GPU_CODE];
-  d.dim = a -> coder_os + a -> coder_ob + 3; d.first = o.first; d.count = o.count;
+  d.code_a = a.code; d.code_b = b.code;
+  d.dim = J.dim; d.first = o.first; d.count = o.count;
   d.step_cost = o.step_cost; d.voicing_cost = o.voicing_cost;
   d.pairs = sc.pairs.p; d.n_pairs = n_pairs;
   const int* lines = around ? sc.center.p : nullptr;
@@ -378,6 +409,16 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
   if(cost) std::copy(host.begin() + frames, host.end(), cost);
   sc.cells = cells;
   return 0;
+}
+
+// The five calls: the batches' own rows, the name and the scratch set on a that follow from `mode`
+int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b, int mode, int pattern,
+  const int* center, const int* band, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
+  const char* who = kAlignCalls[align_call(mode)].name;
+  llsm_gpu_align_options o;
+  if(align_head(a, b, n_pairs, opt, who, o)) return -1;
+  const AlignJob J{a, side_of(a), side_of(b), a -> coder_os + a -> coder_ob + 3, o, & a -> align[align_call(mode)], who};
+  return align_pass(J, n_pairs, utt_a, utt_b, mode, pattern, center, band, pos, cost);
 }
 }  // namespace
 
@@ -560,4 +601,142 @@ extern "C" int llsm_gpu_align_center_line(int na_c, int nb_c, const FP_TYPE* pos
 extern "C" int llsm_gpu_batch_align_around(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const int* center, const int* band, int slope, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
   return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_AROUND | ALIGN_BAND, slope, center, band, opt, pos, cost);
+}
+
+// ---------------------------------------------------------------- pooled vectors (rule P1) and coarse to fine in one call
+namespace {
+const char* const kPyramid = "llsm_gpu_batch_align_pyramid";
+const char* const kPool = "llsm_gpu_batch_pool_code";
+
+int pool_frames(int nfrm, int factor) { return (int)(((long long)nfrm + factor - 1) / factor); }
+
+// the table of k_pool_code (kernels.h) to the device and the launch, in stream order; out: [coarse_frames][dim]
+int pool_launch(llsm_gpu_context* ctx, const float* code_a, const float* code_b, const std::vector<int4>& tab, int dim, int factor,
+  long long coarse_frames, DevBuf<int4>& d_tab, DevBuf<float>& out, const char* who) {
+  if(d_tab.alloc(tab.size()) || out.alloc((size_t)coarse_frames * dim)) return -1;
+  LaunchCtx* P = & ctx -> lc;
+  HIP_OK(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice, P -> stream));
+  const int rc = launch_pool_code(P, code_a, code_b, d_tab.p, (int)tab.size(), dim, factor, coarse_frames, out.p);
+  if(rc) return refuse(std::string("launch failed: ") + hipGetErrorString((hipError_t)rc), who);
+  return 0;
+}
+}  // namespace
+
+extern "C" int llsm_gpu_pool_frames(int nfrm, int factor) {
+  if(nfrm < 1 || factor < 1 || factor > 64)
+    return refuse("nfrm < 1 or a factor outside [1, 64] (nfrm = " + std::to_string(nfrm) + ", factor = " + std::to_string(factor) + ")",
+      "llsm_gpu_pool_frames");
+  return pool_frames(nfrm, factor);
+}
+
+extern "C" int llsm_gpu_batch_pool_code(const llsm_gpu_batch* b, int factor, int n, const int* utts, FP_TYPE* dst) {
+  if(! b) return refuse("NULL batch", kPool);
+  if(b -> coder_os == 0) return refuse("the coder is not enabled", kPool);
+  if(factor < 1 || factor > 64) return refuse("factor = " + std::to_string(factor) + " lies outside [1, 64]", kPool);
+  if(n < 0) return refuse("n < 0", kPool);
+  if(n == 0) return 0;
+  if(! utts || ! dst) return refuse("NULL list or dst", kPool);
+  std::vector<int4> tab((size_t)n);
+  long long frames = 0;
+  for(int k = 0; k < n; k ++) {
+    const int u = utts[k];
+    if(u < 0 || u >= b -> lay.n_utt) return refuse("entry " + std::to_string(k) + ": utterance " + std::to_string(u) + " is outside the batch", kPool);
+    if(b -> nfrm[u] <= 0) return refuse("entry " + std::to_string(k) + ": an utterance without frames", kPool);
+    // (an offset that does not fit is never used: the total is refused below)
+    tab[k] = make_int4(b -> frm_off[u], b -> nfrm[u], (int)frames, 0);
+    frames += pool_frames(b -> nfrm[u], factor);
+  }
+  if(frames > kMaxCells) return refuse("the pooled vectors hold " + std::to_string(frames) + " frames, more than 2^28 = " + std::to_string(kMaxCells), kPool);
+  const int dim = b -> coder_os + b -> coder_ob + 3;
+  hipSetDevice(b -> ctx -> device);
+  DevBuf<int4> d_tab; DevBuf<float> out;                            // (local: the stream is synchronised before they go)
+  const float* code = (const float*)b -> arr[LLSM_GPU_CODE];
+  if(pool_launch(b -> ctx, code, code, tab, dim, factor, frames, d_tab, out, kPool)) return -1;
+  // into memory of our own first: a failed copy leaves dst untouched
+  std::vector<float> host((size_t)frames * dim);
+  hipStream_t stream = b -> ctx -> lc.stream;
+  const hipError_t e = hipMemcpyAsync(host.data(), out.p, host.size() * sizeof(float), hipMemcpyDeviceToHost, stream);
+  const hipError_t s = hipStreamSynchronize(stream);                // (whatever the copy said: the buffers are freed on return)
+  if(e != hipSuccess || s != hipSuccess) return refuse(std::string("copy failed: ") + hipGetErrorString(e != hipSuccess ? e : s), kPool);
+  std::copy(host.begin(), host.end(), dst);
+  return 0;
+}
+
+extern "C" int llsm_gpu_batch_align_pyramid(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
+  const int* utt_b, int factor, int margin, int slope, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost,
+  int* center_out, int* band_out) {
+  const char* who = kPyramid;
+  // 1: what llsm_gpu_batch_align refuses short of its cap
+  llsm_gpu_align_options o;
+  if(align_head(a, b, n_pairs, opt, who, o)) return -1;
+  if(n_pairs == 0) return 0;
+  if(! utt_a || ! utt_b) return refuse("NULL utterance list", who);
+  if(! pos) return refuse("NULL pos", who);
+  const AlignSide fine_a = side_of(a), fine_b = side_of(b);
+  for(int p = 0; p < n_pairs; p ++) {
+    const std::string why = pair_fault(fine_a, fine_b, p, utt_a[p], utt_b[p]);
+    if(! why.empty()) return refuse(why, who);
+  }
+  // 2
+  if(factor < 2 || factor > 64) return refuse("factor = " + std::to_string(factor) + " lies outside [2, 64]", who);
+  if(margin < 0) return refuse("margin < 0", who);
+  if(slope != 0 && slope != 1) return refuse("slope = " + std::to_string(slope) + " is neither 0 nor 1", who);
+  // 3: rule L1 on the fine and on the coarse pair
+  std::vector<int> nca((size_t)n_pairs), ncb((size_t)n_pairs), off_a((size_t)n_pairs + 1, 0), off_b((size_t)n_pairs + 1, 0);
+  for(int p = 0; p < n_pairs; p ++) {
+    const int na = fine_a.nfrm[utt_a[p]], nb = fine_b.nfrm[utt_b[p]];
+    nca[p] = pool_frames(na, factor); ncb[p] = pool_frames(nb, factor);
+    if(! slope) continue;
+    const std::string why = inadmissible(p, na, nb);
+    if(! why.empty()) return refuse(why, who);
+    const std::string bound = slope_bound(nca[p], ncb[p]);
+    if(! bound.empty())
+      return refuse(pair_of(p) + std::to_string(na) + " x " + std::to_string(nb) + " frames pool to " + std::to_string(nca[p]) + " x " +
+        std::to_string(ncb[p]) + " at factor " + std::to_string(factor) + ", which are not admissible: " + bound + " (a smaller factor may admit the pair)", who);
+  }
+  // 4: the planes of the coarse pass.  Under the cap the coarse frames of either side are 2^28 at the most, as a pair has
+  // no fewer cells than frames on either side, so every offset below fits an int.
+  long long cells = 0;
+  for(int p = 0; p < n_pairs; p ++) cells += (long long)nca[p] * ncb[p];
+  if(cells > kMaxCells)
+    return refuse("the coarse distance planes hold " + std::to_string(cells) + " cells, more than 2^28 = " + std::to_string(kMaxCells), who);
+  // accepted.  Y1: the pooled rows of a's utterances, pair after pair, then those of b's, in one launch
+  for(int p = 0; p < n_pairs; p ++) { off_a[p + 1] = off_a[p] + nca[p]; off_b[p + 1] = off_b[p] + ncb[p]; }
+  const int frames_a = off_a[n_pairs], frames_b = off_b[n_pairs], dim = a -> coder_os + a -> coder_ob + 3;
+  std::vector<int4> tab((size_t)2 * n_pairs);
+  std::vector<int> own((size_t)n_pairs);                            // the coarse sides hold one utterance per pair
+  for(int p = 0; p < n_pairs; p ++) {
+    tab[p] = make_int4(fine_a.frm_off[utt_a[p]], fine_a.nfrm[utt_a[p]], off_a[p], 0);
+    tab[(size_t)n_pairs + p] = make_int4(fine_b.frm_off[utt_b[p]], fine_b.nfrm[utt_b[p]], frames_a + off_b[p], 1);
+    own[p] = p;
+  }
+  hipSetDevice(a -> ctx -> device);
+  if(pool_launch(a -> ctx, fine_a.code, fine_b.code, tab, dim, factor, (long long)frames_a + frames_b, a -> pyramid_tab, a -> pyramid_code, who))
+    return -1;
+  // Y2: the coarse pass over the pooled rows
+  const AlignSide coarse_a{a -> pyramid_code.p, off_a.data(), nca.data(), n_pairs};
+  const AlignSide coarse_b{a -> pyramid_code.p + (size_t)frames_a * dim, off_b.data(), ncb.data(), n_pairs};
+  std::vector<FP_TYPE> pos_c((size_t)frames_a);
+  const AlignJob coarse{a, coarse_a, coarse_b, dim, o, & a -> pyramid[0], who};
+  if(align_pass(coarse, n_pairs, own.data(), own.data(), slope ? ALIGN_SLOPE : ALIGN_FULL, 0, nullptr, nullptr, pos_c.data(), nullptr)) return -1;
+  // Y3, Y4: the lines and the bands, by the public host calls
+  long long rows = 0;
+  for(int p = 0; p < n_pairs; p ++) rows += fine_a.nfrm[utt_a[p]];
+  std::vector<int> center((size_t)rows), band((size_t)n_pairs);
+  rows = 0;
+  for(int p = 0; p < n_pairs; p ++) {
+    const int na = fine_a.nfrm[utt_a[p]], nb = fine_b.nfrm[utt_b[p]];
+    int* line = center.data() + rows;
+    if(llsm_gpu_align_center_line(nca[p], ncb[p], pos_c.data() + off_a[p], na, nb, line)) return refuse(pair_of(p) + llsm_gpu_last_error(), who);
+    const int least = llsm_gpu_align_around_min(na, nb, line, slope);
+    if(least < 0) return refuse(pair_of(p) + llsm_gpu_last_error(), who);
+    band[p] = std::max((int)std::min((long long)margin * factor, (long long)nb - 1), least);
+    rows += na;
+  }
+  // Y5: the fine pass; it alone can still refuse, for its cap
+  const AlignJob fine{a, fine_a, fine_b, dim, o, & a -> pyramid[1], who};
+  if(align_pass(fine, n_pairs, utt_a, utt_b, ALIGN_AROUND | ALIGN_BAND, slope, center.data(), band.data(), pos, cost)) return -1;
+  if(center_out) std::copy(center.begin(), center.end(), center_out);
+  if(band_out) std::copy(band.begin(), band.end(), band_out);
+  return 0;
 }

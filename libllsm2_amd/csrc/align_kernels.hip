@@ -2,8 +2,9 @@
 // llsm_gpu_batch_align_band (rules B1 - B4, section 25), llsm_gpu_batch_align_slope (rules L1 - L4, section 27; its planes are
 // k_align_dist_t's full ones) and llsm_gpu_batch_align_band_slope (rules K1 - K4, section 28; its planes are k_align_dist_t's
 // band ones); the path kernel of the last two, k_align_slope_dtw_t, is described above it; and llsm_gpu_batch_align_around
-// (rules A1 - A3, section 30), which runs the band instantiations of all three around a centre line of the caller's; host
-// side: align.cpp.  Three kernel templates, each instantiated for the three geometries (AlignGeo: kernels.h):
+// (rules A1 - A3, section 30), which runs the band instantiations of all three around a centre line of the caller's; and
+// k_pool_code (rule P1, section 34), the pooled vectors of llsm_gpu_batch_pool_code and of the coarse pass of
+// llsm_gpu_batch_align_pyramid, which is otherwise made of the kernels above; host side: align.cpp.  Three kernel templates, each instantiated for the three geometries (AlignGeo: kernels.h):
 //   full    row i spans columns 0 ... nb - 1 and is stored as it is: off = 0, width = nb, all of it known when compiling
 //   band    row i spans lo_i = max(off_i, 0) ... hi_i = min(off_i + 2 band, nb - 1), off_i = c_i - band with c_i =
 //           align_band_center(i), and entry q of its row of the plane [na][width = 2 band + 1] is column off_i + q
@@ -504,6 +505,46 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
   if(lane == 0) pos[0] = 0.0f;                                        // row 0 is (0, 0) alone
 }
 
+// ---------------------------------------------------------------- P1: the pooled vectors of a coarse pass
+// k_pool_code: the mean of every `factor` consecutive rows of LLSM_GPU_CODE, per utterance (rule P1: llsm_gpu.h, DESIGN.md
+// section 34).  One thread per (coarse frame, column) of the output, numbered as the output is laid out, so adjacent lanes
+// read adjacent columns of the same rows -- every load of a row of CODE is coalesced, as is the store -- and a thread walks
+// its at most 64 rows in ascending order, one addition per row and one correctly rounded division: the order is the rule,
+// there is no cross-lane sum, no LDS and no atomic.  The rows are loaded eight at a time ahead of their additions: with one
+// load in flight per thread the kernel waited on latency (2.4 TB/s on 1 024 utterances of 1 154 frames at factor 16, 3.9
+// with eight: DESIGN.md section 34).  tab[u] = (first source frame, frames n, first coarse frame of the
+// output, side) of pooled utterance u, ascending in the third member, which starts at 0; a thread finds its utterance by
+// bisection over that member (the table of a call is a few KiB and stays in the caches).  side: 0 reads code_a, 1 code_b,
+// so one launch pools both batches of llsm_gpu_batch_align_pyramid.  The kernel reads CODE once and writes 1 / factor of it.
+#define POOL_NT 256
+#define POOL_U 8                                   // rows loaded ahead of their additions
+__global__ __launch_bounds__(POOL_NT) void k_pool_code(const float* __restrict__ code_a, const float* __restrict__ code_b,
+  const int4* __restrict__ tab, int n_tab, int dim, int factor, long long total, float* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * POOL_NT + threadIdx.x;
+  if(e >= total) return;
+  const long long kg = e / dim;                                       // the coarse frame of the whole output
+  const int c = (int)(e - kg * dim);
+  int lo = 0, hi = n_tab - 1;                                         // the last utterance that starts at or before kg
+  while(lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if(tab[mid].z <= kg) lo = mid; else hi = mid - 1;
+  }
+  const int4 u = tab[lo];
+  const int j0 = (int)(kg - u.z) * factor, m = min(factor, u.y - j0);  // (m >= 1: the table holds ceil(n / factor) frames)
+  const float* src = (u.w ? code_b : code_a) + ((size_t)u.x + j0) * dim + c;
+  float s = 0.0f;
+  int j = 0;
+  for(; j + POOL_U <= m; j += POOL_U) {                               // POOL_U loads in flight, then their additions in order
+    float v[POOL_U];
+#pragma unroll
+    for(int k = 0; k < POOL_U; k ++) v[k] = src[(size_t)(j + k) * dim];
+#pragma unroll
+    for(int k = 0; k < POOL_U; k ++) s = __fadd_rn(s, v[k]);
+  }
+  for(; j < m; j ++) s = __fadd_rn(s, src[(size_t)j * dim]);
+  out[e] = __fdiv_rn(s, (float)m);
+}
+
 // ---------------------------------------------------------------- launchers
 int launch_align_dist(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const int4* tiles, int n_tiles, float* plane, const int* center) {
   if(n_tiles == 0) return 0;
@@ -528,5 +569,14 @@ int launch_align_slope_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const 
   if(geo == ALIGN_GEO_LINE) LAUNCH("k_align_line_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_LINE>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
   else if(geo == ALIGN_GEO_BAND) LAUNCH("k_align_band_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_BAND>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
   else LAUNCH("k_align_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_FULL>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
+  return 0;
+}
+
+int launch_pool_code(LaunchCtx* P, const float* code_a, const float* code_b, const int4* tab, int n_tab, int dim, int factor,
+  long long coarse_frames, float* out) {
+  const long long total = coarse_frames * dim;
+  if(total == 0) return 0;
+  LAUNCH("k_pool_code", k_pool_code, dim3((unsigned)((total + POOL_NT - 1) / POOL_NT)), dim3(POOL_NT), 0, code_a, code_b, tab, n_tab,
+    dim, factor, total, out);
   return 0;
 }

@@ -109,7 +109,8 @@ template <class T> struct DevBuf {
 // The five alignment calls (align.cpp): two bits, inside a band and under the slope pattern, tell the first four apart, and
 // a third, ALIGN_AROUND, marks llsm_gpu_batch_align_around, whose band follows the caller's centre line and which is one call
 // for both patterns.  align_call(mode) indexes the batch's scratch sets and this table of the call's name and of its plane of
-// llsm_gpu_batch_debug_plane.
+// llsm_gpu_batch_debug_plane.  llsm_gpu_batch_align_pyramid runs two of these modes on scratch sets of its own, which this
+// table does not list: they have no plane.
 enum AlignMode { ALIGN_FULL = 0, ALIGN_BAND = 1, ALIGN_SLOPE = 2, ALIGN_AROUND = 4 };
 enum { ALIGN_CALLS = 5 };
 struct AlignCall { const char* name; int plane; };
@@ -219,6 +220,12 @@ struct llsm_gpu_batch {
     DevBuf<int> center;
     long long cells = 0;
   } align[ALIGN_CALLS];
+  // llsm_gpu_batch_align_pyramid: two sets of its own, [0] of the coarse pass and [1] of the fine pass, outside align[] and
+  // without an entry in kAlignCalls, so that no plane number of llsm_gpu_batch_debug_plane leads to them; the pooled vectors
+  // of both batches ([coarse frames of a's utterances, pair after pair | those of b's][dim]) and the table k_pool_code reads
+  // -- all grow-only
+  AlignScratch pyramid[2];
+  DevBuf<float> pyramid_code; DevBuf<int4> pyramid_tab;
   // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
   // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful
   // llsm_gpu_batch_select; sel_frames 0: no call yet), the back pointers (3 bits per state at bit 8 j, one word pair per

@@ -399,6 +399,12 @@ int launch_align_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float*
 // pairs[p].pad; row: two hand-over rows of nb floats per pair, out as above
 int launch_align_slope_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
   float* row, float* out, int cost0, const int* center);
+// P1 (llsm_gpu_batch_pool_code, llsm_gpu_batch_align_pyramid): the means of every `factor` (1 ... 64) consecutive rows of
+// CODE, the last group of an utterance over the rows it has.  tab[u] = (first source frame, frames, first coarse frame of
+// out, side: 0 reads code_a, 1 code_b) of pooled utterance u, n_tab >= 1 of them, the third member ascending from 0 and each
+// utterance ceil(frames / factor) coarse frames long; out: [coarse_frames][dim]
+int launch_pool_code(LaunchCtx* P, const float* code_a, const float* code_b, const int4* tab, int n_tab, int dim, int factor,
+  long long coarse_frames, float* out);
 
 // ---- unit selection (select.cpp, select_kernels.hip; rules S1 - S5 and C1 - C6: llsm_gpu.h)
 #define SELECT_K 8                                     // candidates kept per target frame
