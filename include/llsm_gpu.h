@@ -872,6 +872,68 @@ int  llsm_gpu_batch_align_pyramid(llsm_gpu_batch* a, const llsm_gpu_batch* b, in
        int* center_out /* sum_p na(p), layout of pos; may be NULL */,
        int* band_out   /* n_pairs; may be NULL */);
 
+/* ---- open-ended (subsequence) alignment: a query inside a take.  Every call above forces its path through both corners of
+ * the matrix, which is right for two trimmed renditions of one phrase and wrong for a phrase that lies somewhere in a long
+ * take, or for two takes whose leading and trailing silences differ.  Here pair p aligns the WHOLE of utterance utt_a[p] of
+ * a, the query of na frames, with SOME stretch of utterance utt_b[p] of b, the take of nb frames: the path may start on any
+ * column of row 0 and end on any column of the last row, at no cost.  The call gives where the query lies in the take
+ * (span), the path through it in the form llsm_gpu_batch_splice takes (pos), its cost, and the matching function along the
+ * take (last_row), from which a caller finds further occurrences.
+ * pos is sum_p na(p) floats as in llsm_gpu_batch_align; all entries of a pair lie in [begin, end] within [0, nb - 1], so they
+ * go into llsm_gpu_splice_map.pos_a or .pos_b with utt_b unchanged.  span (2 n_pairs ints; may be NULL): span[2 p] = begin
+ * and span[2 p + 1] = end, the first and the last frame of the take on the path, exact integers that never pass through a
+ * float (nb may exceed 2^24).  cost[p] (may be NULL) is the accumulated cost at the end.  last_row (sum_p nb(p) floats, pair
+ * after pair; may be NULL) is acc of the query's last row along the take.  The contract is that of llsm_gpu_batch_align --
+ * the same options and llsm_gpu_align_check, synchronous, a == b allowed, LLSM_GPU_CODE of both batches read and no array of
+ * either written, the lowest-F0 bound as it was; a refused call returns -1 with a message that starts with
+ * "llsm_gpu_batch_align_sub:", launches and allocates nothing and leaves all four outputs untouched.  The scratch set is the
+ * call's own, on a: planes 6, 9, 12, 13 and 14 and the scratch of every call above stay as they were.  A pair's result depends
+ * on its own two utterances, slope and the options only.
+ *
+ * The rules, per pair; float32, one rounding per operation, no contraction.
+ *  Q1. The region.  slope = 0: every cell; every pair with na, nb >= 1 is admissible.  slope = 1: row i holds the columns
+ *      lo_i = ceil(i / 2) ... hi_i = nb - 1, integers taken in 64-bit: the cells reached from some cell of row 0 under the
+ *      moves of L3; a pair is admissible when ceil((na - 1) / 2) <= nb - 1.  There is no upper cut: any cell of the last row
+ *      may end a path, and a cell that cannot reach the last row is computed and never lies on the path.  Every cell of the
+ *      region below row 0 has a predecessor inside it.  llsm_gpu_align_sub_rows fills lo and hi (na entries each; either
+ *      may be NULL, both NULL only asks whether the pair is admissible) and returns 0, or -1 with a message that names na, nb
+ *      and the bound that fails for na < 1, nb < 1, a slope that is neither 0 nor 1 or a pair that is not admissible.  Host
+ *      only, needs no device.
+ *  Q2. D[i][j] is rule D1 unchanged, for the whole matrix.
+ *  Q3. acc[0][j] = D[0][j] for every j of row 0: a path may start anywhere on it at no cost, and row 0 has no moves.  For
+ *      i >= 1 with slope = 0, D2 unchanged: column 0 is forced, acc[i][0] = (acc[i-1][0] + step_cost) + D[i][0], move 1;
+ *      elsewhere the diagonal comes first, then up, then left, and a later candidate replaces an earlier one only if it is
+ *      strictly smaller.  For i >= 1 with slope = 1, L3 unchanged over the region of Q1: a candidate exists only if its
+ *      predecessor cell lies in the region, which is decided by integer comparisons, never by values.
+ *  Q4. end is found by walking the last row's range with j ascending: it starts on lo_{na-1} and is replaced only by a
+ *      column whose acc is strictly smaller -- the smallest column of least acc; a NaN never replaces a candidate.
+ *      cost = acc[na-1][end].  last_row[j] = acc[na-1][j] inside the row's range, +infinity for j < lo_{na-1}.
+ *  Q5. The path runs from (na - 1, end) back along the moves until it reaches row 0; begin is its column there: at most
+ *      na - 1 + end moves, whatever the bits of LLSM_GPU_CODE.  pos follows D3 (slope = 0) or L4 (slope = 1), the cells
+ *      between the two ends of a move included.  The path stays inside the matrix under NaN, as in D2 and L3.
+ * It follows, and tests/test_align_sub_host.py and tests/test_gpu_align_sub.py hold it, that pos[0] == begin; that for finite
+ * features and slope = 0 pos[na - 1] == end (a left move into the end cell would make its left neighbour no larger); that
+ * for slope = 1 pos[na - 1] is end or end - 0.5 and pos obeys the step bounds of L4; and that for finite features cost is
+ * never above the cost of llsm_gpu_batch_align on the same pair as float32 values -- with slope = 1 that of
+ * llsm_gpu_batch_align_slope, where that call admits the pair: every acc here is <= the acc there by induction, as rounded
+ * addition and minimum are monotone, and the end is a minimum over a row that contains the corner.
+ *
+ * Refused, every check before anything is allocated: everything llsm_gpu_batch_align refuses, by the same code and in the
+ * same order, the cap of 2^28 cells on the sum of na x nb among it; then a slope that is neither 0 nor 1; then, with
+ * slope = 1, a pair that is not admissible (the message names the pair, na and nb).  n_pairs == 0 returns 0.
+ * llsm_gpu_batch_align_sub_plane returns the distance planes of the last successful llsm_gpu_batch_align_sub with a as a,
+ * pair after pair, each [na][nb], laid out as plane 12 of llsm_gpu_batch_debug_plane: the number of floats, with dst == NULL
+ * the size only, -1 with a message for a destination of fewer than that many floats (cap) and until such a call has run.  It
+ * is a call of its own: the planes have no number in llsm_gpu_batch_debug_plane.
+ * Known limits: one wavefront walks a pair; the whole matrix is computed, so the cap holds a 200-frame query to a take of
+ * 1.3 million frames in all; there is no band; one occurrence is returned per pair -- last_row is there for the others. */
+int  llsm_gpu_align_sub_rows(int na, int nb, int slope, int* lo, int* hi);   /* host only; na entries each, both may be NULL */
+int  llsm_gpu_batch_align_sub(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+       int slope, const llsm_gpu_align_options* opt /* NULL: defaults */, FP_TYPE* pos,
+       int* span /* 2 n_pairs: begin, end of each pair; may be NULL */, FP_TYPE* cost /* may be NULL */,
+       FP_TYPE* last_row /* sum of nb floats, pair after pair; may be NULL */);
+long long llsm_gpu_batch_align_sub_plane(llsm_gpu_batch* a, float* dst, long long cap);
+
 /* ---- unit selection: for every frame of a target batch the frame of a bank that renders it, on the device.  A frame-level
  * search -- the K = 8 nearest bank frames of every target frame under the distance of llsm_gpu_batch_align, from anywhere
  * in the bank -- and then one minimum-cost path per target utterance through these candidates, with a join cost between

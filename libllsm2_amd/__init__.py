@@ -162,6 +162,7 @@ llsm_gpu_batch_align_slope llsm_gpu_align_slope_rows
 llsm_gpu_batch_align_band_slope llsm_gpu_align_band_slope_min llsm_gpu_align_band_slope_rows
 llsm_gpu_batch_align_around llsm_gpu_align_around_rows llsm_gpu_align_around_min llsm_gpu_align_center_line
 llsm_gpu_pool_frames llsm_gpu_batch_pool_code llsm_gpu_batch_align_pyramid
+llsm_gpu_align_sub_rows llsm_gpu_batch_align_sub llsm_gpu_batch_align_sub_plane
 llsm_gpu_select_default_options llsm_gpu_select_check llsm_gpu_batch_select llsm_gpu_batch_select_chain
 """.split()
 
@@ -284,6 +285,13 @@ def load():
         L.llsm_gpu_batch_pool_code.argtypes = [vp, C.c_int, C.c_int, P_int, P_fp]
         L.llsm_gpu_batch_align_pyramid.argtypes = [vp, vp, C.c_int, P_int, P_int, C.c_int, C.c_int, C.c_int, C.POINTER(AlignOptions),
                                                    P_fp, P_fp, P_int, P_int]
+    except AttributeError:
+        if "LLSM_AMD_LIB" not in os.environ:
+            raise
+    try:                                                 # (as above: an experiment build of an earlier commit lacks the open-ended alignment)
+        L.llsm_gpu_align_sub_rows.argtypes = [C.c_int, C.c_int, C.c_int, P_int, P_int]
+        L.llsm_gpu_batch_align_sub.argtypes = [vp, vp, C.c_int, P_int, P_int, C.c_int, C.POINTER(AlignOptions), P_fp, P_int, P_fp, P_fp]
+        L.llsm_gpu_batch_align_sub_plane.argtypes = [vp, vp, C.c_longlong]; L.llsm_gpu_batch_align_sub_plane.restype = C.c_longlong
     except AttributeError:
         if "LLSM_AMD_LIB" not in os.environ:
             raise
@@ -503,6 +511,16 @@ def align_slope_rows(na, nb):
     lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
     _check(load().llsm_gpu_align_slope_rows(int(na), int(nb), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
            "align_slope_rows")
+    return lo, hi
+
+
+def align_sub_rows(na, nb, slope=False):
+    """(lo, hi): the column range of every row of a query of na frames inside a take of nb with free ends, int32 [na] each:
+    every column, or with slope ceil(i / 2) ... nb - 1 (llsm_gpu_align_sub_rows, rule Q1 of llsm_gpu_batch_align_sub); a
+    pair that is not admissible is refused"""
+    lo = np.zeros(max(int(na), 0), np.int32); hi = np.zeros(max(int(na), 0), np.int32)
+    _check(load().llsm_gpu_align_sub_rows(int(na), int(nb), int(slope), lo.ctypes.data_as(P_int), hi.ctypes.data_as(P_int)),
+           "align_sub_rows")
     return lo, hi
 
 
@@ -990,6 +1008,41 @@ class Batch:
                "align_pyramid")
         cut = np.cumsum(na)[:-1]
         return (np.split(pos, cut) if len(ua) else []), cost, (np.split(center, cut) if len(ua) else []), band
+
+    def align_sub(self, other, utt_a, utt_b, slope=False, last_row=False, **options):
+        """open-ended alignment (llsm_gpu_batch_align_sub): the whole of utterance utt_a[p] of this batch, the query, against
+        some stretch of utterance utt_b[p] of `other`, the take; the path starts and ends anywhere along the take.  slope:
+        the moves of align_slope instead of those of align.  Returns (pos, span, cost): pos as align returns it, span int32
+        [n_pairs][2], the first and the last frame of the take on each path, and the float32 array of the path costs; with
+        last_row also a list with acc of the query's last row along the take, one float32 array [nb] per pair"""
+        o = make_align_options(**options)
+        ua, na = self._frames_of(utt_a)
+        ub, nb = other._frames_of(utt_b)
+        assert ua.shape == ub.shape, (ua.shape, ub.shape)
+        pos = np.zeros(int(na.sum()), np.float32); cost = np.zeros(len(ua), np.float32)
+        span = np.zeros((len(ua), 2), np.int32)
+        rows = np.zeros(int(nb.sum()) if last_row else 0, np.float32)
+        _check(self.L.llsm_gpu_batch_align_sub(self.h, other.h, len(ua), ua.ctypes.data_as(P_int), ub.ctypes.data_as(P_int),
+                                               int(slope), C.byref(o), pos.ctypes.data_as(P_fp), span.ctypes.data_as(P_int),
+                                               cost.ctypes.data_as(P_fp), rows.ctypes.data_as(P_fp) if last_row else None),
+               "align_sub")
+        self._sub_shapes = [(int(n), int(m)) for n, m in zip(na, nb)]  # (of the planes the call has just rewritten)
+        out = (np.split(pos, np.cumsum(na)[:-1]) if len(ua) else []), span, cost
+        return out + ((np.split(rows, np.cumsum(nb)[:-1]) if len(ua) else []),) if last_row else out
+
+    def align_sub_planes(self):
+        """the distance planes of the last successful align_sub with this batch as the query side
+        (llsm_gpu_batch_align_sub_plane), cut per pair: a list with one float32 array [na][nb] per pair of that call"""
+        n = self.L.llsm_gpu_batch_align_sub_plane(self.h, None, 0)
+        if n < 0:
+            raise LlsmError("align_sub_planes: " + self.L.llsm_gpu_last_error().decode())
+        a = np.zeros(n, np.float32)
+        if self.L.llsm_gpu_batch_align_sub_plane(self.h, a.ctypes.data, n) != n:
+            raise LlsmError("align_sub_planes: " + self.L.llsm_gpu_last_error().decode())
+        shapes = getattr(self, "_sub_shapes", [])
+        assert n == sum(r * c for r, c in shapes), (n, shapes)
+        cut = np.cumsum([r * c for r, c in shapes])[:-1]
+        return [x.reshape(sh) for x, sh in zip(np.split(a, cut), shapes)]
 
     # ---- unit selection (llsm_gpu.h): LLSM_GPU_CODE of this batch and of a bank -> the index lists splice renders
     def select(self, bank, opt=None, **options):

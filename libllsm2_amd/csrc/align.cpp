@@ -24,6 +24,13 @@
 //                                    section 30: the kernels of the banded calls instantiated for ALIGN_GEO_LINE, which read
 //                                    the centre of a row from a table), with scratch of its own
 //
+//   llsm_gpu_align_sub_rows          host only: whether a query is admissible inside a take with free ends, and the column
+//                                    range of every row (rule Q1)
+//   llsm_gpu_batch_align_sub         a query inside a take: the whole planes, a path that starts anywhere on row 0 and ends
+//                                    anywhere on the last row, under either pattern (rules Q1 - Q5, DESIGN.md section 35: the
+//                                    two path kernels instantiated with free ends), with scratch of its own; its planes
+//                                    through llsm_gpu_batch_align_sub_plane
+//
 //   llsm_gpu_pool_frames            host only: the coarse frames of an utterance under a pooling factor (rule P1)
 //   llsm_gpu_batch_pool_code        the means of every `factor` consecutive rows of LLSM_GPU_CODE of the listed utterances
 //                                    (rule P1, DESIGN.md section 34: k_pool_code) on the host
@@ -213,13 +220,15 @@ int strip_span(bool banded, const AlignPair& q, const int* line, int i0, int& jl
 // which each kernel finds the same way.  Without the slope pattern the window is the span within the matrix.  Under it a
 // strip that has a successor takes one step more, as the first row of the successor may be entered past column jhi, and
 // the window is, by rule L1, lo of the first row and hi of the last (neither decreases with the row), or inside a band, by
-// rule K1, the least lo and the largest hi of the non-empty rows among the pair's rows of the region, `region`.  Around a
+// rule K1, the least lo and the largest hi of the non-empty rows among the pair's rows of the region, `region`; with free
+// ends, by rule Q1, lo of the first row and nb - 1.  Around a
 // line c does not decrease either, and a connected band has c_{i+1} - c_i <= 2 band + 1, so the window of a strip is at most
 // 63 (2 band + 1) + 2 band + 1 columns.
 int strip_steps(int mode, const AlignPair& q, const int* line, int i0, const int2* region) {
   int jlo, jhi, unused;
   const int i1 = strip_span(mode & ALIGN_BAND, q, line, i0, jlo, jhi);
   if(! (mode & ALIGN_SLOPE)) { jlo = std::max(jlo, 0); jhi = std::min(jhi, q.nb - 1); }
+  else if(mode & ALIGN_SUB) align_sub_row(i0, q.nb, jlo, jhi);       // rule Q1: lo of the first row, and every row ends on nb - 1
   else if(mode & ALIGN_BAND) {
     jlo = q.nb - 1; jhi = 0;
     for(int i = i0; i <= i1; i ++)
@@ -250,6 +259,12 @@ std::string pair_fault(const AlignSide& a, const AlignSide& b, int p, int ua, in
   if(a.nfrm[ua] <= 0 || b.nfrm[ub] <= 0) return pair_of(p) + "an utterance without frames";
   return "";
 }
+// rule Q1: empty if a query of na frames is admissible in a take of nb under the slope pattern with free ends (na, nb >= 1),
+// else the bound that fails
+std::string sub_bound(int na, int nb) {
+  const long long need = (long long)na / 2, rb = (long long)nb - 1;  // ceil((na - 1) / 2)
+  return need > rb ? "ceil((na - 1) / 2) = " + std::to_string(need) + " exceeds nb - 1 = " + std::to_string(rb) : "";
+}
 // empty, or rule L1's refusal of pair p in the words of llsm_gpu_batch_align_slope
 std::string inadmissible(int p, int na, int nb) {
   const std::string bound = slope_bound(na, nb);
@@ -276,10 +291,12 @@ int align_head(const llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, co
 // read and the planes hold the whole matrix of every pair.  The checks run in the order in which the calls have always made
 // them.  ALIGN_AROUND comes with ALIGN_BAND, with the centre lines of all pairs in `center` and with the caller's `slope` as
 // `pattern`, which becomes the ALIGN_SLOPE bit once it has been checked; that call makes its checks in the order of its
-// header, each over all pairs before the next.
+// header, each over all pairs before the next.  ALIGN_SUB (rules Q1 - Q5) comes alone, with the caller's slope as `pattern`
+// too, checked after everything llsm_gpu_batch_align refuses, its cap included; span and last_row are that call's further
+// outputs and NULL in every other.
 int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_b, int mode, int pattern, const int* center,
-  const int* band, FP_TYPE* pos, FP_TYPE* cost) {
-  const bool banded = mode & ALIGN_BAND, around = mode & ALIGN_AROUND;
+  const int* band, FP_TYPE* pos, FP_TYPE* cost, int* span = nullptr, FP_TYPE* last_row = nullptr) {
+  const bool banded = mode & ALIGN_BAND, around = mode & ALIGN_AROUND, sub = mode & ALIGN_SUB;
   const char* who = J.who;
   const AlignSide& a = J.a; const AlignSide& b = J.b;
   const llsm_gpu_align_options& o = J.o;
@@ -305,6 +322,8 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
       at += na;
     }
   }
+  // (with free ends the pattern is checked below, behind the cap; a slope that is refused there sizes nothing that is used)
+  if(sub && pattern == 1) mode |= ALIGN_SLOPE;
   const bool slope = mode & ALIGN_SLOPE, bslope = banded && slope;
   // the cells of pair r's plane as far as its utterances exist; a band plane is held below 2^61 so that the total of any
   // list fits 64 bits
@@ -317,7 +336,7 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
   };
   std::vector<int2> table, region;                                  // rule K1: the rows of the region of all pairs, and of one
   std::vector<AlignPair> pairs((size_t)n_pairs);
-  long long cells = 0, rows = 0, frames = 0, steps = 0, n_tiles = 0;
+  long long cells = 0, rows = 0, frames = 0, steps = 0, n_tiles = 0, takes = 0;
   bool over = false;                                                // around a line: the cap is passed, and refused after the last band
   for(int p = 0; p < n_pairs; p ++) {
     const int ua = utt_a[p], ub = utt_b[p], bd = banded ? band[p] : 0;
@@ -331,7 +350,7 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
       return refuse(pair_of(p) + "a band of " + std::to_string(bd) + " is not connected for " + std::to_string(na) + " x " +
         std::to_string(nb) + " frames: " + (around ? "llsm_gpu_align_around_min is " : "llsm_gpu_align_band_min is ") +
         std::to_string(least), who);
-    if(slope) {
+    if(slope && ! sub) {
       const std::string why = inadmissible(p, na, nb);
       if(! why.empty()) return refuse(why, who);
     }
@@ -350,6 +369,7 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
     q.a0 = a.frm_off[ua]; q.na = na; q.b0 = b.frm_off[ub]; q.nb = nb;
     q.cell0 = (int)cells; q.row0 = (int)rows; q.pos0 = (int)frames; q.band = bd; q.mv0 = steps;
     q.pad = as_before ? pairs[p - 1].pad : (int)table.size();       // where the pair's rows of the region start
+    if(sub) q.pad = (int)takes;                                     // ... or, with free ends, its row of the matching function
     if(bslope && ! as_before) table.insert(table.end(), region.begin(), region.end());
     cells += plane_cells(p);                                        // (checked below: the offsets above are only used if it fits)
     if(cells > kMaxCells && around) { over = true; frames += na; continue; }
@@ -365,11 +385,19 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
       n_tiles += (jhi - tile_floor(jlo)) / ALIGN_TILE + 1;
       q.steps = std::max(q.steps, strip_steps(mode, q, line, i0, table.data() + q.pad));
     }
-    rows += slope ? 2ll * nb : nb; frames += na;
+    rows += slope ? 2ll * nb : nb; frames += na; takes += nb;
     steps += (long long)((na + 63) / 64) * q.steps;
   }
   if(over)
     return refuse("the band planes hold " + std::to_string(cells) + " cells, more than 2^28 = " + std::to_string(kMaxCells), who);
+  if(sub) {                                                         // behind the cap: the pattern, then rule Q1 pair by pair
+    if(pattern != 0 && pattern != 1) return refuse("slope = " + std::to_string(pattern) + " is neither 0 nor 1", who);
+    for(int p = 0; p < n_pairs && pattern; p ++) {
+      const std::string bound = sub_bound(pairs[p].na, pairs[p].nb);
+      if(! bound.empty())
+        return refuse(pair_of(p) + std::to_string(pairs[p].na) + " x " + std::to_string(pairs[p].nb) + " frames are not admissible: " + bound, who);
+    }
+  }
   // accepted: from here on this pass's scratch set changes (and those of the other calls, their planes among them, do not)
   llsm_gpu_batch::AlignScratch& sc = *J.sc;
   std::vector<int4> tiles; tiles.reserve((size_t)n_tiles);
@@ -382,7 +410,7 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
   const size_t n_out = (size_t)frames + (size_t)n_pairs;
   if(sc.plane.alloc((size_t)cells) || sc.row.alloc((size_t)rows) || sc.out.alloc(n_out) || sc.moves.alloc((size_t)steps) ||
      sc.pairs.alloc(pairs.size()) || sc.tiles.alloc(tiles.size()) || sc.region.alloc(table.size()) ||
-     (around && sc.center.alloc((size_t)frames))) return -1;
+     (around && sc.center.alloc((size_t)frames)) || (sub && (sc.last.alloc((size_t)takes) || sc.span.alloc((size_t)2 * n_pairs)))) return -1;
   sc.cells = 0;                                                     // the planes are being rewritten
   LaunchCtx* P = & J.owner -> ctx -> lc;
   // (pageable sources: the copies have left the vectors when the calls return, and run in stream order)
@@ -398,15 +426,21 @@ int align_pass(const AlignJob& J, int n_pairs, const int* utt_a, const int* utt_
   d.pairs = sc.pairs.p; d.n_pairs = n_pairs;
   const int* lines = around ? sc.center.p : nullptr;
   int rc = launch_align_dist(P, geo, d, sc.tiles.p, (int)tiles.size(), sc.plane.p, lines);
-  if(! rc) rc = slope ? launch_align_slope_dtw(P, geo, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames, lines)
+  if(! rc) rc = sub ? launch_align_sub_dtw(P, slope, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames, sc.last.p, sc.span.p) :
+                slope ? launch_align_slope_dtw(P, geo, d, sc.plane.p, sc.region.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames, lines)
                       : launch_align_dtw(P, geo, d, sc.plane.p, sc.moves.p, sc.row.p, sc.out.p, (int)frames, lines);
   if(rc) return refuse(std::string("launch failed: ") + hipGetErrorString((hipError_t)rc), who);
-  // into memory of our own first: a failed copy leaves pos and cost untouched
-  std::vector<float> host(n_out);
+  // into memory of our own first: a failed copy leaves the outputs untouched
+  std::vector<float> host(n_out), host_last(sub && last_row ? (size_t)takes : 0);
+  std::vector<int> host_span(sub && span ? (size_t)2 * n_pairs : 0);
   HIP_OK(hipMemcpyAsync(host.data(), sc.out.p, n_out * sizeof(float), hipMemcpyDeviceToHost, P -> stream));
+  if(! host_last.empty()) HIP_OK(hipMemcpyAsync(host_last.data(), sc.last.p, host_last.size() * sizeof(float), hipMemcpyDeviceToHost, P -> stream));
+  if(! host_span.empty()) HIP_OK(hipMemcpyAsync(host_span.data(), sc.span.p, host_span.size() * sizeof(int), hipMemcpyDeviceToHost, P -> stream));
   HIP_OK(hipStreamSynchronize(P -> stream));
   std::copy(host.begin(), host.begin() + frames, pos);
   if(cost) std::copy(host.begin() + frames, host.end(), cost);
+  if(span) std::copy(host_span.begin(), host_span.end(), span);
+  if(last_row) std::copy(host_last.begin(), host_last.end(), last_row);
   sc.cells = cells;
   return 0;
 }
@@ -425,6 +459,49 @@ int align_run(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int
 extern "C" int llsm_gpu_batch_align(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a,
   const int* utt_b, const llsm_gpu_align_options* opt, FP_TYPE* pos, FP_TYPE* cost) {
   return align_run(a, b, n_pairs, utt_a, utt_b, ALIGN_FULL, 0, nullptr, nullptr, opt, pos, cost);
+}
+
+// ---------------------------------------------------------------- a query inside a take: free ends (rules Q1 - Q5)
+namespace { const char* const kSub = "llsm_gpu_batch_align_sub"; }
+
+extern "C" int llsm_gpu_align_sub_rows(int na, int nb, int slope, int* lo, int* hi) {
+  const char* who = "llsm_gpu_align_sub_rows";
+  if(na < 1 || nb < 1) return refuse("na < 1 or nb < 1 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ")", who);
+  if(slope != 0 && slope != 1)
+    return refuse("slope = " + std::to_string(slope) + " is neither 0 nor 1 (na = " + std::to_string(na) + ", nb = " + std::to_string(nb) + ")", who);
+  const std::string bound = slope ? sub_bound(na, nb) : "";
+  if(! bound.empty()) return refuse(std::to_string(na) + " x " + std::to_string(nb) + " frames are not admissible: " + bound, who);
+  for(int i = 0, l = 0, h = nb - 1; i < na && (lo || hi); i ++) {
+    if(slope) align_sub_row(i, nb, l, h);
+    if(lo) lo[i] = l;
+    if(hi) hi[i] = h;
+  }
+  return 0;
+}
+
+extern "C" int llsm_gpu_batch_align_sub(llsm_gpu_batch* a, const llsm_gpu_batch* b, int n_pairs, const int* utt_a, const int* utt_b,
+  int slope, const llsm_gpu_align_options* opt, FP_TYPE* pos, int* span, FP_TYPE* cost, FP_TYPE* last_row) {
+  llsm_gpu_align_options o;
+  if(align_head(a, b, n_pairs, opt, kSub, o)) return -1;
+  const AlignJob J{a, side_of(a), side_of(b), a -> coder_os + a -> coder_ob + 3, o, & a -> align_sub, kSub};
+  return align_pass(J, n_pairs, utt_a, utt_b, ALIGN_SUB, slope, nullptr, nullptr, pos, cost, span, last_row);
+}
+
+// the distance planes of the last successful llsm_gpu_batch_align_sub with this batch as a, pair after pair, each [na][nb];
+// dst == NULL: only the size
+extern "C" long long llsm_gpu_batch_align_sub_plane(llsm_gpu_batch* a, float* dst, long long cap) {
+  const char* who = "llsm_gpu_batch_align_sub_plane";
+  if(! a) { refuse("NULL batch", who); return -1; }
+  const long long n = a -> align_sub.cells;
+  if(n == 0 || ! a -> align_sub.plane.p) { refuse(std::string("no ") + kSub + " has run on this batch", who); return -1; }
+  if(dst) {
+    if(cap < n) { refuse("destination too small", who); return -1; }
+    if(hipStreamSynchronize(a -> ctx -> lc.stream) != hipSuccess ||
+       hipMemcpy(dst, a -> align_sub.plane.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+      refuse("copy failed", who); return -1;
+    }
+  }
+  return n;
 }
 
 // ---------------------------------------------------------------- inside a diagonal band (rules B1 - B4)

@@ -4,7 +4,10 @@
 // band ones); the path kernel of the last two, k_align_slope_dtw_t, is described above it; and llsm_gpu_batch_align_around
 // (rules A1 - A3, section 30), which runs the band instantiations of all three around a centre line of the caller's; and
 // k_pool_code (rule P1, section 34), the pooled vectors of llsm_gpu_batch_pool_code and of the coarse pass of
-// llsm_gpu_batch_align_pyramid, which is otherwise made of the kernels above; host side: align.cpp.  Three kernel templates, each instantiated for the three geometries (AlignGeo: kernels.h):
+// llsm_gpu_batch_align_pyramid, which is otherwise made of the kernels above; and llsm_gpu_batch_align_sub (rules Q1 - Q5,
+// section 35), whose planes are k_align_dist_t's full ones and whose paths are the two path kernels of the full geometry with
+// free ends (k_align_sub_dtw, k_align_sub_slope_dtw: the note above k_align_dtw_t); host side: align.cpp.  Three kernel
+// templates, each instantiated for the three geometries (AlignGeo: kernels.h):
 //   full    row i spans columns 0 ... nb - 1 and is stored as it is: off = 0, width = nb, all of it known when compiling
 //   band    row i spans lo_i = max(off_i, 0) ... hi_i = min(off_i + 2 band, nb - 1), off_i = c_i - band with c_i =
 //           align_band_center(i), and entry q of its row of the plane [na][width = 2 band + 1] is column off_i + q
@@ -197,10 +200,33 @@ DEV void dtw_load(DtwBlock& b, const float* __restrict__ drow, const float* hand
   }
 }
 
-template <int GEO>
+// The free ends of llsm_gpu_batch_align_sub (rules Q1, Q3 - Q5) are one more template parameter of the two path kernels, a
+// pack SUB that is empty -- the kernels as they were, argument for argument -- or (float* last_rows, int* span): acc of every
+// pair's last row (pair p's nb floats from float pairs[p].pad) and {begin, end} of every pair.  OPEN = the pack is not empty.
+// With the empty pack the six instantiations compile to the instructions they had before the parameter (72 / 74 / 72 and 94 /
+// 96 / 96 VGPRs, no scratch: DESIGN.md section 35); a body shared through a device function did not keep them.  Under
+// `if constexpr` OPEN changes four things, for the full geometry only:
+//   row 0      takes acc = D on every column, not on (0, 0) alone, and the plain kernel's forced left move on row 0 goes;
+//              column 0 stays forced.  What is stored as the move of a cell of row 0 is never read.
+//   the rows   of the slope kernel are Q1's (align_sub_row: ceil(i / 2) ... nb - 1), not L1's; the three ranges follow from
+//              them as they do from L1's, and the strip window is [lo of the first row, nb - 1].  Row 64 s starts on 32 s and
+//              row 64 s - 1 on 32 s too, so lane 0 still meets no cell of the region left of wlo.
+//   the end    lane (na - 1) & 63 of the last strip keeps (best, end) under Q4 while it walks its row -- it starts on the
+//              row's first column and takes a later one only if acc is strictly smaller -- and stores acc[na-1][j] to the
+//              pair's row of the matching function: one lane, one compare and one word a step, beside the hand-over store.
+//              After the loop end goes to the wavefront as a scalar and is written with the cost.
+//   the walk   starts on (na - 1, end) and stops on reaching row 0, whose column is begin; begin and end go into span as ints.
+DEV float* sub_last_rows() { return nullptr; }
+DEV float* sub_last_rows(float* last_rows, int*) { return last_rows; }
+DEV int* sub_span() { return nullptr; }
+DEV int* sub_span(float*, int* span) { return span; }
+
+template <int GEO, class... SUB>
 __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* __restrict__ plane, uint4* __restrict__ moves,
-  float* __restrict__ hand_rows, float* __restrict__ out, int cost0, const int* __restrict__ center) {
-  constexpr bool BAND = GEO != ALIGN_GEO_FULL;
+  float* __restrict__ hand_rows, float* __restrict__ out, int cost0, const int* __restrict__ center, SUB... sub) {
+  constexpr bool BAND = GEO != ALIGN_GEO_FULL, OPEN = sizeof...(SUB) != 0;
+  float* const last_rows = sub_last_rows(sub...); int* const span = sub_span(sub...);
+  static_assert(! OPEN || ! BAND, "the free ends are instantiated for the full geometry only");
   const int lane = threadIdx.x;
   const AlignPair p = d.pairs[blockIdx.x];
   const int na = p.na, nb = p.nb, band = p.band, width = BAND ? 2 * band + 1 : nb;
@@ -211,8 +237,13 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
   const float step = d.step_cost;
   const int nstrips = (na + WAVE - 1) / WAVE;
   float v = 0.0f;                                                     // acc of this lane's last cell
+  // OPEN (rule Q4): the lane that owns row na - 1 keeps the least acc of its row and its smallest column while it walks the
+  // row in the last strip, and leaves the row itself in the pair's row of the matching function
+  float* lastrow = OPEN ? last_rows + (size_t)p.pad : nullptr;
+  float best = 0.0f; int end = 0;
   for(int s = 0; s < nstrips; s ++) {
     const int i = s * WAVE + lane, rows = min(WAVE, na - s * WAVE);
+    const bool ender = OPEN && lane == ((na - 1) & (WAVE - 1)) && s + 1 == nstrips;
     // BAND: the ranges of this lane's row and of the row above; an empty range (1, 0) where there is no such row
     int off = 0, lo = 1, hi = 0, plo = 1, phi = 0;
     if constexpr(BAND) if(i < na) {
@@ -250,13 +281,17 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
         } else {                                                      // D2, which is B3 where every row spans 0 ... nb - 1
           if(up < m) { m = up; move = 1; }
           if(lf < m) { m = lf; move = 2; }
-          if(i == 0) { m = lf; move = 2; }                            // the borders are forced, not compared
+          if constexpr(! OPEN) if(i == 0) { m = lf; move = 2; }       // the borders are forced, not compared
           if(j == 0) { m = up; move = 1; }
         }
         float acc = __fadd_rn(m, cur.d[k]);
-        if(i == 0 && j == 0) { acc = cur.d[k]; move = 0; }
+        if(OPEN ? i == 0 : i == 0 && j == 0) { acc = cur.d[k]; move = 0; }   // Q3: a path starts anywhere on row 0, at no cost
         diag = up_raw;
         if(on) v = acc;
+        if constexpr(OPEN) if(on && ender) {
+          lastrow[j] = acc;
+          if(j == 0 || acc < best) { best = acc; end = j; }           // strictly smaller: the smallest column of least acc
+        }
         const unsigned long long b0 = __ballot(on && (move & 1)), b1 = __ballot(on && (move & 2));
         if((t & (WAVE - 1)) == lane) { w0 = b0; w1 = b1; }
         if(((t & (WAVE - 1)) == WAVE - 1 || t == nsteps - 1) && lane <= (t & (WAVE - 1)))
@@ -268,15 +303,18 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
     __threadfence();                                                  // the hand-over row and the masks, before other lanes read them
   }
   const int last = (na - 1) & (WAVE - 1);
-  if(lane == last) out[cost0 + blockIdx.x] = v;                       // acc[na-1][nb-1]: the last cell of the last row's range
+  if constexpr(OPEN) {
+    if(lane == last) out[cost0 + blockIdx.x] = best;
+    end = __builtin_amdgcn_readlane(end, last);                       // (to every lane, as a scalar: the walk below is one)
+  } else if(lane == last) out[cost0 + blockIdx.x] = v;                // acc[na-1][nb-1]: the last cell of the last row's range
 
-  // D3 / B4: back along the moves
+  // D3 / B4: back along the moves; Q5: from (na - 1, end) until row 0 is reached
   float* pos = out + (size_t)p.pos0;
-  int i = na - 1, j = nb - 1, hi = j;
+  int i = na - 1, j = OPEN ? end : nb - 1, hi = j;
   int cur_s = -1, cur_b = -1, wlo = 0;
   uint4 w = make_uint4(0, 0, 0, 0);
   for(int guard = na + nb; guard > 0; guard --) {
-    if(i == 0 && j == 0) break;
+    if(OPEN ? i == 0 : i == 0 && j == 0) break;
     const int s = i >> 6, l = i & (WAVE - 1);
     if constexpr(BAND) if(s != cur_s) wlo = max(align_center<GEO>(center, p, s * WAVE) - band, 0);
     const int t = j - wlo + l, blk = t & ~(WAVE - 1);
@@ -299,7 +337,8 @@ __global__ __launch_bounds__(WAVE) void k_align_dtw_t(AlignDev d, const float* _
       hi = j;
     }
   }
-  if(lane == 0) pos[0] = __fmul_rn((float)(0 + hi), 0.5f);
+  if(lane == 0) pos[0] = __fmul_rn((float)((OPEN ? j : 0) + hi), 0.5f);
+  if constexpr(OPEN) if(lane == 0) { span[2 * blockIdx.x] = j; span[2 * blockIdx.x + 1] = end; }
 }
 
 // ---------------------------------------------------------------- L3 - L4 / K3 - K4: the path under the slope pattern
@@ -369,11 +408,13 @@ DEV void band_slope_window(int lo, int hi, int nb, int& wlo, int& whi) {
   for(int o = WAVE / 2; o > 0; o >>= 1) { wlo = min(wlo, __shfl_xor(wlo, o)); whi = max(whi, __shfl_xor(whi, o)); }
 }
 
-template <int GEO>
+template <int GEO, class... SUB>
 __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const float* __restrict__ plane,
   const int2* __restrict__ region, uint4* __restrict__ moves, float* hand_rows, float* __restrict__ out, int cost0,
-  const int* __restrict__ center) {
-  constexpr bool BAND = GEO != ALIGN_GEO_FULL;
+  const int* __restrict__ center, SUB... sub) {
+  constexpr bool BAND = GEO != ALIGN_GEO_FULL, OPEN = sizeof...(SUB) != 0;
+  float* const last_rows = sub_last_rows(sub...); int* const span = sub_span(sub...);
+  static_assert(! OPEN || ! BAND, "the free ends are instantiated for the full geometry only");
   const int lane = threadIdx.x;
   const AlignPair p = d.pairs[blockIdx.x];
   const int na = p.na, nb = p.nb, band = p.band, width = BAND ? 2 * band + 1 : nb;
@@ -386,9 +427,18 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
   const float step = d.step_cost;
   const int nstrips = (na + WAVE - 1) / WAVE;
   float v = 0.0f;                                                     // acc of this lane's last cell
+  // OPEN (rule Q4), as in align_dtw; the row of the matching function is +infinity left of the last row's range
+  float* lastrow = OPEN ? last_rows + (size_t)p.pad : nullptr;
+  float best = 0.0f; int end = 0;
+  if constexpr(OPEN) {
+    int l, h;
+    align_sub_row((long long)na - 1, nb, l, h);
+    for(int j = lane; j < min(l, nb); j += WAVE) lastrow[j] = __builtin_huge_valf();
+  }
   for(int s = 0; s < nstrips; s ++) {
     const int i = s * WAVE + lane, rows = min(WAVE, na - s * WAVE);
     const bool more = s + 1 < nstrips;
+    const bool ender = OPEN && lane == ((na - 1) & (WAVE - 1)) && ! more;
     // the range of this lane's row of the region, and the columns j for which move 0, 1 and 2 have a candidate: [a0, b0],
     // [a1, b1], and j - 1 in [c0, b0]; empty ranges (1, 0) where there is no such row
     int off = 0, lo = 1, hi = 0, a0 = 1, b0 = 0, a1 = 1, b1 = 0, c0 = 1;
@@ -407,6 +457,13 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
           a1 = max(r2.x + 1, max(cp - band, 0)); b1 = min(r2.y + 1, min(cp + band, nb - 1));
         }
       }
+    } else if constexpr(OPEN) {                                       // Q1: the cells reached from row 0, no upper cut
+      if(i < na) {
+        align_sub_row(i, nb, lo, hi);
+        if(i >= 1) { align_sub_row(i - 1, nb, a0, b0); a0 ++; b0 ++; }
+        if(i >= 2) { align_sub_row(i - 2, nb, a1, b1); a1 ++; b1 ++; }
+      }
+      c0 = a0;
     } else {
       if(i < na) {
         align_slope_row(i, na, nb, lo, hi);
@@ -448,10 +505,14 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
         if(has0 && has1 && qi < m) { m = qi; move = 1; }              // ... and a later one only if strictly smaller
         if((has0 || has1) && has2 && qo < m) { m = qo; move = 2; }
         float acc = __fadd_rn(m, cur.d[k]);
-        if(i == 0 && j == 0) { acc = cur.d[k]; move = 0; }
+        if(OPEN ? i == 0 : i == 0 && j == 0) { acc = cur.d[k]; move = 0; }   // Q3: a path starts anywhere on row 0, at no cost
         qo = __fadd_rn(__fadd_rn(diag, cur.d[k]), step);              // through (i, j) from (i - 1, j - 1)
         diag = up_raw;
         if(on) v = acc;
+        if constexpr(OPEN) if(on && ender) {
+          lastrow[j] = acc;
+          if(j == lo || acc < best) { best = acc; end = j; }          // strictly smaller: the smallest column of least acc
+        }
         const unsigned long long m0 = __ballot(on && (move & 1)), m1 = __ballot(on && (move & 2));
         if((t & (WAVE - 1)) == lane) { w0 = m0; w1 = m1; }
         if(((t & (WAVE - 1)) == WAVE - 1 || t == nsteps - 1) && lane <= (t & (WAVE - 1)))
@@ -466,22 +527,26 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
     __threadfence();                                                  // the hand-over rows and the masks, before other lanes read them
   }
   const int last = (na - 1) & (WAVE - 1);
-  if(lane == last) out[cost0 + blockIdx.x] = v;                       // acc[na-1][nb-1]: the last cell of the last row's range
+  if constexpr(OPEN) {
+    if(lane == last) out[cost0 + blockIdx.x] = best;
+    end = __builtin_amdgcn_readlane(end, last);                       // (to every lane, as a scalar: the walk below is one)
+  } else if(lane == last) out[cost0 + blockIdx.x] = v;                // acc[na-1][nb-1]: the last cell of the last row's range
 
-  // L4 / K4: back along the moves
+  // L4 / K4: back along the moves; Q5: from (na - 1, end) until row 0 is reached, every move leaves its row
   float* pos = out + (size_t)p.pos0;
-  int i = na - 1, j = nb - 1;
+  int i = na - 1, j = OPEN ? end : nb - 1;
   int cur_s = -1, cur_b = -1, wlo = 0;
   uint4 w = make_uint4(0, 0, 0, 0);
-  for(int guard = min(na, nb); guard > 0; guard --) {
-    if(i == 0 && j == 0) break;
+  for(int guard = OPEN ? na : min(na, nb); guard > 0; guard --) {
+    if(OPEN ? i == 0 : i == 0 && j == 0) break;
     const int s = i >> 6, l = i & (WAVE - 1);
     if(s != cur_s) {
       if constexpr(BAND) {
         const int2 r = tab[min(s * WAVE + lane, na - 1)];
         int whi;
         band_slope_window(s * WAVE + lane < na ? r.x : 1, s * WAVE + lane < na ? r.y : 0, nb, wlo, whi);
-      } else { int h; align_slope_row((long long)s * WAVE, na, nb, wlo, h); }
+      } else if constexpr(OPEN) { int h; align_sub_row((long long)s * WAVE, nb, wlo, h); }
+      else { int h; align_slope_row((long long)s * WAVE, na, nb, wlo, h); }
     }
     const int t = j - wlo + l, blk = t & ~(WAVE - 1);
     if(t < 0 || t >= per_strip) break;                                // (a cell outside the region: no stored move leads there)
@@ -502,7 +567,9 @@ __global__ __launch_bounds__(WAVE) void k_align_slope_dtw_t(AlignDev d, const fl
     } else if(move == 2) { i --; j -= 2; }
     else { i --; j --; }
   }
-  if(lane == 0) pos[0] = 0.0f;                                        // row 0 is (0, 0) alone
+  if constexpr(OPEN) {                                                // row 0 is (0, begin) alone
+    if(lane == 0) { pos[0] = __fmul_rn((float)(2 * j), 0.5f); span[2 * blockIdx.x] = j; span[2 * blockIdx.x + 1] = end; }
+  } else if(lane == 0) pos[0] = 0.0f;                                 // row 0 is (0, 0) alone
 }
 
 // ---------------------------------------------------------------- P1: the pooled vectors of a coarse pass
@@ -569,6 +636,15 @@ int launch_align_slope_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const 
   if(geo == ALIGN_GEO_LINE) LAUNCH("k_align_line_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_LINE>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
   else if(geo == ALIGN_GEO_BAND) LAUNCH("k_align_band_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_BAND>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
   else LAUNCH("k_align_slope_dtw", k_align_slope_dtw_t<ALIGN_GEO_FULL>, dim3(d.n_pairs), dim3(WAVE), 0, d, plane, region, moves, row, out, cost0, center);
+  return 0;
+}
+
+int launch_align_sub_dtw(LaunchCtx* P, bool slope, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0,
+  float* last_rows, int* span) {
+  if(d.n_pairs == 0) return 0;
+  const int* none = nullptr; const int2* no_region = nullptr;      // (the full geometry reads neither a line nor a table of rows)
+  if(slope) LAUNCH("k_align_sub_slope_dtw", (k_align_slope_dtw_t<ALIGN_GEO_FULL, float*, int*>), dim3(d.n_pairs), dim3(WAVE), 0, d, plane, no_region, moves, row, out, cost0, none, last_rows, span);
+  else LAUNCH("k_align_sub_dtw", (k_align_dtw_t<ALIGN_GEO_FULL, float*, int*>), dim3(d.n_pairs), dim3(WAVE), 0, d, plane, moves, row, out, cost0, none, last_rows, span);
   return 0;
 }
 

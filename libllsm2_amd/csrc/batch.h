@@ -110,8 +110,10 @@ template <class T> struct DevBuf {
 // a third, ALIGN_AROUND, marks llsm_gpu_batch_align_around, whose band follows the caller's centre line and which is one call
 // for both patterns.  align_call(mode) indexes the batch's scratch sets and this table of the call's name and of its plane of
 // llsm_gpu_batch_debug_plane.  llsm_gpu_batch_align_pyramid runs two of these modes on scratch sets of its own, which this
-// table does not list: they have no plane.
-enum AlignMode { ALIGN_FULL = 0, ALIGN_BAND = 1, ALIGN_SLOPE = 2, ALIGN_AROUND = 4 };
+// table does not list: they have no plane.  A fourth bit, ALIGN_SUB, marks llsm_gpu_batch_align_sub, the whole matrix with free
+// ends, which is one call for both patterns (with ALIGN_SLOPE once its slope has been checked), never comes with ALIGN_BAND
+// and has a scratch set of its own outside the table too.
+enum AlignMode { ALIGN_FULL = 0, ALIGN_BAND = 1, ALIGN_SLOPE = 2, ALIGN_AROUND = 4, ALIGN_SUB = 8 };
 enum { ALIGN_CALLS = 5 };
 struct AlignCall { const char* name; int plane; };
 static const AlignCall kAlignCalls[ALIGN_CALLS] = {{"llsm_gpu_batch_align", 6}, {"llsm_gpu_batch_align_band", 9},
@@ -213,11 +215,13 @@ struct llsm_gpu_batch {
   // successful call (`cells` floats, 0: no call yet), the row one strip of 64 rows hands to the next (two rows under the
   // slope pattern), the device block [pos of every pair | cost of every pair], the moves (2 bits per lane and step of the
   // path kernel), the pair and tile tables, under ALIGN_BAND | ALIGN_SLOPE alone the rows of the region (rule K1: one
-  // {lo, hi} per row of every pair) and, under ALIGN_AROUND alone, the centre lines (rule A1: one int per row of every pair)
+  // {lo, hi} per row of every pair), under ALIGN_AROUND alone, the centre lines (rule A1: one int per row of every pair)
+  // and, under ALIGN_SUB alone, acc of every pair's last row (rule Q4: nb floats per pair) and {begin, end} of every pair
   // -- all grow-only
   struct AlignScratch {
     DevBuf<float> plane, row, out; DevBuf<uint4> moves; DevBuf<AlignPair> pairs; DevBuf<int4> tiles; DevBuf<int2> region;
     DevBuf<int> center;
+    DevBuf<float> last; DevBuf<int> span;
     long long cells = 0;
   } align[ALIGN_CALLS];
   // llsm_gpu_batch_align_pyramid: two sets of its own, [0] of the coarse pass and [1] of the fine pass, outside align[] and
@@ -226,6 +230,9 @@ struct llsm_gpu_batch {
   // -- all grow-only
   AlignScratch pyramid[2];
   DevBuf<float> pyramid_code; DevBuf<int4> pyramid_tab;
+  // llsm_gpu_batch_align_sub: a set of its own, outside align[] as the pyramid's are; its planes are read through
+  // llsm_gpu_batch_align_sub_plane, not through a plane number
+  AlignScratch align_sub;
   // unit selection (select.cpp), scratch of the batch given as t: the per-segment candidate lists of k_select_knn, planes
   // 7 and 8 of llsm_gpu_batch_debug_plane ([sel_frames][16] and [sel_frames][64] of the last successful
   // llsm_gpu_batch_select; sel_frames 0: no call yet), the back pointers (3 bits per state at bit 8 j, one word pair per

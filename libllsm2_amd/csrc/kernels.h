@@ -369,12 +369,18 @@ __host__ __device__ static inline void align_slope_row(long long i, int na, int 
                   h1 = (long long)nb - 1 - (r + 1) / 2;
   lo = (int)(l0 > l1 ? l0 : l1); hi = (int)(h0 < h1 ? h0 : h1);
 }
+// The columns lo ... hi of row i of a query against a take of nb frames under the slope pattern with free ends, rule Q1
+// (llsm_gpu_batch_align_sub): the cells reached from some cell of row 0, ceil(i / 2) ... nb - 1; there is no upper cut.
+__host__ __device__ static inline void align_sub_row(long long i, int nb, int& lo, int& hi) {
+  lo = (int)((i + 1) / 2); hi = nb - 1;
+}
 // One pair: rows [a0, a0 + na) of code_a against rows [b0, b0 + nb) of code_b (flat frame indices); its plane -- [na][nb],
 // or [na][2 band + 1] of a banded call -- starts at float cell0 of the planes, its moves at entry mv0 (`steps` entries of
 // 16 bytes per strip of 64 rows: the anti-diagonals of the strip whose column window is the widest), its hand-over row
 // (two rows of nb floats under the slope pattern) at float row0, its positions at float pos0 of the out block.  band is 0
 // and not read where the whole matrix is searched.  pad is 0 except for llsm_gpu_batch_align_band_slope, where the pair's rows
-// of the region (rule K1) start at entry pad of the table.
+// of the region (rule K1) start at entry pad of the table, and for llsm_gpu_batch_align_sub, where the pair's row of the
+// matching function (rule Q4: nb floats) starts at float pad of the rows of all pairs.
 struct AlignPair { int a0, na, b0, nb; int cell0, row0, pos0, band; long long mv0; int steps, pad; };
 #define ALIGN_TILE 64                                  // k_align_dist_t: cells per side of a workgroup's tile
 // The geometry of a row, which every kernel template is instantiated for: the whole matrix; the band of rule B1, whose
@@ -399,6 +405,12 @@ int launch_align_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float*
 // pairs[p].pad; row: two hand-over rows of nb floats per pair, out as above
 int launch_align_slope_dtw(LaunchCtx* P, AlignGeo geo, const AlignDev& d, const float* plane, const int2* region, uint4* moves,
   float* row, float* out, int cost0, const int* center);
+// Q3 - Q5 over whole-matrix planes (llsm_gpu_batch_align_sub), one wavefront per pair: the path kernels above with free
+// ends, D2's moves or with `slope` L3's over the rows of Q1; row and out as above (two hand-over rows under the pattern),
+// last_rows: acc of the last row of every pair, pair p's nb floats from float pairs[p].pad, +infinity left of the row's
+// range; span[2 p], span[2 p + 1]: the first and the last column of pair p's path
+int launch_align_sub_dtw(LaunchCtx* P, bool slope, const AlignDev& d, const float* plane, uint4* moves, float* row, float* out, int cost0,
+  float* last_rows, int* span);
 // P1 (llsm_gpu_batch_pool_code, llsm_gpu_batch_align_pyramid): the means of every `factor` (1 ... 64) consecutive rows of
 // CODE, the last group of an utterance over the rows it has.  tab[u] = (first source frame, frames, first coarse frame of
 // out, side: 0 reads code_a, 1 code_b) of pooled utterance u, n_tab >= 1 of them, the third member ascending from 0 and each
